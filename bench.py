@@ -23,6 +23,12 @@ Rank 0 prints ONE JSON line: metric cell-months/s (whole job), the roofline obje
 CPU baseline: the numpy oracle (a port of the reference's algorithm) timed on this host.  The run is also a GATE: it exits
 with code 3 (after printing the line, which says why in ``gate``) when a value lies beyond the north-star tolerance,
 a NaN pattern differs or the routed series is not bit-identical to the oracle's.
+
+``--dump-outputs DIR`` writes what the last timed step computed -- PET, AET, Q, Sav, ChStorage, Avg_ChFlow (per basin x, fun,
+nfev, nit for ``--workload calib``) -- as DIR/<name>.npy in float64: the cells whose outputs are all finite (the NaN cells
+of the synthetic forcing and the cells they drain into are left out and counted), a fixed, seeded sample of them when the
+arrays would exceed 64 MB together.  The synthetic world and forcing are seeded, so two builds run with the same arguments can be compared file
+for file.
 """
 import argparse
 import json
@@ -88,6 +94,53 @@ def algorithmic_bytes(ncell, nmonths, nlcs, abcd_spinup, routing_spinup):
         'abcd_sim': cm * 48,                                                       # 3 reads + 3 writes
         'mrtm_route': cm * 24 + ncell * routing_spinup * 8,                        # Q read (+spin-up re-read), 2 writes
     }
+
+
+DUMP_BUDGET_BYTES = 64 * 10 ** 6      # --dump-outputs: all files together stay below this
+DUMP_SEED = 20240807                  # --dump-outputs: which of the finite rows are kept when they exceed the budget
+
+
+def dump_outputs(out_dir, arrays, log):
+    """--dump-outputs: ``arrays`` (name -> device or host array, the outputs a caller of the timed path receives) ->
+    out_dir/<name>.npy in float64, downloaded one at a time.  The arrays with one row per cell (or basin) keep the same rows:
+    those finite in every one of them -- the synthetic forcing gives 0.1 % of the cells NaN precipitation, and like the
+    reference the run carries NaN runoff through ABCD and down the river networks (the bench's gate holds that NaN pattern
+    to the oracle's) -- and of those a seeded, sorted sample when they exceed the budget.  The rows kept depend only on the
+    shapes, the NaN pattern and the budget, so two builds run with the same arguments write files that compare element for
+    element.  Returns what was written, for the result line."""
+    def host(v):
+        return v.download() if hasattr(v, 'download') else np.asarray(v)
+
+    os.makedirs(out_dir, exist_ok=True)
+    shapes = {k: tuple(v.shape) for k, v in arrays.items()}
+    size = {k: int(np.prod(sh, dtype=np.int64)) for k, sh in shapes.items()}
+    nrow = max(sh[0] for sh in shapes.values() if sh)
+    per_row = [k for k, sh in shapes.items() if sh and sh[0] == nrow]
+    finite = np.ones(nrow, dtype=bool)
+    for k in per_row:
+        finite &= np.isfinite(host(arrays[k]).reshape(nrow, -1)).all(axis=1)
+    cand = np.flatnonzero(finite)
+    fixed = sum(8 * n for k, n in size.items() if k not in per_row)
+    row_bytes = sum(8 * size[k] // nrow for k in per_row)
+    keep = min(len(cand), (DUMP_BUDGET_BYTES - fixed) // row_bytes)
+    if keep < 1:
+        raise SystemExit('--dump-outputs: no finite row of the outputs fits into {} bytes'.format(DUMP_BUDGET_BYTES))
+    rows = cand if keep == len(cand) else np.sort(np.random.default_rng(DUMP_SEED).choice(cand, size=keep, replace=False))
+    files, total = [], 0
+    for k, v in arrays.items():
+        v = host(v)
+        if k in per_row:
+            v = v[rows]
+        v = np.ascontiguousarray(v, dtype=np.float64)
+        np.save(os.path.join(out_dir, k + '.npy'), v)
+        files.append(k + '.npy')
+        total += v.nbytes
+    info = {'dir': out_dir, 'files': files, 'bytes': int(total), 'dtype': 'float64', 'rows_total': int(nrow),
+            'rows_not_finite': int(nrow - len(cand)), 'rows_kept': int(len(rows)),
+            'rows': ('every finite row' if len(rows) == len(cand) else
+                     'seeded sample (seed {}) of the finite rows, sorted, every column'.format(DUMP_SEED))}
+    log('outputs of the last timed step: ' + json.dumps(info))
+    return info
 
 
 def cpu_mrtm_child(workdir):
@@ -541,6 +594,12 @@ def calib_measure(args, ctx, rank, world_size, dist, torch, backend, log):
     table = np.column_stack([x, fun, nfev, nit])
     if dist is not None:
         table = gather_results(table, owner, TorchGroup(dist, torch, backend))
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # what the calibration hands its caller after the last timed generation, per basin: parameters, objective, counts
+        nx = x.shape[1]
+        dumped = dump_outputs(args.dump_outputs, {'x': table[:, :nx], 'fun': table[:, nx], 'nfev': table[:, nx + 1],
+                                                  'nit': table[:, nx + 2]}, log)
     total_mcm = args.members * NCELL * (args.months + args.abcd_spinup)
     value = total_mcm * args.steps / elapsed
     ms = {k: ctx.timing(k) for k in ('calib_abcd', 'calib_kge', 'calib_de')}
@@ -565,6 +624,8 @@ def calib_measure(args, ctx, rank, world_size, dist, torch, backend, log):
         'kernels': {k: {'avg_ms': v[0] / args.steps, 'launches': v[1]} for k, v in ms.items()},
         'host_share_of_step': 1.0 - sum(v[0] for v in ms.values()) / (1e3 * elapsed),
     }
+    if dumped is not None:
+        result['dump_outputs'] = dumped
     # MEASURED issue fraction of the two marches: fp64 wave-instructions x 4 cycles over the cycles
     # the chip's SIMDs have in the marches' time.  SQ_INSTS_VALU of k_calib_march_m<true|false> from the committed counter pass
     # of `bench.py --workload calib` (tools/profile_round.sh); the time is this run's.  Refused when the pass is not about
@@ -669,6 +730,7 @@ def secondary_lines(ctx, pipe, args, log, kernel_times, pmc_i, insts_src, parity
     cargs = _ap.Namespace(**vars(args))
     cargs.workload, cargs.months, cargs.steps, cargs.warmup = 'calib', 480, 3, 1
     cargs.cpu_calib_seconds = 3.0
+    cargs.dump_outputs = None                # the dump is the primary line's
     try:
         line = calib_measure(cargs, ctx, 0, 1, None, None, None, log)
         out['calib'] = {kk: line[kk] for kk in ('metric', 'value', 'unit', 'steps', 'warmup', 'ms_per_step', 'dtype', 'data', 'config',
@@ -763,7 +825,12 @@ def main():
                     help='pm_abcd_mrtm: "staged" = the three stages strictly one after the other; "fed" = the routing kernel '
                          'starts after the first max(spin-ups) months and the rest of PM and ABCD runs beside it (xh_run_fused '
                          'mode 1, DESIGN.md 4.7); "auto" = the library default')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write the outputs of the last one as DIR/<name>.npy (float64; the cells '
+                         'whose outputs are all finite, a fixed, seeded sample of them when they exceed 64 MB together)')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
     if args.cpu_mrtm_child:                                     # CPU-only child of the baseline leg: no GPU code is imported
         return cpu_mrtm_child(args.cpu_mrtm_child)
     if args.gpus > 1 and 'RANK' not in os.environ and 'WORLD_SIZE' not in os.environ:
@@ -916,6 +983,12 @@ def main():
         units_per_step = NCELL * args.months * world_size
         parallelism = ('{} independent scenarios, one per GPU'.format(world_size) if world_size > 1 else
                        'one world on one GPU')
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # before anything below runs the pipeline again: what the last timed step left, in grid order
+        names = ('pet', 'aet', 'q', 'sav') + (('chs', 'avg') if 'mrtm' in args.stages else ())
+        ctx.sync()
+        dumped = dump_outputs(args.dump_outputs, {k: (gather.out if sharded else pipe.out)[k] for k in names}, log)
     info = pipe.plan.info() if pipe.plan is not None else {}
     if pipe.plan is not None:
         info['form'] = 'bit-exact kernels, every unit in pair form'
@@ -1062,6 +1135,8 @@ def main():
         # the selective plain form has been learnt (routing_plan.form)
         'first_calls': timed.first_calls[:2],
     }
+    if dumped is not None:
+        result['dump_outputs'] = dumped
     gate_failed = False
     if sharded:
         result['gather'] = gather.report()

@@ -282,3 +282,50 @@ def test_bench_starts_its_own_ranks_without_a_launcher():
         got = json.loads(out.stdout.strip().splitlines()[-1])
         assert got['RANK'] == '0' and got['LOCAL_RANK'] == '0' and got['WORLD_SIZE'] == str(n)
         assert got['MASTER_ADDR'] == '127.0.0.1' and int(got['MASTER_PORT']) > 0
+
+
+def test_bench_dump_outputs_sample(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: every output as <name>.npy in float64, every value finite.  Rows (cells) with a NaN or an
+    inf in any per-cell output are left out of all of them and counted; above the byte budget the finite rows keep the same
+    seeded, sorted sample; the total stays within the budget, and a second dump is identical."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location('bench_under_test', os.path.join(ROOT, 'bench.py'))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    ncell, nm = 5000, 24
+    rng = np.random.default_rng(3)
+    arrays = {k: rng.standard_normal((ncell, nm)) for k in ('pet', 'q', 'chs')}
+    arrays['q'][7, 5:] = np.nan                          # runoff NaN from one month on
+    arrays['chs'][[7, 11, 4000]] = np.nan                # routed NaN: that cell and the ones it drains into
+    arrays['pet'][12, 3] = np.inf
+    bad = [7, 11, 12, 4000]
+    good = np.setdiff1d(np.arange(ncell), bad)
+    small = {'x': rng.standard_normal((9, 5))}
+    log = lambda msg: None                                # noqa: E731
+
+    info = bench.dump_outputs(str(tmp_path / 'all'), dict(arrays, **small), log)
+    assert sorted(info['files']) == sorted(k + '.npy' for k in list(arrays) + list(small))
+    assert info['rows_not_finite'] == len(bad) and info['rows_kept'] == len(good) and info['rows'] == 'every finite row'
+    for k, v in arrays.items():
+        got = np.load(str(tmp_path / 'all' / (k + '.npy')))
+        assert got.dtype == np.float64 and np.isfinite(got).all() and np.array_equal(got, v[good])
+    assert np.array_equal(np.load(str(tmp_path / 'all' / 'x.npy')), small['x'])
+
+    budget = 3 * 8 * nm * 400 + 8 * small['x'].size + 100          # room for 400 cells of the three per-cell arrays
+    monkeypatch.setattr(bench, 'DUMP_BUDGET_BYTES', budget)
+    for d in ('a', 'b'):
+        info = bench.dump_outputs(str(tmp_path / d), dict(arrays, **small), log)
+        assert info['bytes'] <= budget and info['rows_kept'] == 400 and 'seeded sample' in info['rows']
+    rows = np.sort(np.random.default_rng(bench.DUMP_SEED).choice(good, size=400, replace=False))
+    for k, v in arrays.items():
+        a, b = (np.load(str(tmp_path / d / (k + '.npy'))) for d in ('a', 'b'))
+        assert a.shape == (400, nm) and np.array_equal(a, b) and np.array_equal(a, v[rows]) and np.isfinite(a).all()
+
+    # the calibration's per-basin outputs: 1-D and 2-D arrays of one row per basin share the rows
+    basins = {'x': rng.standard_normal((9, 5)), 'fun': rng.standard_normal(9), 'nit': np.arange(9, dtype=np.int32)}
+    basins['fun'][2] = np.nan
+    info = bench.dump_outputs(str(tmp_path / 'calib'), basins, log)
+    assert info['rows_not_finite'] == 1
+    keep = np.array([0, 1, 3, 4, 5, 6, 7, 8])
+    for k, v in basins.items():
+        assert np.array_equal(np.load(str(tmp_path / 'calib' / (k + '.npy'))), v[keep].astype(np.float64))
