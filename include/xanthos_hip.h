@@ -84,7 +84,7 @@ int xh_transpose(xh_ctx *ctx, const double *d_src, int64_t rows, int64_t cols, d
 
 /* HIP-event timing of the kernels each entry point launches, accumulated per kernel name on the context's stream.
  * Names: "pm_pet", "abcd_spinup", "abcd_basin_mean", "abcd_sim", "mrtm_route", "calib_abcd", "calib_kge", "calib_de",
- * "agg_time", "agg_spatial", "drought_thresh", "drought_stats".  xh_timing_get waits for the stream, then returns total milliseconds and launch count. */
+ * "agg_time", "agg_spatial", "drought_thresh", "drought_stats", "hargreaves_pet", "gwam_spinup", "gwam_sim".  xh_timing_get waits for the stream, then returns total milliseconds and launch count. */
 int xh_timing_reset(xh_ctx *ctx);
 /* a caller-named span on the context's stream, read back with xh_timing_get like the library's own timers (one open
  * at a time): e.g. what a step still spends in the write-out gather after the routing kernel has ended                */
@@ -130,6 +130,32 @@ int xh_abcd(xh_ctx *ctx, int64_t ncell, int32_t nmonths, int32_t spinup, int32_t
             const double *d_pet, const double *d_precip, const double *d_tmin,
             double *d_aet, double *d_q, double *d_sav,
             double *d_sm0, double *d_gw0);          /* optional out [n_groups]: post-spin-up initial state */
+
+/* ------------------------------------------------------------------ Hargreaves PET
+ * Replaces pet/hargreaves.py:calculate_pet (:17-73) over every month at once, with the input preparation of
+ * components.py:144-187 (nan_to_num of T and D) and data_load.py:83-84 (negative DTR -> 0) applied on the device to the
+ * forcing as uploaded.  h_solar_dec / h_dr: utils/general.py:calc_sinusoidal_factor (:53-90) per month; h_ndays: days of
+ * each month (general.py set_month_arrays).  d_lat_rad: radians(coords[:, 2]) (data_load.py:71-72).
+ * Asynchronous (one stream synchronisation for the small month table).                                             */
+int xh_hargreaves_pet(xh_ctx *ctx, int64_t ncell, int32_t nmonths,
+                      const double *d_temp, const double *d_dtr,  /* [ncell, nmonths]                                 */
+                      const double *d_lat_rad,                    /* [ncell]                                          */
+                      const double *h_solar_dec, const double *h_dr, const double *h_ndays,   /* host, [nmonths]  */
+                      double *d_pet);                             /* out [ncell, nmonths]                             */
+
+/* ------------------------------------------------------------------ GWAM runoff
+ * Replaces runoff/gwam.py:runoffgen (:18-88) driven month by month as components.py:298-384 / configurations.py:54-121
+ * drive it: a spin-up pass over months [0, spinup) from d_sm0 whose final soil moisture starts the simulation over
+ * [0, nmonths).  precip_col_spinup / precip_col_sim: the column of d_precip every month of that pass reads (the
+ * reference's self.P, components.py:230 and :334: runoff_spinup - 1 and nmonths - 1); -1 = month m reads column m.
+ * indexing: the soil-moisture marker of water bodies (999, gwam.py:18).  nmonths must be even and the [ncell, nmonths]
+ * arrays 16-byte aligned.  d_aet, d_q, d_sav, d_sm_end (out [ncell]: soil moisture after the last month) may be NULL. */
+int xh_gwam(xh_ctx *ctx, int64_t ncell, int32_t nmonths, int32_t spinup, int32_t precip_col_spinup,
+            int32_t precip_col_sim, double indexing,
+            const double *d_pet, const double *d_precip,  /* [ncell, nmonths]                                        */
+            const double *d_sm_max, const double *d_sm0,  /* [ncell]: max soil moisture, initial soil moisture       */
+            double *d_aet, double *d_q, double *d_sav,    /* out [ncell, nmonths]                                    */
+            double *d_sm_end);
 
 /* ------------------------------------------------------------------ MRTM routing
  * xh_route_plan_create replaces the per-call topology work of routing/mrtm.py:upstream_genmatrix (:194-230):

@@ -81,6 +81,8 @@ SIGNATURES = {
     'xh_pm_pet': (c_int, [_P, POINTER(PmTables), c_int64, c_int32, c_int32, c_int32, _P, c_int32, c_int32,
                           _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     'xh_abcd': (c_int, [_P, c_int64, c_int32, c_int32, c_int32, _P, _P, c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    'xh_hargreaves_pet': (c_int, [_P, c_int64, c_int32, _P, _P, _P, _P, _P, _P, _P]),
+    'xh_gwam': (c_int, [_P, c_int64, c_int32, c_int32, c_int32, c_int32, c_double, _P, _P, _P, _P, _P, _P, _P, _P]),
     'xh_route_plan_create': (c_int, [_P, c_int64, _P, _P, _P, POINTER(c_void_p)]),
     'xh_route_plan_destroy': (None, [_P]),
     'xh_route_plan_info': (c_int, [_P, POINTER(c_int64)]),
@@ -122,7 +124,7 @@ SIGNATURES = {
 _lib = None
 
 
-ABI_VERSION = 5        # xh_abi_version() of the library these signatures describe
+ABI_VERSION = 6        # xh_abi_version() of the library these signatures describe
 
 
 def lib():
@@ -421,6 +423,21 @@ class Context:
         self._check(lib().xh_abcd(self.handle, ncell, nmonths, spinup, n_groups, _host_ptr(bi), _host_ptr(pi),
                                   npar_rows, _dptr(pars), _dptr(pet), _dptr(precip), _dptr(tmin), _dptr(aet),
                                   _dptr(q), _dptr(sav), _dptr(sm0), _dptr(gw0)))
+
+    # ---- Hargreaves PET / GWAM runoff
+    def hargreaves_pet(self, ncell, nmonths, temp, dtr, lat_rad, solar_dec, dr, ndays, pet):
+        """temp / dtr / lat_rad / pet device arrays; solar_dec / dr / ndays host arrays of nmonths values."""
+        tabs = [np.ascontiguousarray(a, dtype=np.float64) for a in (solar_dec, dr, ndays)]
+        if any(t.size != nmonths for t in tabs):
+            raise ValueError('solar_dec, dr and ndays must have nmonths entries')
+        self._check(lib().xh_hargreaves_pet(self.handle, ncell, nmonths, _dptr(temp), _dptr(dtr), _dptr(lat_rad),
+                                            _host_ptr(tabs[0]), _host_ptr(tabs[1]), _host_ptr(tabs[2]), _dptr(pet)))
+
+    def gwam(self, ncell, nmonths, spinup, precip_col_spinup, precip_col_sim, indexing, pet, precip, sm_max, sm0, aet,
+             q, sav, sm_end=None):
+        self._check(lib().xh_gwam(self.handle, ncell, nmonths, spinup, precip_col_spinup, precip_col_sim, float(indexing),
+                                  _dptr(pet), _dptr(precip), _dptr(sm_max), _dptr(sm0), _dptr(aet), _dptr(q), _dptr(sav),
+                                  _dptr(sm_end)))
 
     # ---- MRTM
     def route_plan(self, indptr, indices, sign):

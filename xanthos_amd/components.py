@@ -16,7 +16,7 @@ import numpy as np
 from . import _hip, launch
 from .calibrate import calibrate_abcd as calib_mod
 from .data_load import DataLoader
-from .ini_reader import ValidationException
+from .ini_reader import ValidationException, check_modules
 from .pipeline import DevicePipeline
 from .utils import set_month_arrays
 
@@ -93,14 +93,19 @@ class Components:
         global pet_mod, runoff_mod, routing_mod
         if self.s.pet_module == 'pm':
             from .pet import penman_monteith as pet_mod
+        elif self.s.pet_module == 'hargreaves':
+            from .pet import hargreaves as pet_mod
         elif self.s.pet_module != 'none':
             raise ValidationException("pet_module '{}' is not part of the MI355X hot path".format(self.s.pet_module))
         if self.s.runoff_module == 'abcd':
             from .runoff import abcd as runoff_mod
+        elif self.s.runoff_module == 'gwam':
+            from .runoff import gwam as runoff_mod
         elif self.s.runoff_module != 'none':
             raise ValidationException("runoff_module '{}' is not part of the MI355X hot path".format(self.s.runoff_module))
         if self.s.routing_module == 'mrtm':
             from .routing import mrtm as routing_mod
+        check_modules(self.s)
 
     # ------------------------------------------------------------------ stage by stage (host arrays)
     def calculate_pet(self):
@@ -108,6 +113,9 @@ class Components:
         if self.s.pet_module == 'pm':
             return pet_mod.run_pmpet(self.data, self.s.ncell, self.s.pm_nlcs, self.s.StartYear, self.s.EndYear,
                                      self.s.pm_water_idx, self.s.pm_snow_idx, self.s.pm_lc_years, device=self.s.device)
+        if self.s.pet_module == 'hargreaves':
+            return pet_mod.run_hargreaves(self.data.temp, self.data.dtr, self.data.lat_radians, self.s.StartYear,
+                                          self.s.EndYear, device=self.s.device)
         if self.s.pet_module == 'none':
             return self.data.pet_out
 
@@ -117,6 +125,12 @@ class Components:
             rg = runoff_mod.abcd_execute(n_basins=self.s.n_basins, basin_ids=self.data.basin_ids, pet=pet,
                                          precip=self.data.precip, tmin=self.data.tmin, calib_file=self.s.calib_file,
                                          n_months=self.s.nmonths, spinup_steps=self.s.runoff_spinup, jobs=self.s.ro_jobs)
+            self.PET, self.AET, self.Q, self.Sav = rg
+        elif self.s.runoff_module == 'gwam':
+            self._check_gwam_spinup()
+            rg = runoff_mod.gwam_execute(pet, self.data.precip, self.data.soil_moisture, self.data.sm_prev,
+                                         self.s.runoff_spinup, self.s.nmonths, precipitation=self.s.gwam_precipitation,
+                                         device=self.s.device)
             self.PET, self.AET, self.Q, self.Sav = rg
         elif getattr(self.s, 'alt_runoff', None) is not None:
             self.Q = np.load(self.s.alt_runoff)
@@ -167,6 +181,8 @@ class Components:
         logging.info('---{} in progress...'.format(notify))
         t0 = time.time()
         s, d = self.s, self.data
+        if s.pet_module == 'hargreaves' and run_pet:
+            return self._simulation_hgm(run_runoff, run_routing, t0, notify)
         full = (s.pet_module == 'pm' and s.runoff_module == 'abcd' and run_pet and run_runoff)
         if not full:
             pet_out = self.calculate_pet()
@@ -214,6 +230,71 @@ class Components:
         logging.info('\tPET + runoff + routing kernels: {:.3f} seconds'.format(time.time() - t))
         self._log_stage_rates(ctx, pipe, um is not None)
         self._host = {}                    # the six results stay in HBM until they are read (or written)
+        self.pipe = pipe
+        self.timings['download'] = 0.0
+        logging.info('---{0} has finished successfully: {1} seconds ---'.format(notify, time.time() - t0))
+
+    def _check_gwam_spinup(self):
+        n = self.s.runoff_spinup
+        if n < 1 or n > self.s.nmonths:
+            # the reference dies here: an IndexError in its PET step loop beyond the last month (components.py:330-340),
+            # an AttributeError with no step at all (:337-340 take the whole-series branch, which Hargreaves lacks)
+            raise ValidationException('[[gwam]] runoff_spinup = {} must lie in [1, nmonths = {}].'.format(n, self.s.nmonths))
+
+    def _simulation_hgm(self, run_runoff, run_routing, t0, notify):
+        """Hargreaves PET -> GWAM / ABCD (-> MRTM), device resident (configurations.py:104-121, components.py:298-384).
+        GWAM's spin-up pass and its simulation are one xh_gwam call; the spin-up pass's routing is skipped -- it changes
+        nothing (streamrouting does not mutate its inputs and calculate_routing starts again from data.chs_prev)."""
+        from .pipeline import HgmPipeline
+        from .runoff import abcd as abcd_mod
+        s, d = self.s, self.data
+        if self.group is not None and self.group.size > 1:
+            raise ValidationException('{}: Hargreaves PET and GWAM runoff run on one GPU; sharding them over several GPUs '
+                                      'is not implemented.'.format(s.mod_cfg))
+        runoff = s.runoff_module if run_runoff else 'none'
+        if runoff == 'gwam':
+            self._check_gwam_spinup()
+        elif runoff == 'abcd':
+            abcd_mod._check_spinup(s.runoff_spinup, s.nmonths)
+        ctx = _hip.get_context(s.device)
+        t = time.time()
+        um = self.topology() if (run_routing and s.routing_module == 'mrtm') else None
+        self.timings['topology'] = time.time() - t
+        t = time.time()
+        kw = {}
+        if runoff == 'gwam':
+            kw = dict(sm_max=d.soil_moisture, sm0=d.sm_prev, gwam_spinup=s.runoff_spinup,
+                      precipitation=s.gwam_precipitation)
+        elif runoff == 'abcd':
+            kw = dict(basin_ids=d.basin_ids, abcd_pars=s.calib_file if isinstance(s.calib_file, np.ndarray) else
+                      np.load(s.calib_file), abcd_spinup=s.runoff_spinup, use_snow=d.tmin is not None)
+        pipe = HgmPipeline(ctx, ncell=s.ncell, nmonths=s.nmonths, start_year=s.StartYear, runoff_module=runoff,
+                           lat_radians=d.lat_radians, um=um, flow_dist=d.flow_dist if um is not None else None,
+                           velocity=d.str_velocity if um is not None else None, area=d.area,
+                           routing_spinup=getattr(s, 'routing_spinup', 0), chs_prev=getattr(d, 'chs_prev', None),
+                           route_flags=self.route_flags(), **kw)
+        self.timings['plan'] = time.time() - t
+        t = time.time()
+        pipe.set_forcing({'temp': d.temp, 'dtr': d.dtr, 'precip': getattr(d, 'precip', None) if runoff != 'none' else None,
+                          'abcd_tmin': getattr(d, 'tmin', None) if runoff == 'abcd' else None})
+        ctx.sync()
+        self.timings['upload'] = time.time() - t
+        t = time.time()
+        ctx.timing_reset()
+        pipe.run()
+        ctx.sync()
+        self.timings['kernels'] = time.time() - t
+        logging.info('\tPET + runoff + routing kernels: {:.3f} seconds'.format(time.time() - t))
+        cm = pipe.ncell * pipe.nmonths
+        for name, nbytes in (('hargreaves_pet', cm * 24), ('gwam_spinup', pipe.ncell * pipe.gwam_spinup * 16),
+                             ('gwam_sim', cm * (40 if s.gwam_precipitation == 'monthly' else 32) if runoff == 'gwam' else 0),
+                             ('abcd_sim', cm * 48), ('mrtm_route', cm * 24 + pipe.ncell * pipe.routing_spinup * 8)):
+            ms, n = ctx.timing(name)
+            if n:
+                logging.info('\t{:14s} {:8.3f} ms, {:7.1f} GB/s of {} MB algorithmic traffic'.format(
+                    name, ms / n, nbytes / (ms / n) / 1e6, nbytes // 1000000))
+                self.timings['kernel_' + name] = ms / n / 1e3
+        self._host = {}
         self.pipe = pipe
         self.timings['download'] = 0.0
         logging.info('---{0} has finished successfully: {1} seconds ---'.format(notify, time.time() - t0))

@@ -5,15 +5,17 @@ from .components import Components
 
 
 class ConfigRunner:
-    PET_COMPONENTS = ['pm']                 # the reference also lists hs / hargreaves / thornthwaite (:61)
-    RUNOFF_COMPONENTS = ['abcd']            # reference: + gwam (:62)
+    PET_COMPONENTS = ['pm', 'hargreaves']   # the reference also lists hs / thornthwaite (:61)
+    RUNOFF_COMPONENTS = ['abcd', 'gwam']    # (:62)
     ROUTING_COMPONENTS = ['mrtm']           # (:63)
 
     def __init__(self, config):
         self.run_pet = config.pet_module in self.PET_COMPONENTS
         self.run_runoff = config.runoff_module in self.RUNOFF_COMPONENTS
         self.run_routing = config.routing_module in self.ROUTING_COMPONENTS
-        # pm / abcd / mrtm iterate internally: all *_timestep are 0 and no whole-model spin-up (:69-85)
+        # every stage iterates internally: all *_timestep are 0 and no whole-model spin-up (:69-85).  The reference runs
+        # Hargreaves and GWAM month by month and GWAM's spin-up as a pass of the whole model (:104-113); here one
+        # xh_gwam call does the spin-up pass and the simulation (components.Components.simulation)
         self.pet_timestep = self.runoff_timestep = self.routing_timestep = 0
         self.spinup = False
         self.config = config

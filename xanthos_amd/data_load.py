@@ -8,6 +8,9 @@ changes its inputs:
   ``settings.device_transforms = False``; ``tairprev`` is tas shifted by one CELL, zeros for cell 0 (:127-129);
   land cover and elevation nan_to_num (:132,:135); 13 per-class parameters + 4 per-(class, month) tables (:94-117)
 * precipitation keeps NaN (:186); ABCD tmin nan_to_num (:194-195), optional
+* Hargreaves: temperature and daily temperature range as loaded (the kernel clamps and cleans them), latitude in
+  radians (:71-84); GWAM: the maximum-soil-moisture composite with the water bodies and the initial soil moisture
+  (:149-182, :226-260)
 * routing: flow distance < 1000 -> 1000 (:204-205), velocity < 0 -> 0 (:207-208), 2-D DRT maps flattened with the
   reference's ``vectorize`` (:415-425), zero initial channel storage in historic mode (:427-438)
 
@@ -123,13 +126,24 @@ class DataLoader:
             self._tairprev = None        # tairprev_load: built on first use (the device pipeline derives it in HBM)
             self.lct_load = np.nan_to_num(load_file(s.pm_lct))
             self.elev = np.nan_to_num(load_file(s.pm_elev))
+        elif s.pet_module == 'hargreaves':
+            # temperature and daily temperature range (data_load.py:74-84): memory maps, untouched on the host -- the
+            # negative-DTR clamp and nan_to_num of both (components.py:144-187) run in the Hargreaves kernel
+            self.temp = self.load_to_array(s.TemperatureFile, 'TemperatureFile', key=getattr(s, 'TempVarName', None))
+            self.dtr = self.load_to_array(s.DailyTemperatureRangeFile, 'DailyTemperatureRangeFile',
+                                          key=getattr(s, 'DTRVarName', None))
         elif s.pet_module == 'none':
             self.pet_out = self.load_to_array(s.pet_file, 'pet_file')
+        self.lat_radians = np.radians(self.latitude)          # data_load.py:71-72
 
         if s.runoff_module == 'abcd':
             self.precip = self.load_to_array(s.PrecipitationFile, 'PrecipitationFile', key=getattr(s, 'PrecipVarName', None))
             self.tmin = None if s.TempMinFile is None else self.load_to_array(
                 s.TempMinFile, 'TempMinFile', nan_to_num=True, key=getattr(s, 'TempMinVarName', None))
+
+        elif s.runoff_module == 'gwam':
+            self.precip = self.load_to_array(s.PrecipitationFile, 'PrecipitationFile', key=getattr(s, 'PrecipVarName', None))
+            self.soil_moisture, self.sm_prev = self.load_soil_moisture()
 
         if s.routing_module == 'mrtm':
             self.flow_dist = self.load_routing_data(s.flow_distance, rep_val=1000)
@@ -166,6 +180,30 @@ class DataLoader:
         if arr.shape[0] != s.ncell:
             raise ValidationException('ChStorageFile has {} cells, expected {}'.format(arr.shape[0], s.ncell))
         return np.ascontiguousarray(arr[:, -1])
+
+    def load_soil_moisture(self):
+        """GWAM's maximum soil moisture and initial soil moisture (data_load.py:149-182, :226-260): the max_soil_moisture
+        table (one header row), overwritten at the water bodies of the two 1-based (cell, value) tables, lakes_msm and
+        addit_water_msm (values truncated to integers, 999 marks a water body); initial soil moisture half of it in
+        historic mode, the last column of SavFile in future mode."""
+        s = self.s
+        sm = np.asarray(load_file(s.max_soil_moisture, 1), dtype=float).reshape(-1).copy()
+        if sm.shape[0] != s.ncell:
+            raise ValidationException('max_soil_moisture has {} cells, expected {}'.format(sm.shape[0], s.ncell))
+        for f in (s.lakes_msm, s.addit_water_msm):
+            tab = np.asarray(load_file(f), dtype=float).reshape(-1, 2).astype(int)
+            cells = tab[:, 0] - 1
+            if cells.size and (cells.min() < 0 or cells.max() >= s.ncell):
+                raise ValidationException('{}: cell ids outside 1..{}'.format(f, s.ncell))
+            sm[cells] = tab[:, 1]
+        if str(getattr(s, 'HistFlag', 'True')) == 'True':
+            return sm, 0.5 * sm
+        sav = np.asarray(load_file(s.SavFile, 0, getattr(s, 'SavVarName', None)), dtype=float)
+        if sav.ndim == 1:
+            sav = sav[:, None]
+        if sav.shape[0] != s.ncell:
+            raise ValidationException('SavFile has {} cells, expected {}'.format(sav.shape[0], s.ncell))
+        return sm, np.ascontiguousarray(sav[:, -1])
 
     def load_to_array(self, f, var_name, nan_to_num=False, key=None):
         # the big forcing files stay on disk as read-only memory maps (mmap_inputs = False restores host arrays)

@@ -3,8 +3,8 @@
 The reference parses the file with ``configobj`` (not installed here) and flattens it into an attribute bag
 (ini_reader.py:24-607).  This module has its own small parser for the same syntax (``[Section]``, nested
 ``[[subsection]]``, ``key = value``, ``#`` comments, comma lists, optional quotes) and builds the same attributes for
-the sections the hot path reads: ``[Project]``, ``[PET][[penman-monteith]]``, ``[Runoff][[abcd]]``,
-``[Routing][[mrtm]]`` and ``[Calibrate]``.  Selector strings are lower-cased and validated exactly like the
+the sections the hot path reads: ``[Project]``, ``[PET][[penman-monteith]]`` / ``[[hargreaves]]``,
+``[Runoff][[abcd]]`` / ``[[gwam]]``, ``[Routing][[mrtm]]`` and ``[Calibrate]``.  Selector strings are lower-cased and validated exactly like the
 reference (:214, :309, :397); selectors that belong to other reference modules are rejected with a clear message
 because only the MI355X hot path is implemented here.  ``update()`` keeps the in-memory override hook (:598-607).
 """
@@ -63,11 +63,39 @@ def _value(text):
     return parts[0] if parts else ''
 
 
+def check_modules(s):
+    """Module combinations the reference accepts in its reader but cannot run (components.py:144-187, :229-232), and the
+    GWAM features this package leaves out: each a ValidationException here instead of a crash later."""
+    pet, runoff = s.pet_module, s.runoff_module
+    if runoff == 'gwam' and pet == 'none':
+        raise ValidationException("runoff_module = gwam needs pet_module = hargreaves: the reference's GWAM driver takes its "
+                                  "precipitation from the Hargreaves step loop (components.py:230, :334), so with a PET file "
+                                  "it has none.")
+    if runoff == 'gwam' and pet != 'hargreaves':
+        raise ValidationException("runoff_module = gwam runs with pet_module = hargreaves only, not '{}': the reference's "
+                                  "GWAM driver reads the temperature only Hargreaves loads (components.py:144-160).".format(pet))
+    if runoff == 'gwam' and getattr(s, 'calibrate', 0):
+        raise ValidationException('Calibrate = 1 calibrates the ABCD parameters; there is no calibration of GWAM.')
+
+
+def _subsection(cfg, name, section):
+    m = cfg.get(name)
+    if not isinstance(m, dict):
+        raise ValidationException('[{0}] selects {1} but has no [[{1}]] subsection.'.format(section, name))
+    return m
+
+
+def _key(m, key, name):
+    if key not in m:
+        raise ValidationException('{} is required in the [[{}]] section of the config file.'.format(key, name))
+    return m[key]
+
+
 class ConfigReader:
     """Attribute bag of settings for one run (ini_reader.py:24)."""
 
-    PET_OTHER = ('hargreaves', 'hs', 'thornthwaite')
-    RUNOFF_OTHER = ('gwam',)
+    PET_OTHER = ('hs', 'thornthwaite')
+    RUNOFF_OTHER = ()
 
     def __init__(self, ini):
         c = parse_ini(ini) if not isinstance(ini, dict) else ini
@@ -134,6 +162,7 @@ class ConfigReader:
             if getattr(self, flag):
                 raise ValidationException("{} = 1: this post-processor belongs to the reference's host-side modules and "
                                           "is not part of this package.".format(flag))
+        check_modules(self)
         if self.calibrate:
             if 'Calibrate' not in c:
                 raise ValidationException('Calibrate = 1 but no [Calibrate] section.')
@@ -162,6 +191,14 @@ class ConfigReader:
             self.pm_laimin = os.path.join(self.pet_dir, 'gcam_laimin.csv')
             self.pm_laimax = os.path.join(self.pet_dir, 'gcam_laimax.csv')
             self.pm_elev = os.path.join(self.pet_dir, 'elev.npy')
+        elif self.pet_module == 'hargreaves':
+            m = _subsection(cfg, 'hargreaves', 'PET')
+            self.pet_dir = os.path.join(self.PET, _key(m, 'pet_dir', 'hargreaves'))
+            # climate data (ini_reader.py:216-243): file names relative to pet_dir, optional NetCDF variable names
+            self.TemperatureFile = os.path.join(self.pet_dir, _key(m, 'TemperatureFile', 'hargreaves'))
+            self.TempVarName = m.get('TempVarName')
+            self.DailyTemperatureRangeFile = os.path.join(self.pet_dir, _key(m, 'DailyTemperatureRangeFile', 'hargreaves'))
+            self.DTRVarName = m.get('DTRVarName')
         elif self.pet_module == 'none':
             try:
                 self.pet_file = cfg['pet_file']
@@ -212,6 +249,8 @@ class ConfigReader:
                     if os.environ.get('XH_STRICT_FUTURE') == '1':
                         raise ValidationException(msg)
                     logging.warning(msg)
+        elif self.runoff_module == 'gwam':
+            self.configure_gwam(_subsection(cfg, 'gwam', 'Runoff'))
         elif self.runoff_module == 'none':
             pass
         elif self.runoff_module in self.RUNOFF_OTHER:
@@ -220,6 +259,35 @@ class ConfigReader:
         else:
             raise ValidationException("ERROR: Runoff module '{0}' not found. Please check "
                                       "spelling and try again.".format(self.runoff_module))
+
+    def configure_gwam(self, m):
+        """[[gwam]] (ini_reader.py:311-350)."""
+        self.ro_model_dir = os.path.join(self.RunoffDir, _key(m, 'runoff_dir', 'gwam'))
+        try:
+            self.runoff_spinup = int(_key(m, 'runoff_spinup', 'gwam'))
+        except ValueError:
+            raise ValidationException('runoff_spinup in [[gwam]] must be an integer')
+        # built-in files: maximum soil moisture and the two water-body tables
+        for key in ('max_soil_moisture', 'lakes_msm', 'addit_water_msm'):
+            setattr(self, key, os.path.join(self.ro_model_dir, _key(m, key, 'gwam')))
+        # future mode: channel storage and soil moisture at the end of the historical run, all four keys required
+        self.ChStorageFile = self.ChStorageVarName = self.SavFile = self.SavVarName = None
+        if not self.historic:
+            missing = [k for k in ('ChStorageFile', 'ChStorageVarName', 'SavFile', 'SavVarName') if k not in m]
+            if missing:
+                raise ValidationException('Error: ChStorageFile, ChStorageVarName, SavFile and SavVarName are required '
+                                          'in [[gwam]] for Future Mode (missing: {}).'.format(', '.join(missing)))
+            self.ChStorageFile, self.ChStorageVarName = m['ChStorageFile'], m['ChStorageVarName']
+            self.SavFile, self.SavVarName = m['SavFile'], m['SavVarName']
+        self.PrecipitationFile = os.path.join(self.ro_model_dir, _key(m, 'PrecipitationFile', 'gwam'))
+        self.PrecipVarName = m.get('PrecipVarName')
+        # (not a key of the reference) which precipitation GWAM reads.  `reference` (default): what the reference's driver
+        # hands it -- ONE column for every month of a pass, runoff_spinup - 1 in the spin-up and nmonths - 1 in the
+        # simulation (components.py:230, :334).  `monthly`: month m's precipitation in month m.
+        self.gwam_precipitation = str(m.get('precipitation', 'reference')).strip().lower()
+        if self.gwam_precipitation not in ('reference', 'monthly'):
+            raise ValidationException("[[gwam]] precipitation must be 'reference' or 'monthly', not '{}'".format(
+                self.gwam_precipitation))
 
     def configure_routing(self, cfg):
         """[Routing] / [[mrtm]] (ini_reader.py:390-423)."""

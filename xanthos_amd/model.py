@@ -48,6 +48,14 @@ class Xanthos:
             h.close()
 
 
+def check_single_device(config):
+    """Hargreaves and GWAM run on one GPU: the basin sharding covers the pm / abcd / mrtm stages only."""
+    from .ini_reader import ValidationException
+    if config.pet_module == 'hargreaves' or config.runoff_module == 'gwam':
+        raise ValidationException('{}: Hargreaves PET and GWAM runoff run on one GPU; sharding them over several GPUs is '
+                                  'not implemented.'.format(config.mod_cfg))
+
+
 def run_model(config_file, gpus=None):
     """Run Xanthos from a configuration file (model.py:111-121).
 
@@ -58,6 +66,7 @@ def run_model(config_file, gpus=None):
     if gpus is None and os.environ.get('XH_GPUS'):
         gpus = int(os.environ['XH_GPUS'])
     if gpus and int(gpus) > 1 and 'RANK' not in os.environ and 'WORLD_SIZE' not in os.environ:
+        check_single_device(ConfigReader(config_file))
         env = dict(os.environ)             # the rank processes import this very package, wherever the caller found it
         pkg_parent = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
         env['PYTHONPATH'] = pkg_parent + (os.pathsep + env['PYTHONPATH'] if env.get('PYTHONPATH') else '')

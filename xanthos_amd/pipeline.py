@@ -242,3 +242,97 @@ def pipeline_from_world(ctx, world, nmonths, start_year, abcd_spinup, routing_sp
                           abcd_pars=world.abcd_pars, pm_tables=tables, lct=world.lct, elev=world.elev,
                           lc_years=world.lc_years, um=um, flow_dist=world.flow_dist, velocity=world.velocity,
                           area=world.area, abcd_spinup=abcd_spinup, routing_spinup=routing_spinup, **kw)
+
+
+class HgmPipeline:
+    """Hargreaves PET -> GWAM or ABCD runoff (-> MRTM) for the whole grid on one GPU: the device-resident path of the
+    reference's hargreaves_gwam_mrtm and hargreaves_abcd_mrtm configurations.  Like DevicePipeline it owns the six output
+    arrays in HBM (``out``) and enqueues the stages on the context's stream; nothing crosses PCIe between them."""
+
+    def __init__(self, ctx, *, ncell, nmonths, start_year, runoff_module, lat_radians, um=None, flow_dist=None,
+                 velocity=None, area=None, routing_spinup=0, chs_prev=None, route_flags=0, sm_max=None, sm0=None,
+                 gwam_spinup=0, precipitation='reference', basin_ids=None, abcd_pars=None, abcd_spinup=0, use_snow=False):
+        from .pet import hargreaves as hg_mod
+        self.ctx = ctx
+        self.ncell, self.nmonths, self.start_year = int(ncell), int(nmonths), int(start_year)
+        self.end_year = self.start_year + self.nmonths // 12 - 1
+        self.runoff_module = runoff_module
+        self.solar_dec, self.dr, self.ndays_f = hg_mod.month_factors(self.start_year, self.end_year)
+        self.ndays = self.ndays_f.astype(np.int32)
+        up = ctx.upload
+        self.d_lat = up(np.asarray(lat_radians, dtype=np.float64).reshape(-1))
+        self.gwam_spinup, self.precipitation = int(gwam_spinup), precipitation
+        self.abcd_spinup, self.use_snow = int(abcd_spinup), use_snow
+        if runoff_module == 'gwam':
+            self.d_sm_max, self.d_sm0 = up(sm_max), up(sm0)
+        elif runoff_module == 'abcd':
+            basin_ids = np.asarray(basin_ids)
+            self.basin_index = np.unique(basin_ids, return_inverse=True)[1].astype(np.int32)
+            self.n_groups = int(self.basin_index.max()) + 1 if self.ncell else 0
+            self.par_index = (basin_ids - 1).astype(np.int32)           # row of abcd_pars = basin id - 1 (abcd.py:332)
+            self.npar_rows = int(np.asarray(abcd_pars).shape[0])
+            self.d_pars = up(np.asarray(abcd_pars, dtype=np.float64))
+        self.forcing = {}
+        self.out = {k: ctx.empty((self.ncell, self.nmonths)) for k in OUTPUTS}
+        if runoff_module not in ('gwam', 'abcd'):             # PET only: no runoff, as the reference's zero arrays
+            for k in ('aet', 'q', 'sav'):
+                self.out[k].zero()
+        self.route_flags = route_flags
+        self.routing_spinup = int(routing_spinup)
+        self._plan = None
+        if um is not None:
+            self.d_flow_dist, self.d_velocity, self.d_area = up(flow_dist), up(velocity), up(area)
+            self.d_S0 = up(chs_prev) if chs_prev is not None and np.any(np.asarray(chs_prev) != 0) else None
+            self._plan = um.plan(ctx)
+            self._plan.prepare(flow_dist, velocity, 10800.0)
+
+    @property
+    def plan(self):
+        return self._plan
+
+    def set_forcing(self, host):
+        """host: 'temp', 'dtr' (+ 'precip', + 'abcd_tmin' with ABCD and snow) as [ncell, nmonths] arrays or memory maps.
+        Temperature and DTR go up as they are (the Hargreaves kernel cleans them), precipitation keeps NaN, ABCD's tmin
+        passes through nan_to_num (data_load.py:194-195)."""
+        for k, src in host.items():
+            if src is None:
+                continue
+            arr = np.asarray(src, dtype=np.float64)
+            if arr.shape != (self.ncell, self.nmonths):
+                raise ValueError('forcing {} has shape {}, expected {}'.format(k, arr.shape, (self.ncell, self.nmonths)))
+            if k not in self.forcing:
+                self.forcing[k] = self.ctx.empty((self.ncell, self.nmonths))
+            self.forcing[k].upload(arr)
+            if k == 'abcd_tmin':
+                self.ctx.nan_to_num(self.forcing[k])
+
+    def run_hargreaves(self):
+        f = self.forcing
+        self.ctx.hargreaves_pet(self.ncell, self.nmonths, f['temp'], f['dtr'], self.d_lat, self.solar_dec, self.dr,
+                                self.ndays_f, self.out['pet'])
+
+    def run_gwam(self):
+        from .runoff import gwam as gwam_mod
+        gwam_mod.gwam_device(self.ctx, self.ncell, self.nmonths, self.gwam_spinup, self.out['pet'], self.forcing['precip'],
+                             self.d_sm_max, self.d_sm0, precipitation=self.precipitation,
+                             out={k: self.out[k] for k in ('aet', 'q', 'sav')})
+
+    def run_abcd(self):
+        f = self.forcing
+        self.ctx.abcd(self.ncell, self.nmonths, self.abcd_spinup, self.n_groups, self.basin_index, self.par_index,
+                      self.npar_rows, self.d_pars, self.out['pet'], f['precip'], f['abcd_tmin'] if self.use_snow else None,
+                      self.out['aet'], self.out['q'], self.out['sav'])
+
+    def run_mrtm(self):
+        self.ctx.route_series(self._plan, self.nmonths, self.routing_spinup, self.ndays, 10800.0, self.d_flow_dist,
+                              self.d_velocity, self.d_area, self.out['q'], self.d_S0, self.out['chs'], self.out['avg'],
+                              flags=self.route_flags)
+
+    def run(self):
+        self.run_hargreaves()
+        if self.runoff_module == 'gwam':
+            self.run_gwam()
+        elif self.runoff_module == 'abcd':
+            self.run_abcd()
+        if self._plan is not None:
+            self.run_mrtm()

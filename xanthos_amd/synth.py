@@ -359,3 +359,134 @@ flow_direction = flow_dir.npy
                   rtsp=nmonths if routing_spinup is None else routing_spinup,
                   pr=os.path.join(dirs['ro'], 'pr.npy'), tn=os.path.join(dirs['ro'], 'tmin.npy'), calib=calib))
     return ini
+
+
+def hgm_forcing(world, forcing):
+    """Hargreaves inputs from a ``make_forcing`` set: temperature = tas, daily temperature range = tas - tmin."""
+    return {'temp': forcing['tas'], 'dtr': forcing['tas'] - forcing['tmin'], 'precip': forcing['precip'],
+            'abcd_tmin': forcing['abcd_tmin']}
+
+
+def hgm_soil(world, seed=7):
+    """GWAM soil inputs for ``world``: maximum soil moisture [ncell] (mm, zeros at every 37th cell: no soil) and the two
+    water-body tables, rows of (1-based cell id, 999)."""
+    n = world.ncell
+    sm = 50.0 + 450.0 * uniform(splitmix64(np.uint64(seed)), 1, np.arange(n, dtype=np.uint64))
+    sm[::37] = 0.0
+    cells = np.arange(1, n + 1)
+    lakes = np.stack([cells[5::41], np.full(len(cells[5::41]), 999)], axis=1)
+    addit = np.stack([cells[9::53], np.full(len(cells[9::53]), 999)], axis=1)
+    return sm, lakes, addit
+
+
+def write_hgm_example(root, world, forcing, start_year, end_year, project='hargreaves_gwam_mrtm_synth', runoff='gwam',
+                      runoff_spinup=12, routing_spinup=12, output_vars=('q', 'avgchflow'), hist_flag=True, sav=None,
+                      ch_storage=None, precipitation=None, soil=None, routing=True):
+    """Write a hargreaves_gwam_mrtm (``runoff='abcd'``: hargreaves_abcd_mrtm) input tree under ``root``; returns the .ini.
+
+    Keys and layout follow the reference's test configuration (xanthos/test/configs/hargreaves_gwam_mrtm.ini; ini_reader.py
+    :216-243, :311-350): input/pet/hargreaves/{tas.npy, dtr.npy}, input/runoff/gwam/{soil_moisture.csv, lakes.csv,
+    addit.csv, pr.npy}, the reference grid tables under input/reference (with the region / country maps the reference's
+    loader always reads) and the routing inputs under input/routing/mrtm.  ``forcing``: ``hgm_forcing`` keys.
+    ``hist_flag=False``: future mode from ``sav`` and ``ch_storage`` [ncell, k] (SavFile, ChStorageFile: last column read).
+    ``precipitation``: the [[gwam]] precipitation key (None: not written, the reference's behaviour)."""
+    import os
+    inp = os.path.join(root, 'input')
+    dirs = {k: os.path.join(inp, *v) for k, v in dict(ref=('reference',), pet=('pet', 'hargreaves'),
+                                                      ro=('runoff', runoff), rt=('routing', 'mrtm')).items()}
+    for d in dirs.values():
+        os.makedirs(d, exist_ok=True)
+    np.savetxt(os.path.join(dirs['ref'], 'Grid_Areas_ID.csv'), world.area * 100.0, delimiter=',', fmt='%.17g')   # ha
+    np.savetxt(os.path.join(dirs['ref'], 'coordinates.csv'), world.coords, delimiter=',', fmt='%.17g')
+    np.savetxt(os.path.join(dirs['ref'], 'basin.csv'), np.concatenate([[0], world.basin_ids]), fmt='%d')   # 1 header row
+    with open(os.path.join(dirs['ref'], 'BasinNames235.txt'), 'w') as fh:
+        fh.write('\n'.join('Basin{:03d}'.format(k) for k in range(1, world.n_basins + 1)) + '\n')
+    np.savetxt(os.path.join(dirs['ref'], 'region32_grids.csv'), np.concatenate([[0], world.basin_ids % 6 + 1]), fmt='%d')
+    with open(os.path.join(dirs['ref'], 'Rgn32Names.csv'), 'w') as fh:
+        fh.write('region,region_id\n' + '\n'.join('Region{},{}'.format(k, k) for k in range(1, 8)))
+    np.savetxt(os.path.join(dirs['ref'], 'country.csv'), np.concatenate([[0], world.basin_ids % 9 + 1]), fmt='%d')
+    with open(os.path.join(dirs['ref'], 'country-names.csv'), 'w') as fh:
+        fh.write(''.join('{},Country{}\n'.format(k, k) for k in range(10)))
+    np.save(os.path.join(dirs['pet'], 'tas.npy'), forcing['temp'])
+    np.save(os.path.join(dirs['pet'], 'dtr.npy'), forcing['dtr'])
+    np.save(os.path.join(dirs['ro'], 'pr.npy'), forcing['precip'])
+    if routing:
+        np.save(os.path.join(dirs['rt'], 'velocity.npy'), world.velocity)
+        np.save(os.path.join(dirs['rt'], 'flow_dist.npy'), world.flow_dist)
+        np.save(os.path.join(dirs['rt'], 'flow_dir.npy'), world.flow_dir)
+    future = ''
+    if runoff == 'gwam':
+        sm, lakes, addit = hgm_soil(world) if soil is None else soil
+        np.savetxt(os.path.join(dirs['ro'], 'soil_moisture.csv'), sm, fmt='%.17g', header='max_soil_moisture', comments='')
+        np.savetxt(os.path.join(dirs['ro'], 'lakes.csv'), lakes, delimiter=',', fmt='%d')
+        np.savetxt(os.path.join(dirs['ro'], 'addit.csv'), addit, delimiter=',', fmt='%d')
+        runoff_sec = ('[[gwam]]\nrunoff_dir = gwam\nrunoff_spinup = {}\nPrecipitationFile = pr.npy\n'
+                      'max_soil_moisture = soil_moisture.csv\nlakes_msm = lakes.csv\naddit_water_msm = addit.csv\n'
+                      ).format(runoff_spinup)
+        if precipitation is not None:
+            runoff_sec += 'precipitation = {}\n'.format(precipitation)
+        if not hist_flag:
+            np.save(os.path.join(dirs['ro'], 'sav.npy'), np.asarray(sav, dtype=float))
+            np.save(os.path.join(dirs['rt'], 'ch_storage.npy'), np.asarray(ch_storage, dtype=float))
+            future = ('ChStorageFile = {}\nChStorageVarName = chs\nSavFile = {}\nSavVarName = sav\n').format(
+                os.path.join(dirs['rt'], 'ch_storage.npy'), os.path.join(dirs['ro'], 'sav.npy'))
+    else:
+        np.save(os.path.join(dirs['ro'], 'pars.npy'), world.abcd_pars)
+        np.save(os.path.join(dirs['ro'], 'tmin.npy'), forcing['abcd_tmin'])
+        runoff_sec = ('[[abcd]]\nrunoff_dir = abcd\ncalib_file = pars.npy\nrunoff_spinup = {}\njobs = -1\n'
+                      'PrecipitationFile = {}\nTempMinFile = {}\n').format(
+            runoff_spinup, os.path.join(dirs['ro'], 'pr.npy'), os.path.join(dirs['ro'], 'tmin.npy'))
+    routing_sec = ''
+    if routing:
+        routing_sec = ('[Routing]\nrouting_module = mrtm\n[[mrtm]]\nrouting_dir = mrtm\nrouting_spinup = {}\n'
+                       'channel_velocity = velocity.npy\nflow_distance = flow_dist.npy\nflow_direction = flow_dir.npy\n'
+                       ).format(routing_spinup)
+    ini = os.path.join(root, project + '.ini')
+    with open(ini, 'w') as fh:
+        fh.write('''[Project]
+# synthetic hargreaves_{runoff}_mrtm example written by xanthos_amd.synth.write_hgm_example
+ProjectName = {project}
+RootDir = {root}
+InputFolder = input
+OutputFolder = output
+RefDir = reference
+pet_dir = pet
+RunoffDir = runoff
+RoutingDir = routing
+HistFlag = {hist}
+n_basins = {nb}
+ncell = {ncell}
+ngridrow = {nrow}
+ngridcol = {ncol}
+StartYear = {y0}
+EndYear = {y1}
+output_vars = {ov}
+OutputFormat = 1
+OutputUnit = 0
+OutputInYear = 0
+AggregateRunoffBasin = 0
+AggregateRunoffCountry = 0
+AggregateRunoffGCAMRegion = 0
+PerformDiagnostics = 0
+CreateTimeSeriesPlot = 0
+CalculateDroughtStats = 0
+CalculateAccessibleWater = 0
+CalculateHydropowerPotential = 0
+CalculateHydropowerActual = 0
+Calibrate = 0
+
+[PET]
+pet_module = hargreaves
+[[hargreaves]]
+pet_dir = hargreaves
+TemperatureFile = tas.npy
+DailyTemperatureRangeFile = dtr.npy
+
+[Runoff]
+runoff_module = {runoff}
+{runoff_sec}{future}
+{routing_sec}'''.format(runoff=runoff, project=project, root=root, hist='True' if hist_flag else 'False',
+                        nb=world.n_basins, ncell=world.ncell, nrow=world.nrow, ncol=world.ncol, y0=start_year,
+                        y1=end_year, ov=', '.join(output_vars), runoff_sec=runoff_sec, future=future,
+                        routing_sec=routing_sec))
+    return ini
