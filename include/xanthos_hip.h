@@ -84,7 +84,8 @@ int xh_transpose(xh_ctx *ctx, const double *d_src, int64_t rows, int64_t cols, d
 
 /* HIP-event timing of the kernels each entry point launches, accumulated per kernel name on the context's stream.
  * Names: "pm_pet", "abcd_spinup", "abcd_basin_mean", "abcd_sim", "mrtm_route", "calib_abcd", "calib_kge", "calib_de",
- * "agg_time", "agg_spatial", "drought_thresh", "drought_stats", "hargreaves_pet", "gwam_spinup", "gwam_sim".  xh_timing_get waits for the stream, then returns total milliseconds and launch count. */
+ * "agg_time", "agg_spatial", "drought_thresh", "drought_stats", "hargreaves_pet", "gwam_spinup", "gwam_sim",
+ * "hs_pet", "trn_daylight", "trn_pet".  xh_timing_get waits for the stream, then returns total milliseconds and launch count. */
 int xh_timing_reset(xh_ctx *ctx);
 /* a caller-named span on the context's stream, read back with xh_timing_get like the library's own timers (one open
  * at a time): e.g. what a step still spends in the write-out gather after the routing kernel has ended                */
@@ -142,6 +143,36 @@ int xh_hargreaves_pet(xh_ctx *ctx, int64_t ncell, int32_t nmonths,
                       const double *d_lat_rad,                    /* [ncell]                                          */
                       const double *h_solar_dec, const double *h_dr, const double *h_ndays,   /* host, [nmonths]  */
                       double *d_pet);                             /* out [ncell, nmonths]                             */
+
+/* ------------------------------------------------------------------ Hargreaves-Samani PET
+ * Replaces pet/hargreaves_samani.py:execute (:95-119), one scalar pet() call per cell and month (:34-64), over every
+ * month at once.  Inputs as the loader keeps them (data_load.py:86-90: NaN stays): t < 0 gives 0, a NaN t, tmax or tmin
+ * gives NaN.  The day of year is j[m % 12] (15, 45, ..., 345); arccos of -tan(dec) tan(phi) inside [-1, 1], 0 outside;
+ * ra = 118 / pi * acs + cos(phi) cos(dec) sin(acs) exactly as written (:60).  d_lat_deg: coords[:, 2] in degrees;
+ * h_ndays: days of each month of the run (:18-28, leap years included).  Asynchronous after one stream synchronisation
+ * for the small month tables.                                                                                        */
+int xh_hs_pet(xh_ctx *ctx, int64_t ncell, int32_t nmonths,
+              const double *d_tas, const double *d_tmax, const double *d_tmin,   /* [ncell, nmonths]                */
+              const double *d_lat_deg,                                           /* [ncell]                         */
+              const double *h_ndays,                                             /* host, [nmonths]                 */
+              double *d_pet);                                                    /* out [ncell, nmonths]            */
+
+/* ------------------------------------------------------------------ Thornthwaite PET
+ * Replaces pet/thornthwaite.py:execute (:51-130) and calc_daylight_hours (:18-48).  NaN and negative temperatures count
+ * as 0 (:85; the loader's nan_to_num, data_load.py:137-138, is xh_nan_to_num on the upload).  I = sum over each year of
+ * (T / 5)^1.514, a = 6.75e-7 I^3 - 7.71e-5 I^2 + 0.0179 I + 0.492 (the code's constants, not the docstring's), PET =
+ * 16 (10 T / I)^a (0 where I == 0) x L / 12 x N / 30.  daylight_mode XH_DAYLIGHT_REFERENCE: the daylight L of a common
+ * year's month m is that of month-of-year m // nyears, as np.repeat spreads it (:113); leap years get the leap table in
+ * month order (:116-122).  XH_DAYLIGHT_MONTHLY: every month its own month's daylight.  nmonths: whole years from
+ * start_year; 0 with d_tas / d_pet NULL computes only the daylight table.  d_daylight (optional out [ncell, 24]): mean
+ * daylight hours of the 12 months of a common year, then of a leap year.                                             */
+#define XH_DAYLIGHT_REFERENCE 0
+#define XH_DAYLIGHT_MONTHLY 1
+int xh_thornthwaite_pet(xh_ctx *ctx, int64_t ncell, int32_t nmonths, int32_t start_year, int32_t daylight_mode,
+                        const double *d_tas,                      /* [ncell, nmonths]                                  */
+                        const double *d_lat_rad,                  /* [ncell]: radians(coords[:, 2])                    */
+                        double *d_pet,                            /* out [ncell, nmonths]                              */
+                        double *d_daylight);                      /* optional out [ncell, 24]                          */
 
 /* ------------------------------------------------------------------ GWAM runoff
  * Replaces runoff/gwam.py:runoffgen (:18-88) driven month by month as components.py:298-384 / configurations.py:54-121

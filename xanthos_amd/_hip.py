@@ -18,6 +18,7 @@ XH_ROUTE_DEFAULT, XH_ROUTE_FORCE_FALLBACK, XH_ROUTE_ATOMIC, XH_ROUTE_NO_DATAFLOW
 XH_ROUTE_TEST_FAULT, XH_ROUTE_VALIDATE = 16, 32
 XH_ROUTE_REASSOC, XH_ROUTE_EXACT = 128, 256      # reassociated (tolerance) form of the routing kernel / the bit-exact kernels
 XH_ROUTE_NO_PLAIN = 0x4000                       # (xh_common.h, what a guard trip re-routes with) pairs of sums in every unit: not the prepared plan
+XH_DAYLIGHT_REFERENCE, XH_DAYLIGHT_MONTHLY = 0, 1  # Thornthwaite's daylight order: the reference's repeat / every month its own
 
 
 class HipUnavailable(RuntimeError):
@@ -83,6 +84,8 @@ SIGNATURES = {
     'xh_abcd': (c_int, [_P, c_int64, c_int32, c_int32, c_int32, _P, _P, c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     'xh_hargreaves_pet': (c_int, [_P, c_int64, c_int32, _P, _P, _P, _P, _P, _P, _P]),
     'xh_gwam': (c_int, [_P, c_int64, c_int32, c_int32, c_int32, c_int32, c_double, _P, _P, _P, _P, _P, _P, _P, _P]),
+    'xh_hs_pet': (c_int, [_P, c_int64, c_int32, _P, _P, _P, _P, _P, _P]),
+    'xh_thornthwaite_pet': (c_int, [_P, c_int64, c_int32, c_int32, c_int32, _P, _P, _P, _P]),
     'xh_route_plan_create': (c_int, [_P, c_int64, _P, _P, _P, POINTER(c_void_p)]),
     'xh_route_plan_destroy': (None, [_P]),
     'xh_route_plan_info': (c_int, [_P, POINTER(c_int64)]),
@@ -124,7 +127,7 @@ SIGNATURES = {
 _lib = None
 
 
-ABI_VERSION = 6        # xh_abi_version() of the library these signatures describe
+ABI_VERSION = 7        # xh_abi_version() of the library these signatures describe
 
 
 def lib():
@@ -438,6 +441,20 @@ class Context:
         self._check(lib().xh_gwam(self.handle, ncell, nmonths, spinup, precip_col_spinup, precip_col_sim, float(indexing),
                                   _dptr(pet), _dptr(precip), _dptr(sm_max), _dptr(sm0), _dptr(aet), _dptr(q), _dptr(sav),
                                   _dptr(sm_end)))
+
+    # ---- Hargreaves-Samani / Thornthwaite PET
+    def hs_pet(self, ncell, nmonths, tas, tmax, tmin, lat_deg, ndays, pet):
+        """tas / tmax / tmin / lat_deg / pet device arrays; ndays a host array of nmonths values."""
+        nd = np.ascontiguousarray(ndays, dtype=np.float64)
+        if nd.size != nmonths:
+            raise ValueError('ndays must have nmonths entries')
+        self._check(lib().xh_hs_pet(self.handle, ncell, nmonths, _dptr(tas), _dptr(tmax), _dptr(tmin), _dptr(lat_deg),
+                                    _host_ptr(nd), _dptr(pet)))
+
+    def thornthwaite_pet(self, ncell, nmonths, start_year, daylight_mode, tas, lat_rad, pet, daylight=None):
+        """tas / lat_rad / pet (/ daylight [ncell, 24]) device arrays; daylight_mode XH_DAYLIGHT_REFERENCE or _MONTHLY."""
+        self._check(lib().xh_thornthwaite_pet(self.handle, ncell, nmonths, start_year, daylight_mode, _dptr(tas),
+                                              _dptr(lat_rad), _dptr(pet), _dptr(daylight)))
 
     # ---- MRTM
     def route_plan(self, indptr, indices, sign):

@@ -20,6 +20,8 @@ from .ini_reader import ValidationException, check_modules
 from .pipeline import DevicePipeline
 from .utils import set_month_arrays
 
+HGM_PET = ('hargreaves', 'hs', 'thornthwaite')      # PET modules of the HgmPipeline (pipeline.py)
+
 pet_mod = runoff_mod = routing_mod = None
 
 _TOPOLOGIES = {}      # (digest of coords + flow directions, grid shape) -> (dsid, upid, UM with its cached device plan)
@@ -95,6 +97,10 @@ class Components:
             from .pet import penman_monteith as pet_mod
         elif self.s.pet_module == 'hargreaves':
             from .pet import hargreaves as pet_mod
+        elif self.s.pet_module == 'hs':
+            from .pet import hargreaves_samani as pet_mod
+        elif self.s.pet_module == 'thornthwaite':
+            from .pet import thornthwaite as pet_mod
         elif self.s.pet_module != 'none':
             raise ValidationException("pet_module '{}' is not part of the MI355X hot path".format(self.s.pet_module))
         if self.s.runoff_module == 'abcd':
@@ -116,6 +122,11 @@ class Components:
         if self.s.pet_module == 'hargreaves':
             return pet_mod.run_hargreaves(self.data.temp, self.data.dtr, self.data.lat_radians, self.s.StartYear,
                                           self.s.EndYear, device=self.s.device)
+        if self.s.pet_module == 'hs':
+            return pet_mod.execute(self.s, self.data)
+        if self.s.pet_module == 'thornthwaite':
+            return pet_mod.execute(self.data.tair, self.data.lat_radians, self.s.StartYear, self.s.EndYear,
+                                   daylight=self.s.trn_daylight, device=self.s.device)
         if self.s.pet_module == 'none':
             return self.data.pet_out
 
@@ -181,7 +192,7 @@ class Components:
         logging.info('---{} in progress...'.format(notify))
         t0 = time.time()
         s, d = self.s, self.data
-        if s.pet_module == 'hargreaves' and run_pet:
+        if s.pet_module in HGM_PET and run_pet:
             return self._simulation_hgm(run_runoff, run_routing, t0, notify)
         full = (s.pet_module == 'pm' and s.runoff_module == 'abcd' and run_pet and run_runoff)
         if not full:
@@ -242,15 +253,16 @@ class Components:
             raise ValidationException('[[gwam]] runoff_spinup = {} must lie in [1, nmonths = {}].'.format(n, self.s.nmonths))
 
     def _simulation_hgm(self, run_runoff, run_routing, t0, notify):
-        """Hargreaves PET -> GWAM / ABCD (-> MRTM), device resident (configurations.py:104-121, components.py:298-384).
+        """Hargreaves, Hargreaves-Samani or Thornthwaite PET -> GWAM (Hargreaves only) / ABCD / no runoff (-> MRTM), device
+        resident (configurations.py:104-121, components.py:298-384).
         GWAM's spin-up pass and its simulation are one xh_gwam call; the spin-up pass's routing is skipped -- it changes
         nothing (streamrouting does not mutate its inputs and calculate_routing starts again from data.chs_prev)."""
         from .pipeline import HgmPipeline
         from .runoff import abcd as abcd_mod
         s, d = self.s, self.data
         if self.group is not None and self.group.size > 1:
-            raise ValidationException('{}: Hargreaves PET and GWAM runoff run on one GPU; sharding them over several GPUs '
-                                      'is not implemented.'.format(s.mod_cfg))
+            raise ValidationException('{}: {} PET and {} runoff run on one GPU; sharding them over several GPUs is not '
+                                      'implemented.'.format(s.mod_cfg, s.pet_module, s.runoff_module))
         runoff = s.runoff_module if run_runoff else 'none'
         if runoff == 'gwam':
             self._check_gwam_spinup()
@@ -269,14 +281,23 @@ class Components:
             kw = dict(basin_ids=d.basin_ids, abcd_pars=s.calib_file if isinstance(s.calib_file, np.ndarray) else
                       np.load(s.calib_file), abcd_spinup=s.runoff_spinup, use_snow=d.tmin is not None)
         pipe = HgmPipeline(ctx, ncell=s.ncell, nmonths=s.nmonths, start_year=s.StartYear, runoff_module=runoff,
-                           lat_radians=d.lat_radians, um=um, flow_dist=d.flow_dist if um is not None else None,
+                           pet_module=s.pet_module, lat_radians=d.lat_radians, lat_degrees=d.latitude,
+                           daylight=getattr(s, 'trn_daylight', 'reference'), um=um,
+                           flow_dist=d.flow_dist if um is not None else None,
                            velocity=d.str_velocity if um is not None else None, area=d.area,
                            routing_spinup=getattr(s, 'routing_spinup', 0), chs_prev=getattr(d, 'chs_prev', None),
                            route_flags=self.route_flags(), **kw)
         self.timings['plan'] = time.time() - t
         t = time.time()
-        pipe.set_forcing({'temp': d.temp, 'dtr': d.dtr, 'precip': getattr(d, 'precip', None) if runoff != 'none' else None,
-                          'abcd_tmin': getattr(d, 'tmin', None) if runoff == 'abcd' else None})
+        if s.pet_module == 'hs':
+            forcing = {'tas': d.hs_tas, 'tmax': d.hs_tmax, 'tmin': d.hs_tmin}
+        elif s.pet_module == 'thornthwaite':
+            forcing = {'tas': d.tair}
+        else:
+            forcing = {'temp': d.temp, 'dtr': d.dtr}
+        forcing.update(precip=getattr(d, 'precip', None) if runoff != 'none' else None,
+                       abcd_tmin=getattr(d, 'tmin', None) if runoff == 'abcd' else None)
+        pipe.set_forcing(forcing)
         ctx.sync()
         self.timings['upload'] = time.time() - t
         t = time.time()
@@ -286,7 +307,8 @@ class Components:
         self.timings['kernels'] = time.time() - t
         logging.info('\tPET + runoff + routing kernels: {:.3f} seconds'.format(time.time() - t))
         cm = pipe.ncell * pipe.nmonths
-        for name, nbytes in (('hargreaves_pet', cm * 24), ('gwam_spinup', pipe.ncell * pipe.gwam_spinup * 16),
+        for name, nbytes in (('hargreaves_pet', cm * 24), ('hs_pet', cm * 32), ('trn_daylight', pipe.ncell * 24 * 8),
+                             ('trn_pet', cm * 16), ('gwam_spinup', pipe.ncell * pipe.gwam_spinup * 16),
                              ('gwam_sim', cm * (40 if s.gwam_precipitation == 'monthly' else 32) if runoff == 'gwam' else 0),
                              ('abcd_sim', cm * 48), ('mrtm_route', cm * 24 + pipe.ncell * pipe.routing_spinup * 8)):
             ms, n = ctx.timing(name)

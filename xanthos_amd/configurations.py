@@ -5,7 +5,7 @@ from .components import Components
 
 
 class ConfigRunner:
-    PET_COMPONENTS = ['pm', 'hargreaves']   # the reference also lists hs / thornthwaite (:61)
+    PET_COMPONENTS = ['pm', 'hargreaves', 'hs', 'thornthwaite']   # (:61)
     RUNOFF_COMPONENTS = ['abcd', 'gwam']    # (:62)
     ROUTING_COMPONENTS = ['mrtm']           # (:63)
 

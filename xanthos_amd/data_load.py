@@ -11,6 +11,8 @@ changes its inputs:
 * Hargreaves: temperature and daily temperature range as loaded (the kernel clamps and cleans them), latitude in
   radians (:71-84); GWAM: the maximum-soil-moisture composite with the water bodies and the initial soil moisture
   (:149-182, :226-260)
+* Hargreaves-Samani: tas, tmin and tmax as loaded, NaN kept (:86-90); Thornthwaite: tas through nan_to_num (:137-138),
+  on the device after upload unless ``device_transforms = False``
 * routing: flow distance < 1000 -> 1000 (:204-205), velocity < 0 -> 0 (:207-208), 2-D DRT maps flattened with the
   reference's ``vectorize`` (:415-425), zero initial channel storage in historic mode (:427-438)
 
@@ -132,6 +134,12 @@ class DataLoader:
             self.temp = self.load_to_array(s.TemperatureFile, 'TemperatureFile', key=getattr(s, 'TempVarName', None))
             self.dtr = self.load_to_array(s.DailyTemperatureRangeFile, 'DailyTemperatureRangeFile',
                                           key=getattr(s, 'DTRVarName', None))
+        elif s.pet_module == 'hs':
+            self.hs_tas = self.load_to_array(s.hs_tas, 'hs_tas')
+            self.hs_tmin = self.load_to_array(s.hs_tmin, 'hs_tmin')
+            self.hs_tmax = self.load_to_array(s.hs_tmax, 'hs_tmax')
+        elif s.pet_module == 'thornthwaite':
+            self.tair = self.load_to_array(s.trn_tas, 'trn_tas', nan_to_num=True)
         elif s.pet_module == 'none':
             self.pet_out = self.load_to_array(s.pet_file, 'pet_file')
         self.lat_radians = np.radians(self.latitude)          # data_load.py:71-72

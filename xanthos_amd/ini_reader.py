@@ -3,7 +3,8 @@
 The reference parses the file with ``configobj`` (not installed here) and flattens it into an attribute bag
 (ini_reader.py:24-607).  This module has its own small parser for the same syntax (``[Section]``, nested
 ``[[subsection]]``, ``key = value``, ``#`` comments, comma lists, optional quotes) and builds the same attributes for
-the sections the hot path reads: ``[Project]``, ``[PET][[penman-monteith]]`` / ``[[hargreaves]]``,
+the sections the hot path reads: ``[Project]``, ``[PET][[penman-monteith]]`` / ``[[hargreaves]]`` /
+``[[hargreaves-samani]]`` / ``[[thornthwaite]]``,
 ``[Runoff][[abcd]]`` / ``[[gwam]]``, ``[Routing][[mrtm]]`` and ``[Calibrate]``.  Selector strings are lower-cased and validated exactly like the
 reference (:214, :309, :397); selectors that belong to other reference modules are rejected with a clear message
 because only the MI355X hot path is implemented here.  ``update()`` keeps the in-memory override hook (:598-607).
@@ -94,7 +95,7 @@ def _key(m, key, name):
 class ConfigReader:
     """Attribute bag of settings for one run (ini_reader.py:24)."""
 
-    PET_OTHER = ('hs', 'thornthwaite')
+    PET_OTHER = ()
     RUNOFF_OTHER = ()
 
     def __init__(self, ini):
@@ -199,6 +200,22 @@ class ConfigReader:
             self.TempVarName = m.get('TempVarName')
             self.DailyTemperatureRangeFile = os.path.join(self.pet_dir, _key(m, 'DailyTemperatureRangeFile', 'hargreaves'))
             self.DTRVarName = m.get('DTRVarName')
+        elif self.pet_module == 'hs':
+            m = _subsection(cfg, 'hargreaves-samani', 'PET')
+            self.pet_dir = os.path.join(self.PET, _key(m, 'pet_dir', 'hargreaves-samani'))
+            # climate data (ini_reader.py:245-252): file names relative to pet_dir
+            for key in ('hs_tas', 'hs_tmin', 'hs_tmax'):
+                setattr(self, key, os.path.join(self.pet_dir, _key(m, key, 'hargreaves-samani')))
+        elif self.pet_module == 'thornthwaite':
+            m = _subsection(cfg, 'thornthwaite', 'PET')
+            self.pet_dir = os.path.join(self.PET, _key(m, 'pet_dir', 'thornthwaite'))
+            self.trn_tas = os.path.join(self.pet_dir, _key(m, 'trn_tas', 'thornthwaite'))      # (ini_reader.py:281-287)
+            # (not a key of the reference) which month's daylight each month gets.  `reference` (default): the order the
+            # reference's np.repeat gives common years (thornthwaite.py:113); `monthly`: every month its own month's.
+            self.trn_daylight = str(m.get('daylight', 'reference')).strip().lower()
+            if self.trn_daylight not in ('reference', 'monthly'):
+                raise ValidationException("[[thornthwaite]] daylight must be 'reference' or 'monthly', not '{}'".format(
+                    self.trn_daylight))
         elif self.pet_module == 'none':
             try:
                 self.pet_file = cfg['pet_file']

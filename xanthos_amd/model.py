@@ -49,11 +49,12 @@ class Xanthos:
 
 
 def check_single_device(config):
-    """Hargreaves and GWAM run on one GPU: the basin sharding covers the pm / abcd / mrtm stages only."""
+    """Hargreaves, Hargreaves-Samani and Thornthwaite PET and GWAM run on one GPU: the basin sharding covers the pm / abcd /
+    mrtm stages only."""
     from .ini_reader import ValidationException
-    if config.pet_module == 'hargreaves' or config.runoff_module == 'gwam':
-        raise ValidationException('{}: Hargreaves PET and GWAM runoff run on one GPU; sharding them over several GPUs is '
-                                  'not implemented.'.format(config.mod_cfg))
+    if config.pet_module in ('hargreaves', 'hs', 'thornthwaite') or config.runoff_module == 'gwam':
+        raise ValidationException('{}: {} PET and {} runoff run on one GPU; sharding them over several GPUs is not '
+                                  'implemented.'.format(config.mod_cfg, config.pet_module, config.runoff_module))
 
 
 def run_model(config_file, gpus=None):

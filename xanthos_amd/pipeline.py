@@ -245,22 +245,37 @@ def pipeline_from_world(ctx, world, nmonths, start_year, abcd_spinup, routing_sp
 
 
 class HgmPipeline:
-    """Hargreaves PET -> GWAM or ABCD runoff (-> MRTM) for the whole grid on one GPU: the device-resident path of the
-    reference's hargreaves_gwam_mrtm and hargreaves_abcd_mrtm configurations.  Like DevicePipeline it owns the six output
-    arrays in HBM (``out``) and enqueues the stages on the context's stream; nothing crosses PCIe between them."""
+    """Hargreaves, Hargreaves-Samani (``hs``) or Thornthwaite PET -> GWAM or ABCD runoff (-> MRTM) for the whole grid on one
+    GPU: the device-resident path of the reference's hargreaves_gwam_mrtm, hargreaves_abcd_mrtm, hs_abcd_mrtm and
+    thornthwaite_abcd_mrtm configurations.  Like DevicePipeline it owns the six output arrays in HBM (``out``) and
+    enqueues the stages on the context's stream; nothing crosses PCIe between them."""
 
-    def __init__(self, ctx, *, ncell, nmonths, start_year, runoff_module, lat_radians, um=None, flow_dist=None,
-                 velocity=None, area=None, routing_spinup=0, chs_prev=None, route_flags=0, sm_max=None, sm0=None,
-                 gwam_spinup=0, precipitation='reference', basin_ids=None, abcd_pars=None, abcd_spinup=0, use_snow=False):
-        from .pet import hargreaves as hg_mod
+    PET_MODULES = ('hargreaves', 'hs', 'thornthwaite')
+
+    def __init__(self, ctx, *, ncell, nmonths, start_year, runoff_module, lat_radians, pet_module='hargreaves',
+                 lat_degrees=None, daylight='reference', um=None, flow_dist=None, velocity=None, area=None,
+                 routing_spinup=0, chs_prev=None, route_flags=0, sm_max=None, sm0=None, gwam_spinup=0,
+                 precipitation='reference', basin_ids=None, abcd_pars=None, abcd_spinup=0, use_snow=False):
+        from .pet import hargreaves as hg_mod, hargreaves_samani as hs_mod, thornthwaite as trn_mod
+        if pet_module not in self.PET_MODULES:
+            raise ValueError("pet_module must be one of {}, not '{}'".format(self.PET_MODULES, pet_module))
         self.ctx = ctx
         self.ncell, self.nmonths, self.start_year = int(ncell), int(nmonths), int(start_year)
         self.end_year = self.start_year + self.nmonths // 12 - 1
-        self.runoff_module = runoff_module
+        self.runoff_module, self.pet_module = runoff_module, pet_module
+        # routing's days per month (general.py set_month_arrays) whatever the PET module's own calendar
         self.solar_dec, self.dr, self.ndays_f = hg_mod.month_factors(self.start_year, self.end_year)
         self.ndays = self.ndays_f.astype(np.int32)
         up = ctx.upload
-        self.d_lat = up(np.asarray(lat_radians, dtype=np.float64).reshape(-1))
+        if pet_module == 'hs':                                   # latitude in degrees (hargreaves_samani.py:105)
+            if lat_degrees is None:
+                raise ValueError('Hargreaves-Samani PET needs lat_degrees')
+            self.hs_ndays = hs_mod.days_per_month(self.start_year, self.end_year)
+            self.d_lat = up(np.asarray(lat_degrees, dtype=np.float64).reshape(-1))
+        else:
+            self.daylight = daylight
+            trn_mod.daylight_mode(daylight)                      # (a bad name fails here, not at run time)
+            self.d_lat = up(np.asarray(lat_radians, dtype=np.float64).reshape(-1))
         self.gwam_spinup, self.precipitation = int(gwam_spinup), precipitation
         self.abcd_spinup, self.use_snow = int(abcd_spinup), use_snow
         if runoff_module == 'gwam':
@@ -291,9 +306,11 @@ class HgmPipeline:
         return self._plan
 
     def set_forcing(self, host):
-        """host: 'temp', 'dtr' (+ 'precip', + 'abcd_tmin' with ABCD and snow) as [ncell, nmonths] arrays or memory maps.
-        Temperature and DTR go up as they are (the Hargreaves kernel cleans them), precipitation keeps NaN, ABCD's tmin
-        passes through nan_to_num (data_load.py:194-195)."""
+        """host: the PET module's forcing -- 'temp', 'dtr' (Hargreaves), 'tas', 'tmax', 'tmin' (Hargreaves-Samani) or 'tas'
+        (Thornthwaite) -- (+ 'precip', + 'abcd_tmin' with ABCD and snow) as [ncell, nmonths] arrays or memory maps.
+        Hargreaves' and Hargreaves-Samani's forcing goes up as it is (the kernels clean it or keep NaN as the reference
+        does), precipitation keeps NaN, Thornthwaite's tas and ABCD's tmin pass through nan_to_num (data_load.py:137-138,
+        :194-195)."""
         for k, src in host.items():
             if src is None:
                 continue
@@ -303,13 +320,25 @@ class HgmPipeline:
             if k not in self.forcing:
                 self.forcing[k] = self.ctx.empty((self.ncell, self.nmonths))
             self.forcing[k].upload(arr)
-            if k == 'abcd_tmin':
+            if k == 'abcd_tmin' or (k == 'tas' and self.pet_module == 'thornthwaite'):
                 self.ctx.nan_to_num(self.forcing[k])
 
     def run_hargreaves(self):
         f = self.forcing
         self.ctx.hargreaves_pet(self.ncell, self.nmonths, f['temp'], f['dtr'], self.d_lat, self.solar_dec, self.dr,
                                 self.ndays_f, self.out['pet'])
+
+    def run_pet(self):
+        f = self.forcing
+        if self.pet_module == 'hargreaves':
+            self.run_hargreaves()
+        elif self.pet_module == 'hs':
+            self.ctx.hs_pet(self.ncell, self.nmonths, f['tas'], f['tmax'], f['tmin'], self.d_lat, self.hs_ndays,
+                            self.out['pet'])
+        else:
+            from .pet import thornthwaite as trn_mod
+            trn_mod.thornthwaite_device(self.ctx, self.ncell, self.nmonths, self.start_year, f['tas'], self.d_lat,
+                                        daylight=self.daylight, d_pet=self.out['pet'])
 
     def run_gwam(self):
         from .runoff import gwam as gwam_mod
@@ -329,7 +358,7 @@ class HgmPipeline:
                               flags=self.route_flags)
 
     def run(self):
-        self.run_hargreaves()
+        self.run_pet()
         if self.runoff_module == 'gwam':
             self.run_gwam()
         elif self.runoff_module == 'abcd':

@@ -381,7 +381,8 @@ def hgm_soil(world, seed=7):
 
 def write_hgm_example(root, world, forcing, start_year, end_year, project='hargreaves_gwam_mrtm_synth', runoff='gwam',
                       runoff_spinup=12, routing_spinup=12, output_vars=('q', 'avgchflow'), hist_flag=True, sav=None,
-                      ch_storage=None, precipitation=None, soil=None, routing=True):
+                      ch_storage=None, precipitation=None, soil=None, routing=True, pet='hargreaves', daylight=None,
+                      obs=None):
     """Write a hargreaves_gwam_mrtm (``runoff='abcd'``: hargreaves_abcd_mrtm) input tree under ``root``; returns the .ini.
 
     Keys and layout follow the reference's test configuration (xanthos/test/configs/hargreaves_gwam_mrtm.ini; ini_reader.py
@@ -389,10 +390,13 @@ def write_hgm_example(root, world, forcing, start_year, end_year, project='hargr
     addit.csv, pr.npy}, the reference grid tables under input/reference (with the region / country maps the reference's
     loader always reads) and the routing inputs under input/routing/mrtm.  ``forcing``: ``hgm_forcing`` keys.
     ``hist_flag=False``: future mode from ``sav`` and ``ch_storage`` [ncell, k] (SavFile, ChStorageFile: last column read).
-    ``precipitation``: the [[gwam]] precipitation key (None: not written, the reference's behaviour)."""
+    ``precipitation``: the [[gwam]] precipitation key (None: not written, the reference's behaviour).
+    ``pet``: 'hs' or 'thornthwaite' write that PET module instead (``write_pet_ext_example``), ``daylight`` its
+    [[thornthwaite]] daylight key.  ``obs``: observed runoff rows (basin, -, -, value) -> Calibrate = 1 on basins 1-2."""
     import os
     inp = os.path.join(root, 'input')
-    dirs = {k: os.path.join(inp, *v) for k, v in dict(ref=('reference',), pet=('pet', 'hargreaves'),
+    pet_dirname = {'hargreaves': 'hargreaves', 'hs': 'hargreaves_samani', 'thornthwaite': 'thornthwaite'}[pet]
+    dirs = {k: os.path.join(inp, *v) for k, v in dict(ref=('reference',), pet=('pet', pet_dirname),
                                                       ro=('runoff', runoff), rt=('routing', 'mrtm')).items()}
     for d in dirs.values():
         os.makedirs(d, exist_ok=True)
@@ -407,8 +411,23 @@ def write_hgm_example(root, world, forcing, start_year, end_year, project='hargr
     np.savetxt(os.path.join(dirs['ref'], 'country.csv'), np.concatenate([[0], world.basin_ids % 9 + 1]), fmt='%d')
     with open(os.path.join(dirs['ref'], 'country-names.csv'), 'w') as fh:
         fh.write(''.join('{},Country{}\n'.format(k, k) for k in range(10)))
-    np.save(os.path.join(dirs['pet'], 'tas.npy'), forcing['temp'])
-    np.save(os.path.join(dirs['pet'], 'dtr.npy'), forcing['dtr'])
+    pet_files = {'hargreaves': (('tas', 'temp'), ('dtr', 'dtr')), 'hs': (('tas', 'tas'), ('tmin', 'tmin'), ('tmax', 'tmax')),
+                 'thornthwaite': (('tas', 'tas'),)}[pet]
+    for fn, key in pet_files:
+        np.save(os.path.join(dirs['pet'], fn + '.npy'), forcing[key])
+    pet_sec = {'hargreaves': '[[hargreaves]]\npet_dir = hargreaves\nTemperatureFile = tas.npy\n'
+                             'DailyTemperatureRangeFile = dtr.npy\n',
+               'hs': '[[hargreaves-samani]]\npet_dir = hargreaves_samani\nhs_tas = tas.npy\nhs_tmin = tmin.npy\n'
+                     'hs_tmax = tmax.npy\n',
+               'thornthwaite': '[[thornthwaite]]\npet_dir = thornthwaite\ntrn_tas = tas.npy\n'}[pet]
+    if daylight is not None:
+        pet_sec += 'daylight = {}\n'.format(daylight)
+    calib = ''
+    if obs is not None:
+        obs_file = os.path.join(inp, 'obs.csv')
+        np.savetxt(obs_file, obs, delimiter=',', fmt='%.17g')
+        calib = ('\n[Calibrate]\nset_calibrate = 0\nobserved = {}\nobs_unit = km3_per_mth\ncalib_out_dir = {}\n'
+                 'calibration_basins = 1-2\n').format(obs_file, os.path.join(root, 'calib_out'))
     np.save(os.path.join(dirs['ro'], 'pr.npy'), forcing['precip'])
     if routing:
         np.save(os.path.join(dirs['rt'], 'velocity.npy'), world.velocity)
@@ -444,7 +463,7 @@ def write_hgm_example(root, world, forcing, start_year, end_year, project='hargr
     ini = os.path.join(root, project + '.ini')
     with open(ini, 'w') as fh:
         fh.write('''[Project]
-# synthetic hargreaves_{runoff}_mrtm example written by xanthos_amd.synth.write_hgm_example
+# synthetic {pet}_{runoff}_mrtm example written by xanthos_amd.synth.write_hgm_example
 ProjectName = {project}
 RootDir = {root}
 InputFolder = input
@@ -473,20 +492,32 @@ CalculateDroughtStats = 0
 CalculateAccessibleWater = 0
 CalculateHydropowerPotential = 0
 CalculateHydropowerActual = 0
-Calibrate = 0
+Calibrate = {cal}
 
 [PET]
-pet_module = hargreaves
-[[hargreaves]]
-pet_dir = hargreaves
-TemperatureFile = tas.npy
-DailyTemperatureRangeFile = dtr.npy
-
+pet_module = {pet}
+{pet_sec}
 [Runoff]
 runoff_module = {runoff}
 {runoff_sec}{future}
-{routing_sec}'''.format(runoff=runoff, project=project, root=root, hist='True' if hist_flag else 'False',
+{routing_sec}{calib}'''.format(pet=pet, pet_sec=pet_sec, cal=int(obs is not None), calib=calib, runoff=runoff, project=project, root=root, hist='True' if hist_flag else 'False',
                         nb=world.n_basins, ncell=world.ncell, nrow=world.nrow, ncol=world.ncol, y0=start_year,
                         y1=end_year, ov=', '.join(output_vars), runoff_sec=runoff_sec, future=future,
                         routing_sec=routing_sec))
     return ini
+
+
+def pet_ext_forcing(world, forcing):
+    """Hargreaves-Samani / Thornthwaite inputs from a ``make_forcing`` set: tas, tmin, tmax = 2 tas - tmin."""
+    return {'tas': forcing['tas'], 'tmin': forcing['tmin'], 'tmax': 2.0 * forcing['tas'] - forcing['tmin'],
+            'precip': forcing['precip'], 'abcd_tmin': forcing['abcd_tmin']}
+
+
+def write_pet_ext_example(root, world, forcing, start_year, end_year, pet='hs', runoff_spinup=25, **kw):
+    """Write an hs_abcd_mrtm (``pet='hs'``) or thornthwaite_abcd_mrtm input tree under ``root``; returns the .ini.
+    ``forcing``: ``pet_ext_forcing`` keys; the other keywords as ``write_hgm_example``'s (``daylight``, ``obs``, ...)."""
+    if pet not in ('hs', 'thornthwaite'):
+        raise ValueError("pet must be 'hs' or 'thornthwaite', not '{}'".format(pet))
+    kw.setdefault('project', '{}_abcd_mrtm_synth'.format(pet))
+    return write_hgm_example(root, world, forcing, start_year, end_year, runoff='abcd', runoff_spinup=runoff_spinup,
+                             pet=pet, **kw)
