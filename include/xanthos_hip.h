@@ -382,6 +382,39 @@ int xh_drought_thresholds(xh_ctx *ctx, int64_t ncell, int32_t nmonths, int32_t m
 int xh_drought_stats(xh_ctx *ctx, int64_t ncell, int32_t nmonths, int32_t nthresh, const double *d_hydro,
                      const double *d_thresh, double *d_severity, double *d_intensity, double *d_duration);
 
+/* ------------------------------------------------------------------ hydropower potential
+ * xh_hpot_qmax replaces hydropower/potential.py:constrain_q (:75-86) row by row: q_max[c] = np.percentile(d_q[c, :],
+ * q_ex * 100) over all nmonths (<= 8192) samples, numpy's "linear" method; the caller passes k_prev / k_next / gamma
+ * exactly as for xh_drought_thresholds.  A NaN in the row gives NaN.
+ * xh_hpot_energy replaces :30-46: per cell and calendar year, the compensated sum (pandas resample("A").sum(), NaN
+ * skipped) of (((c_ef_sww * clip(q, 0, q_max)) * c_hours) * c_twh) * elev[c], times c_ej.  d_year_of_month [nmonths]
+ * int32: the year index 0 .. nyears-1 of each month.  d_E out [ncell, nyears].
+ * xh_hpot_region replaces groupby(key, axis=1).sum() (:50, :61): d_R[g, y] = compensated sum of d_E[cells[j], y] over
+ * j in [indptr[g], indptr[g+1]), in that order.  d_indptr [ngroups + 1], d_cells int64.                              */
+int xh_hpot_qmax(xh_ctx *ctx, int64_t ncell, int32_t nmonths, int32_t k_prev, int32_t k_next, double gamma,
+                 const double *d_q, double *d_qmax);
+int xh_hpot_energy(xh_ctx *ctx, int64_t ncell, int32_t nmonths, int32_t nyears, const int32_t *d_year_of_month,
+                   double c_ef_sww, double c_hours, double c_twh, double c_ej, const double *d_q, const double *d_qmax,
+                   const double *d_elev, double *d_E);
+int xh_hpot_region(xh_ctx *ctx, int32_t ngroups, int32_t nyears, const int64_t *d_indptr, const int64_t *d_cells,
+                   const double *d_E, double *d_R);
+
+/* ------------------------------------------------------------------ hydropower actual
+ * xh_hact_inflow replaces hydropower/actual.py:56-62 and env_flow_constraint (:109-117): d_inflow out [nmonths, ndams] =
+ * d_q[dam_cell[d], t] * catch[d] / assumed[d] * cumecs_to_mm3; d_env out [ndams, 12] by calendar month (month0 = start
+ * month - 1), from the compensated monthly means and numpy's pairwise mean of all months; d_bad out [ndams] int32: 1
+ * where the dam's inflow holds a NaN.  nmonths >= 12.
+ * xh_hact_sim replaces get_power (:124-145) for every dam: d_rc [5, 12, ndams] rule curves (NaN already 1.1), d_par
+ * [5, ndams] = cap, cap_live, q_max, efficiency, head (fall-backs applied); d_power out [nmonths, ndams] (MW), d_annual
+ * out [nyears, ndams] compensated annual means (resample("A").mean()), d_bad_month out [ndams] int32: the first month
+ * with no rule-curve row <= s / cap (the reference's IndexError), else -1.                                           */
+int xh_hact_inflow(xh_ctx *ctx, int64_t ncell, int32_t nmonths, int32_t ndams, int32_t month0, const int64_t *d_dam_cell,
+                   const double *d_catch, const double *d_assumed, double cumecs_to_mm3, const double *d_q, double *d_inflow,
+                   double *d_env, int32_t *d_bad);
+int xh_hact_sim(xh_ctx *ctx, int32_t nmonths, int32_t ndams, int32_t nyears, int32_t month0, const int32_t *d_year_of_month,
+                double sww, double secs_in_month, const double *d_inflow, const double *d_env, const double *d_rc,
+                const double *d_par, double *d_power, double *d_annual, int32_t *d_bad_month);
+
 /* The same objective for SEVERAL basins in one launch, each basin with its own population: one basin alone is only
  * months x ~1.7 us of dependent chain, far too little to fill the chip.  h_ncell [nbasins]; h_pars [nbasins, nmembers,
  * npar]; h_pet_t / h_precip_t / h_tmin_t / h_area: host arrays of nbasins DEVICE pointers ([nmonths, ncell_b] each;

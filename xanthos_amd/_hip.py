@@ -121,6 +121,11 @@ SIGNATURES = {
     'xh_nan_to_num': (c_int, [_P, _P, c_int64]),
     'xh_drought_thresholds': (c_int, [_P, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_double, _P, _P]),
     'xh_drought_stats': (c_int, [_P, c_int64, c_int32, c_int32, _P, _P, _P, _P, _P]),
+    'xh_hpot_qmax': (c_int, [_P, c_int64, c_int32, c_int32, c_int32, c_double, _P, _P]),
+    'xh_hpot_energy': (c_int, [_P, c_int64, c_int32, c_int32, _P, c_double, c_double, c_double, c_double, _P, _P, _P, _P]),
+    'xh_hpot_region': (c_int, [_P, c_int32, c_int32, _P, _P, _P, _P]),
+    'xh_hact_inflow': (c_int, [_P, c_int64, c_int32, c_int32, c_int32, _P, _P, _P, c_double, _P, _P, _P, _P]),
+    'xh_hact_sim': (c_int, [_P, c_int32, c_int32, c_int32, c_int32, _P, c_double, c_double, _P, _P, _P, _P, _P, _P, _P]),
     'xh_synth_forcing': (c_int, [_P, c_uint64, c_double, c_int64, c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
 }
 
@@ -143,7 +148,11 @@ def lib():
         except OSError as exc:
             raise HipUnavailable('cannot load {}: {}'.format(LIB_PATH, exc))
         for name, (res, args) in SIGNATURES.items():
-            fn = getattr(handle, name)      # AttributeError here = header / library mismatch
+            try:
+                fn = getattr(handle, name)
+            except AttributeError:          # a library built from older sources than these signatures
+                raise HipUnavailable('{} lacks {}: it was built from older sources; rebuild it (make -C xanthos_amd/csrc)'
+                                     .format(LIB_PATH, name))
             fn.restype = res
             fn.argtypes = args
         if handle.xh_abi_version() != ABI_VERSION:
@@ -522,6 +531,29 @@ class Context:
     def drought_stats(self, ncell, nmonths, nthresh, hydro, thresh, severity, intensity, duration):
         self._check(lib().xh_drought_stats(self.handle, ncell, nmonths, nthresh, _dptr(hydro), _dptr(thresh),
                                            _dptr(severity), _dptr(intensity), _dptr(duration)))
+
+    # ---- hydropower (csrc/xh_hydro.hip)
+    def hpot_qmax(self, ncell, nmonths, k_prev, k_next, gamma, q, qmax):
+        self._check(lib().xh_hpot_qmax(self.handle, ncell, nmonths, k_prev, k_next, float(gamma), _dptr(q), _dptr(qmax)))
+
+    def hpot_energy(self, ncell, nmonths, nyears, year_of_month, c_ef_sww, c_hours, c_twh, c_ej, q, qmax, elev, E):
+        self._check(lib().xh_hpot_energy(self.handle, ncell, nmonths, nyears, _dptr(year_of_month), float(c_ef_sww),
+                                         float(c_hours), float(c_twh), float(c_ej), _dptr(q), _dptr(qmax), _dptr(elev),
+                                         _dptr(E)))
+
+    def hpot_region(self, ngroups, nyears, indptr, cells, E, R):
+        self._check(lib().xh_hpot_region(self.handle, ngroups, nyears, _dptr(indptr), _dptr(cells), _dptr(E), _dptr(R)))
+
+    def hact_inflow(self, ncell, nmonths, ndams, month0, dam_cell, catch, assumed, cumecs_to_mm3, q, inflow, env, bad):
+        self._check(lib().xh_hact_inflow(self.handle, ncell, nmonths, ndams, month0, _dptr(dam_cell), _dptr(catch),
+                                         _dptr(assumed), float(cumecs_to_mm3), _dptr(q), _dptr(inflow), _dptr(env),
+                                         _dptr(bad)))
+
+    def hact_sim(self, nmonths, ndams, nyears, month0, year_of_month, sww, secs_in_month, inflow, env, rc, par, power,
+                 annual, bad_month):
+        self._check(lib().xh_hact_sim(self.handle, nmonths, ndams, nyears, month0, _dptr(year_of_month), float(sww),
+                                      float(secs_in_month), _dptr(inflow), _dptr(env), _dptr(rc), _dptr(par),
+                                      _dptr(power), _dptr(annual), _dptr(bad_month)))
 
     # ---- bench support
     def synth_forcing(self, seed, ncell, nmonths, lat, out, nan_frac=0.001, cell_ids=None):

@@ -427,6 +427,31 @@ class Components:
             AccessibleWater(self.s, self.data, self.Q)
             logging.info('---Accessible Water has finished successfully: %s seconds ------' % (time.time() - t0))
 
+    def _routed_flow(self):
+        """Avg_ChFlow for a post-processor: the DeviceArray in HBM after a device-resident simulation (on a sharded run the
+        root's gathered array, in grid order), without the download the host property would make."""
+        if self.pipe is not None and 'Avg_ChFlow' not in self._host and self.pipe.plan is not None:
+            return self.pipe.out[_RESULTS['Avg_ChFlow']]
+        return self.Avg_ChFlow
+
+    def hydropower_potential(self):
+        """Hydropower potential per GCAM region (components.py:411-419)."""
+        if self.s.CalculateHydropowerPotential and self.is_root:
+            from .hydropower.potential import HydropowerPotential
+            logging.info('---Start Hydropower Potential:')
+            t0 = time.time()
+            HydropowerPotential(self.s, self._routed_flow())
+            logging.info('---Hydropower Potential has finished successfully: %s seconds ------' % (time.time() - t0))
+
+    def hydropower_actual(self):
+        """Actual hydropower per GCAM region (components.py:421-429)."""
+        if self.s.CalculateHydropowerActual and self.is_root:
+            from .hydropower.actual import HydropowerActual
+            logging.info('---Start Hydropower Actual:')
+            t0 = time.time()
+            HydropowerActual(self.s, self._routed_flow())
+            logging.info('---Hydropower Actual has finished successfully: %s seconds ------' % (time.time() - t0))
+
     def output_simulation(self):
         """Aggregate / convert on the device and write the selected variables (components.py:441-474)."""
         from .data_writer.out_writer import OutWriter

@@ -31,6 +31,8 @@ class ConfigRunner:
         t = time.time()
         c.accessible_water()          # post-processors, then the outputs: the reference's order (configurations.py:117-136)
         c.drought()
+        c.hydropower_potential()
+        c.hydropower_actual()
         c.timings['post'] = time.time() - t
         t = time.time()
         c.output_simulation()

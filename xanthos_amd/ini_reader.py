@@ -5,7 +5,7 @@ The reference parses the file with ``configobj`` (not installed here) and flatte
 ``[[subsection]]``, ``key = value``, ``#`` comments, comma lists, optional quotes) and builds the same attributes for
 the sections the hot path reads: ``[Project]``, ``[PET][[penman-monteith]]`` / ``[[hargreaves]]`` /
 ``[[hargreaves-samani]]`` / ``[[thornthwaite]]``,
-``[Runoff][[abcd]]`` / ``[[gwam]]``, ``[Routing][[mrtm]]`` and ``[Calibrate]``.  Selector strings are lower-cased and validated exactly like the
+``[Runoff][[abcd]]`` / ``[[gwam]]``, ``[Routing][[mrtm]]``, ``[Calibrate]`` and the post-processors' sections.  Selector strings are lower-cased and validated exactly like the
 reference (:214, :309, :397); selectors that belong to other reference modules are rejected with a clear message
 because only the MI355X hot path is implemented here.  ``update()`` keeps the in-memory override hook (:598-607).
 """
@@ -158,11 +158,12 @@ class ConfigReader:
                 raise ValidationException('CalculateAccessibleWater = 1 needs AccWatDir in [Project].')
             self.AccWatDir = os.path.join(self.InputFolder, p['AccWatDir'])
             self.configure_acc_water(c['AccessibleWater'])
-        for flag in ('PerformDiagnostics', 'CreateTimeSeriesPlot', 'CalculateHydropowerPotential',
-                     'CalculateHydropowerActual'):
+        for flag in ('PerformDiagnostics', 'CreateTimeSeriesPlot'):
             if getattr(self, flag):
                 raise ValidationException("{} = 1: this post-processor belongs to the reference's host-side modules and "
                                           "is not part of this package.".format(flag))
+        if self.CalculateHydropowerPotential or self.CalculateHydropowerActual:
+            self.configure_hydropower(c, p)
         check_modules(self)
         if self.calibrate:
             if 'Calibrate' not in c:
@@ -370,6 +371,68 @@ class ConfigReader:
         self.Env_FlowPercent = float(cfg['Env_FlowPercent'])
         if self.StartYear > self.GCAM_StartYear or self.EndYear < self.GCAM_EndYear:
             raise ValidationException('Accessible water range of GCAM years are outside the range of years in climate data.')
+
+    def configure_hydropower(self, c, p):
+        """[HydropowerPotential] / [HydropowerActual] (ini_reader.py:95-105, :488-504).  HydActDir is read whenever either
+        switch is on (the reference reads it only with [HydropowerActual], so potential alone dies there)."""
+        if 'HydActDir' not in p:
+            raise ValidationException('CalculateHydropowerPotential / CalculateHydropowerActual = 1 needs HydActDir in '
+                                      '[Project].')
+        if self.routing_module == 'none':
+            raise ValidationException('the hydropower post-processors read the routed channel flow (Avg_ChFlow): they need '
+                                      'routing_module = mrtm, not none.')
+        self.HydActDir = os.path.join(self.InputFolder, p['HydActDir'])
+        self.GridData = os.path.join(self.HydActDir, 'gridData.csv')
+        try:
+            with open(self.GridData) as fh:
+                nrows = sum(1 for line in fh if line.strip()) - 1
+        except OSError as exc:
+            raise ValidationException('cannot read the hydropower grid data {}: {}'.format(self.GridData, exc))
+        if nrows != self.ncell:
+            raise ValidationException('{} has {} rows; its rows are matched to the {} cells by position.'.format(
+                self.GridData, nrows, self.ncell))
+        if self.CalculateHydropowerPotential:
+            m = self._hydro_section(c, 'HydropowerPotential')
+            self.hpot_start_date = self._month(m, 'hpot_start_date', 'HydropowerPotential')
+            try:
+                self.q_ex = float(self._hydro_key(m, 'q_ex', 'HydropowerPotential'))
+                self.ef = float(self._hydro_key(m, 'ef', 'HydropowerPotential'))
+            except ValueError as exc:
+                raise ValidationException('[HydropowerPotential]: {}'.format(exc))
+            if not 0.0 <= self.q_ex <= 1.0:
+                raise ValidationException('[HydropowerPotential] q_ex = {} is a quantile and must lie in [0, 1].'.format(
+                    self.q_ex))
+        if self.CalculateHydropowerActual:
+            m = self._hydro_section(c, 'HydropowerActual')
+            self.hact_start_date = self._month(m, 'hact_start_date', 'HydropowerActual')
+            self.HydroDamData = os.path.join(self.HydActDir, 'resData_1593.csv')
+            self.MissingCap = os.path.join(self.HydActDir, 'simulated_cap_by_country.csv')
+            self.rule_curves = os.path.join(self.HydActDir, 'rule_curves_1593.npy')
+            self.DrainArea = os.path.join(self.HydActDir, 'DRT_half_SourceArea_globe_float.txt')
+
+    @staticmethod
+    def _hydro_section(c, name):
+        m = c.get(name)
+        if not isinstance(m, dict):
+            raise ValidationException('Calculate{0} = 1 but the config file has no [{0}] section.'.format(name))
+        return m
+
+    @staticmethod
+    def _hydro_key(m, key, name):
+        if key not in m:
+            raise ValidationException('{} is required in the [{}] section of the config file.'.format(key, name))
+        return m[key]
+
+    @classmethod
+    def _month(cls, m, key, name):
+        """A start month in the reference's "M/YYYY" form, kept as written (the modules hand it to pd.period_range)."""
+        text = str(cls._hydro_key(m, key, name)).strip()
+        import pandas as pd
+        try:
+            pd.Period(text, freq='M')
+        except (ValueError, TypeError) as exc:
+            raise ValidationException('[{}] {} = {!r} is not a month ("M/YYYY"): {}'.format(name, key, text, exc))
+        return text
 
     def ck_year(self, yr):
         """A year inside the run (ini_reader.py:547-551)."""

@@ -521,3 +521,75 @@ def write_pet_ext_example(root, world, forcing, start_year, end_year, pet='hs', 
     kw.setdefault('project', '{}_abcd_mrtm_synth'.format(pet))
     return write_hgm_example(root, world, forcing, start_year, end_year, runoff='abcd', runoff_spinup=runoff_spinup,
                              pet=pet, **kw)
+
+
+def write_hydro_inputs(root, world, ndams=40, seed=11, nan_rule_frac=0.1, ties=True, dir_name='hydropower'):
+    """Write a hydropower input tree matched to ``world`` under ``root``/input/``dir_name`` (the reference's HydActDir,
+    ini_reader.py:495-504) and return its path.
+
+    gridData.csv (ID, long, lati from world.coords, elevD, regID 0..32, inGrandELEC); resData_1593.csv with LONG_DD / LAT_DD
+    first (the reference reads them with iloc[:, 0:2]), some CAPLIVE / HEAD NaN (the fall-backs); a few dams exactly on a
+    cell border (idxmin ties: the first value in gridData order wins); simulated_cap_by_country.csv (factor, GCAM_ID by
+    the position of the sorted countries); rule_curves_1593.npy [5, 12, ndams] with NaN entries (-> 1.1) and a first row
+    of 0 (a release option for every storage); DRT_half_SourceArea_globe_float.txt, 360 x 720.  Dams sit on distinct
+    cells; the routed flow of those cells must be finite (``make_forcing(..., nan_precip=False)``) for every dam to run.
+    """
+    import os
+    import pandas as pd
+    rng = np.random.default_rng(seed)
+    hyd = os.path.join(root, 'input', dir_name)
+    os.makedirs(hyd, exist_ok=True)
+    n = world.ncell
+    lon, lat = world.coords[:, 1], world.coords[:, 2]
+    grid = pd.DataFrame({'ID': np.arange(1, n + 1), 'long': lon, 'lati': lat,
+                         'elevD': np.round(rng.uniform(0.0, 400.0, n), 3), 'regID': rng.integers(0, 33, n),
+                         'inGrandELEC': (rng.random(n) < 0.6).astype(int)})
+    grid.loc[rng.random(n) < 0.05, 'elevD'] = 0.0
+    grid.to_csv(os.path.join(hyd, 'gridData.csv'), index=False)
+    cells = rng.choice(n, size=min(ndams, n), replace=False)
+    nd = len(cells)
+    dlon = lon[cells] + rng.uniform(-0.2, 0.2, nd)
+    dlat = lat[cells] + rng.uniform(-0.2, 0.2, nd)
+    if ties:
+        # half a cell east / north of the cell centre: two longitudes (latitudes) are equally near; keep such a dam only
+        # where the pair the reference's idxmin picks is a land cell
+        pairs = set(zip(lon.tolist(), lat.tolist()))
+        for d in range(0, nd, 5):
+            tl, tt = lon[cells[d]] + 0.25, lat[cells[d]] + (0.25 if d % 10 == 0 else 0.0)
+            pl = lon[np.argmin(np.abs(lon - tl))]
+            pt = lat[np.argmin(np.abs(lat - tt))]
+            if (pl, pt) in pairs:
+                dlon[d], dlat[d] = tl, tt
+    countries = np.array(['C{:02d}'.format(k) for k in range(7)])
+    cap = rng.uniform(50.0, 3000.0, nd)
+    res = pd.DataFrame({'LONG_DD': dlon, 'LAT_DD': dlat, 'DAM_NAME': ['Dam {}'.format(k) for k in range(nd)],
+                        'COUNTRY': countries[np.arange(nd) % len(countries)], 'CAP': cap,
+                        'CAPLIVE': cap * rng.uniform(0.3, 1.0, nd), 'ECAP': rng.uniform(20.0, 2000.0, nd),
+                        'FLOW_M3S': rng.uniform(20.0, 600.0, nd), 'EFF': rng.uniform(0.8, 0.95, nd),
+                        'HEAD': rng.uniform(10.0, 200.0, nd), 'CATCH': rng.uniform(500.0, 20000.0, nd)})
+    res.loc[rng.random(nd) < 0.2, 'CAPLIVE'] = np.nan
+    res.loc[rng.random(nd) < 0.2, 'HEAD'] = np.nan
+    res.to_csv(os.path.join(hyd, 'resData_1593.csv'), index=False)
+    nc = len(np.unique(res['COUNTRY']))
+    pd.DataFrame({'country': np.unique(res['COUNTRY']), 'factor': rng.uniform(1.0, 2.5, nc),
+                  'GCAM_ID': rng.integers(1, 4, nc)}).to_csv(os.path.join(hyd, 'simulated_cap_by_country.csv'), index=False)
+    rc = np.sort(rng.uniform(0.0, 1.05, (5, 12, nd)), axis=0)
+    rc[0] = 0.0
+    rc[1:][rng.random((4, 12, nd)) < nan_rule_frac] = np.nan
+    np.save(os.path.join(hyd, 'rule_curves_1593.npy'), rc)
+    ii, jj = np.mgrid[0:360, 0:720]
+    np.savetxt(os.path.join(hyd, 'DRT_half_SourceArea_globe_float.txt'), 750.0 * (1 + (3 * ii + jj) % 23), fmt='%.1f')
+    return hyd
+
+
+def enable_hydro(ini, hpot_start_date='1/1971', hact_start_date='1/1971', q_ex=0.9, ef=0.85, dir_name='hydropower',
+                 potential=True, actual=True):
+    """Switch the hydropower post-processors on in an .ini written by ``write_example`` / ``write_hgm_example``."""
+    text = open(ini).read()
+    proj = 'HydActDir = {}\nCalculateHydropowerPotential = {}\nCalculateHydropowerActual = {}\n'.format(
+        dir_name, int(potential), int(actual))
+    text = text.replace('\n[PET]', '\n' + proj + '\n[PET]', 1)
+    text += ('\n[HydropowerPotential]\nhpot_start_date = {}\nq_ex = {!r}\nef = {!r}\n'
+             '\n[HydropowerActual]\nhact_start_date = {}\n').format(hpot_start_date, q_ex, ef, hact_start_date)
+    open(ini, 'w').write(text)
+    return ini
