@@ -85,7 +85,8 @@ int xh_transpose(xh_ctx *ctx, const double *d_src, int64_t rows, int64_t cols, d
 /* HIP-event timing of the kernels each entry point launches, accumulated per kernel name on the context's stream.
  * Names: "pm_pet", "abcd_spinup", "abcd_basin_mean", "abcd_sim", "mrtm_route", "calib_abcd", "calib_kge", "calib_de",
  * "agg_time", "agg_spatial", "drought_thresh", "drought_stats", "hargreaves_pet", "gwam_spinup", "gwam_sim",
- * "hs_pet", "trn_daylight", "trn_pet".  xh_timing_get waits for the stream, then returns total milliseconds and launch count. */
+ * "hs_pet", "trn_daylight", "trn_pet", "diag_cell_total", "diag_group_sum".  xh_timing_get waits for the stream, then
+ * returns total milliseconds and launch count. */
 int xh_timing_reset(xh_ctx *ctx);
 /* a caller-named span on the context's stream, read back with xh_timing_get like the library's own timers (one open
  * at a time): e.g. what a step still spends in the write-out gather after the routing kernel has ended                */
@@ -414,6 +415,21 @@ int xh_hact_inflow(xh_ctx *ctx, int64_t ncell, int32_t nmonths, int32_t ndams, i
 int xh_hact_sim(xh_ctx *ctx, int32_t nmonths, int32_t ndams, int32_t nyears, int32_t month0, const int32_t *d_year_of_month,
                 double sww, double secs_in_month, const double *d_inflow, const double *d_env, const double *d_rc,
                 const double *d_par, double *d_power, double *d_annual, int32_t *d_bad_month);
+
+/* ------------------------------------------------------------------ diagnostics
+ * xh_diag_cell_total replaces diagnostics/diagnostics.py:58 (q = np.sum(Q, axis=1) / nyear * area / 1e6) and :62
+ * (np.mean(VIC, axis=1)): d_out[c * out_stride] = (((0.0 + pairwise(d_in[c, :])) / div1) * d_scale[c]) / div2, with
+ * pairwise = np.sum's order over the contiguous row of ncols >= 1 values (blocks of 8192 added in turn, each by numpy's
+ * pairwise_sum; NaN propagates; up to about 50,000 values, whose leaf table fills the LDS) and the multiplication
+ * skipped when d_scale is NULL.
+ * xh_diag_group_sum replaces :111-112 (runoff_df.groupby('id').sum()): d_sums[g, j] = pandas' compensated sum of
+ * d_vals[c, j] over the cells with h_group[c] == g in ascending order, NaN skipped (0-based groups, -1 = no group;
+ * d_vals [ncell, k], d_sums [ngroups, k]; a group without cells gives 0); d_counts [ngroups] out: cells per group.
+ * The time-series plots (time_series.py:Aggregation_Map) use xh_agg_spatial.                                         */
+int xh_diag_cell_total(xh_ctx *ctx, int64_t ncell, int32_t ncols, const double *d_in, double div1, const double *d_scale,
+                       double div2, double *d_out, int64_t out_stride);
+int xh_diag_group_sum(xh_ctx *ctx, int64_t ncell, int32_t k, int32_t ngroups, const int32_t *h_group, const double *d_vals,
+                      double *d_sums, int64_t *d_counts);
 
 /* The same objective for SEVERAL basins in one launch, each basin with its own population: one basin alone is only
  * months x ~1.7 us of dependent chain, far too little to fill the chip.  h_ncell [nbasins]; h_pars [nbasins, nmembers,

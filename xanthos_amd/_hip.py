@@ -126,6 +126,8 @@ SIGNATURES = {
     'xh_hpot_region': (c_int, [_P, c_int32, c_int32, _P, _P, _P, _P]),
     'xh_hact_inflow': (c_int, [_P, c_int64, c_int32, c_int32, c_int32, _P, _P, _P, c_double, _P, _P, _P, _P]),
     'xh_hact_sim': (c_int, [_P, c_int32, c_int32, c_int32, c_int32, _P, c_double, c_double, _P, _P, _P, _P, _P, _P, _P]),
+    'xh_diag_cell_total': (c_int, [_P, c_int64, c_int32, _P, c_double, _P, c_double, _P, c_int64]),
+    'xh_diag_group_sum': (c_int, [_P, c_int64, c_int32, c_int32, _P, _P, _P, _P]),
     'xh_synth_forcing': (c_int, [_P, c_uint64, c_double, c_int64, c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
 }
 
@@ -554,6 +556,16 @@ class Context:
         self._check(lib().xh_hact_sim(self.handle, nmonths, ndams, nyears, month0, _dptr(year_of_month), float(sww),
                                       float(secs_in_month), _dptr(inflow), _dptr(env), _dptr(rc), _dptr(par),
                                       _dptr(power), _dptr(annual), _dptr(bad_month)))
+
+    # ---- diagnostics (csrc/xh_diag.hip)
+    def diag_cell_total(self, ncell, ncols, src, div1, scale, div2, out, out_stride=1):
+        self._check(lib().xh_diag_cell_total(self.handle, ncell, ncols, _dptr(src), float(div1), _dptr(scale), float(div2),
+                                             _dptr(out), out_stride))
+
+    def diag_group_sum(self, ncell, k, ngroups, group_index, vals, sums, counts):
+        gi = np.ascontiguousarray(group_index, dtype=np.int32)
+        self._check(lib().xh_diag_group_sum(self.handle, ncell, k, ngroups, _host_ptr(gi), _dptr(vals), _dptr(sums),
+                                            _dptr(counts)))
 
     # ---- bench support
     def synth_forcing(self, seed, ncell, nmonths, lat, out, nan_frac=0.001, cell_ids=None):

@@ -452,6 +452,50 @@ class Components:
             HydropowerActual(self.s, self._routed_flow())
             logging.info('---Hydropower Actual has finished successfully: %s seconds ------' % (time.time() - t0))
 
+    def _runoff(self):
+        """Q for a post-processor: the DeviceArray in HBM after a device-resident simulation (on a sharded run the root's
+        gathered array), without the download the host property would make."""
+        if self.pipe is not None and 'Q' not in self._host:
+            return self.pipe.out[_RESULTS['Q']]
+        return self.Q
+
+    def _diag_maps(self):
+        """The loader's maps as the reference's diagnostics and plots see them.  In a GWAM run its loader sets the basin and
+        country ids of every cell without maximum soil moisture, country or basin to -9999, in place
+        (data_load.py:241-271); those cells then fall out of both post-processors.  The maps of this package's loader
+        stay as read (the writer's aggregation uses them): the change is made on copies, for these two only."""
+        d = self.data
+        if self.s.runoff_module != 'gwam' or d.country_ids is None:
+            return d
+        from types import SimpleNamespace
+        invalid = (np.asarray(d.soil_moisture) == 0) | (d.country_ids == 0) | (d.basin_ids == 0)
+        view = SimpleNamespace(**vars(d))
+        view.country_ids, view.basin_ids = d.country_ids.copy(), d.basin_ids.copy()
+        view.country_ids[invalid] = -9999
+        view.basin_ids[invalid] = -9999
+        return view
+
+    def diagnostics(self):
+        """Runoff diagnostics against the comparison data (components.py:431-439)."""
+        if self.s.PerformDiagnostics and self.is_root:
+            from .diagnostics.diagnostics import Diagnostics
+            logging.info('---Start Diagnostics:')
+            t0 = time.time()
+            Diagnostics(self.s, self._runoff(), self._diag_maps())
+            logging.info('---Diagnostics has finished successfully: %s seconds ------' % (time.time() - t0))
+
+    def plots(self):
+        """Time-series plots of the written q and ac (components.py:476-484), read from the writer without a download."""
+        if self.s.CreateTimeSeriesPlot and self.is_root:
+            from .diagnostics.time_series import TimeSeriesPlot
+            logging.info('---Creating Time Series Plots:')
+            t0 = time.time()
+            w = self._writer
+            q = w.get('q', host=False) if w is not None and 'q' in w.output_names else self._runoff()
+            ac = w.get('avgchflow', host=False) if w is not None and 'avgchflow' in w.output_names else self._routed_flow()
+            TimeSeriesPlot(self.s, q, ac, self._diag_maps())
+            logging.info('---Plots has finished successfully: %s seconds ------' % (time.time() - t0))
+
     def output_simulation(self):
         """Aggregate / convert on the device and write the selected variables (components.py:441-474)."""
         from .data_writer.out_writer import OutWriter

@@ -29,13 +29,18 @@ class ConfigRunner:
         c.simulation(run_pet=self.run_pet, run_runoff=self.run_runoff, run_routing=self.run_routing,
                      pet_num_steps=0, runoff_num_steps=0, routing_num_steps=0, notify='Simulation')
         t = time.time()
-        c.accessible_water()          # post-processors, then the outputs: the reference's order (configurations.py:117-136)
+        c.accessible_water()          # post-processors, the outputs, the plots: the reference's order (configurations.py:117-139)
         c.drought()
         c.hydropower_potential()
         c.hydropower_actual()
+        c.diagnostics()
         c.timings['post'] = time.time() - t
         t = time.time()
         c.output_simulation()
         c.timings['write'] = time.time() - t
+        if self.config.CreateTimeSeriesPlot:
+            t = time.time()
+            c.plots()
+            c.timings['plots'] = time.time() - t
         logging.info('run_model phases (s): ' + ', '.join('{} {:.3f}'.format(k, v) for k, v in c.timings.items()))
         return c

@@ -13,6 +13,7 @@ changes its inputs:
   (:149-182, :226-260)
 * Hargreaves-Samani: tas, tmin and tmax as loaded, NaN kept (:86-90); Thornthwaite: tas through nan_to_num (:137-138),
   on the device after upload unless ``device_transforms = False``
+* diagnostics: the four comparison tables as loaded (:216-220)
 * routing: flow distance < 1000 -> 1000 (:204-205), velocity < 0 -> 0 (:207-208), 2-D DRT maps flattened with the
   reference's ``vectorize`` (:415-425), zero initial channel storage in historic mode (:427-438)
 
@@ -110,6 +111,28 @@ class DataLoader:
         if getattr(s, 'AggregateRunoffCountry', 0) and self.country_ids is None:
             raise ValidationException('AggregateRunoffCountry = 1 needs country.csv and country-names.csv in the '
                                       'reference directory')
+        # the diagnostics and the time-series plots read the maps of the scales they are asked for
+        # (diagnostics.py:84-94, time_series.py:52-68)
+        need_region = need_country = False
+        if getattr(s, 'PerformDiagnostics', 0):
+            need_country |= s.DiagnosticScale in (0, 2)
+            need_region |= s.DiagnosticScale in (0, 3)
+        if getattr(s, 'CreateTimeSeriesPlot', 0):
+            need_country |= s.TimeSeriesScale not in (1, 3)
+            need_region |= s.TimeSeriesScale not in (1, 2)
+        if need_region and self.region_ids is None:
+            raise ValidationException('the diagnostics / time-series scale asked for needs region32_grids.csv and '
+                                      'Rgn32Names.csv in the reference directory')
+        if need_country and self.country_ids is None:
+            raise ValidationException('the diagnostics / time-series scale asked for needs country.csv and '
+                                      'country-names.csv in the reference directory')
+        # comparison runoff of the diagnostics (data_load.py:216-220)
+        self.vic = self.unh = self.wbmd = self.wbmc = None
+        if getattr(s, 'PerformDiagnostics', 0):
+            self.vic = np.asarray(load_file(s.VICDataFile, 0, 'q'), dtype=float)
+            self.unh = np.asarray(load_file(s.UNHDataFile, 0, 'q'), dtype=float)
+            self.wbmd = np.asarray(load_file(s.WBMDataFile, 0, 'q'), dtype=float)
+            self.wbmc = np.asarray(load_file(s.WBMCDataFile, 0, 'q'), dtype=float)
 
         if s.pet_module == 'pm':
             et = np.asarray(load_file(s.pm_params), dtype=float)

@@ -158,10 +158,10 @@ class ConfigReader:
                 raise ValidationException('CalculateAccessibleWater = 1 needs AccWatDir in [Project].')
             self.AccWatDir = os.path.join(self.InputFolder, p['AccWatDir'])
             self.configure_acc_water(c['AccessibleWater'])
-        for flag in ('PerformDiagnostics', 'CreateTimeSeriesPlot'):
-            if getattr(self, flag):
-                raise ValidationException("{} = 1: this post-processor belongs to the reference's host-side modules and "
-                                          "is not part of this package.".format(flag))
+        if self.PerformDiagnostics:
+            self.configure_diagnostics(c, p)
+        if self.CreateTimeSeriesPlot:
+            self.configure_timeseries_plot(c)
         if self.CalculateHydropowerPotential or self.CalculateHydropowerActual:
             self.configure_hydropower(c, p)
         check_modules(self)
@@ -409,6 +409,40 @@ class ConfigReader:
             self.MissingCap = os.path.join(self.HydActDir, 'simulated_cap_by_country.csv')
             self.rule_curves = os.path.join(self.HydActDir, 'rule_curves_1593.npy')
             self.DrainArea = os.path.join(self.HydActDir, 'DRT_half_SourceArea_globe_float.txt')
+
+    def configure_diagnostics(self, c, p):
+        """DiagDir and [Diagnostics] (ini_reader.py:74-78, :439-445).  The reference skips this when the section or DiagDir is
+        missing and then dies with an AttributeError in the loader; here that is refused by the flag's name."""
+        m = c.get('Diagnostics')
+        if not isinstance(m, dict):
+            raise ValidationException('PerformDiagnostics = 1 but the config file has no [Diagnostics] section.')
+        if 'DiagDir' not in p:
+            raise ValidationException('PerformDiagnostics = 1 needs DiagDir in [Project].')
+        self.DiagDir = os.path.join(self.InputFolder, p['DiagDir'])
+        for key in ('VICDataFile', 'UNHDataFile', 'WBMDataFile', 'WBMCDataFile'):
+            setattr(self, key, os.path.join(self.DiagDir, self._hydro_key(m, key, 'Diagnostics')))
+        self.DiagnosticScale = self._int(m, 'Scale', 'Diagnostics')
+
+    def configure_timeseries_plot(self, c):
+        """[TimeSeriesPlot] (ini_reader.py:79-83, :447-458): Scale, and MapID as one integer (999: every row) or a list."""
+        m = c.get('TimeSeriesPlot')
+        if not isinstance(m, dict):
+            raise ValidationException('CreateTimeSeriesPlot = 1 but the config file has no [TimeSeriesPlot] section.')
+        self.TimeSeriesScale = self._int(m, 'Scale', 'TimeSeriesPlot')
+        raw = self._hydro_key(m, 'MapID', 'TimeSeriesPlot')
+        try:
+            self.TimeSeriesMapID = [int(v) for v in raw] if isinstance(raw, list) else int(raw)
+        except ValueError as exc:
+            raise ValidationException('[TimeSeriesPlot] MapID = {!r} is not an integer or a list of integers: {}'.format(
+                raw, exc))
+
+    @classmethod
+    def _int(cls, m, key, name):
+        raw = cls._hydro_key(m, key, name)
+        try:
+            return int(raw)
+        except (TypeError, ValueError):
+            raise ValidationException('[{}] {} = {!r} is not an integer.'.format(name, key, raw))
 
     @staticmethod
     def _hydro_section(c, name):

@@ -593,3 +593,49 @@ def enable_hydro(ini, hpot_start_date='1/1971', hact_start_date='1/1971', q_ex=0
              '\n[HydropowerActual]\nhact_start_date = {}\n').format(hpot_start_date, q_ex, ef, hact_start_date)
     open(ini, 'w').write(text)
     return ini
+
+
+def write_diag_inputs(root, world, seed=17, nvic=30, dir_name='diagnostics'):
+    """Write the four comparison tables of the diagnostics (the reference's DiagDir, ini_reader.py:439-445) matched to
+    ``world`` under ``root``/input/``dir_name`` and return its path.
+
+    vic.csv [ncell, nvic] (km3/yr, a few NaN cells), unh.csv [ncell], and the two-column (cell id, value) tables wbm.csv and
+    wbmc.csv: most cells once, some missing, a few ids repeated (the later row wins) and one row with id 0 (the reference
+    puts it on the last cell)."""
+    import os
+    rng = np.random.default_rng(seed)
+    d = os.path.join(root, 'input', dir_name)
+    os.makedirs(d, exist_ok=True)
+    n = world.ncell
+    vic = rng.lognormal(-3.0, 1.5, (n, nvic))
+    vic[rng.random(n) < 0.03] = np.nan
+    np.savetxt(os.path.join(d, 'vic.csv'), vic, delimiter=',', fmt='%.17g')
+    unh = rng.lognormal(-3.0, 1.5, n)
+    unh[rng.random(n) < 0.03] = np.nan
+    np.savetxt(os.path.join(d, 'unh.csv'), unh, fmt='%.17g')
+    for k, name in enumerate(('wbm.csv', 'wbmc.csv')):
+        ids = np.flatnonzero(rng.random(n) < 0.9) + 1
+        ids = np.concatenate([ids, rng.choice(ids, max(1, n // 50)), [0]])
+        vals = rng.lognormal(-3.0 + k, 1.5, len(ids))
+        np.savetxt(os.path.join(d, name), np.stack([ids, vals], axis=1), delimiter=',', fmt='%.17g')
+    return d
+
+
+def enable_diagnostics(ini, diag_scale=0, plot_scale=0, map_id=999, dir_name='diagnostics', diagnostics=True, plots=True):
+    """Switch the diagnostics and / or the time-series plots on in an .ini written by ``write_example`` /
+    ``write_hgm_example`` (DiagDir, [Diagnostics] for ``write_diag_inputs``' files, [TimeSeriesPlot]).  ``map_id``: an
+    integer or a list.  The basin, country and region maps must be in the reference directory (``write_hgm_example``, or
+    ``write_example(..., aggregates=True)``)."""
+    import re
+    text = open(ini).read()
+    text = re.sub(r'\n(PerformDiagnostics|CreateTimeSeriesPlot) *=[^\n]*', '', text)
+    proj = 'DiagDir = {}\nPerformDiagnostics = {}\nCreateTimeSeriesPlot = {}\n'.format(dir_name, int(diagnostics), int(plots))
+    text = text.replace('\n[PET]', '\n' + proj + '\n[PET]', 1)
+    if diagnostics:
+        text += ('\n[Diagnostics]\nVICDataFile = vic.csv\nUNHDataFile = unh.csv\nWBMDataFile = wbm.csv\n'
+                 'WBMCDataFile = wbmc.csv\nScale = {}\n').format(diag_scale)
+    if plots:
+        ids = ', '.join(str(int(i)) for i in map_id) if isinstance(map_id, (list, tuple)) else str(int(map_id))
+        text += '\n[TimeSeriesPlot]\nScale = {}\nMapID = {}\n'.format(plot_scale, ids)
+    open(ini, 'w').write(text)
+    return ini
