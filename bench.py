@@ -14,15 +14,21 @@ line and exits with the worst exit code): the 235 basins of ONE world are sharde
 configs[3]; strong scaling) and every step ends with a single gather of the six outputs to rank 0 -- PET / AET / Q / Sav
 travel on a second stream while the routing runs; the timed region is bracketed by a barrier and a device synchronise
 on both sides and the slowest rank's time is used.
-The figure for N independent whole-world scenarios (one per GPU, no collective) is measured afterwards and printed as
-the secondary object ``replicas``; ``--replicas`` makes that mode the primary one (weak scaling).
+``--replicas`` runs N independent whole-world scenarios instead (one per GPU, no collective; weak scaling).
 ``--workload calib`` runs BASELINE configs[4] (one step = one differential-evolution generation of all 235 basins).
 
-Rank 0 prints ONE JSON line: metric cell-months/s (whole job), the roofline object for the dominant kernel
-(HIP-event durations measured on the library's stream inside this run), per-kernel figures, and -- at N = 1 -- the
-CPU baseline: the numpy oracle (a port of the reference's algorithm) timed on this host.  The run is also a GATE: it exits
-with code 3 (after printing the line, which says why in ``gate``) when a value lies beyond the north-star tolerance,
-a NaN pattern differs or the routed series is not bit-identical to the oracle's.
+Rank 0 prints ONE JSON line: metric cell-months/s (whole job), the roofline object for the dominant kernel and per-kernel
+figures, both from the HIP-event durations of the timed steps on the library's stream.  A plain run does nothing else: it
+sets up, warms up, times the steps, writes ``--dump-outputs`` and prints the line.
+
+``--full`` adds everything that takes runs or work of its own after the timed steps: the kernels' stand-alone times when
+the steps ran in the fed order, and -- at N = 1 -- the routing kernel alone in both of its forms, the PCIe-inclusive
+rates, the CPU baseline (the numpy oracle, a port of the reference's algorithm, timed on this host) with the parity of
+the run against it, and the secondary lines of configs[1] and configs[4]; at N > 1 the figure for N independent
+whole-world scenarios (``replicas``); for ``--workload calib`` the oracle's objective timed and compared.  A ``--full``
+run is also a GATE: it exits with code 3 (after printing the line, which says why in ``gate``) when a value lies beyond
+the north-star tolerance, a NaN pattern differs or the routed series is not bit-identical to the oracle's.  The
+``--no-*`` options leave single parts of ``--full`` out.
 
 ``--dump-outputs DIR`` writes what the last timed step computed -- PET, AET, Q, Sav, ChStorage, Avg_ChFlow (per basin x, fun,
 nfev, nit for ``--workload calib``) -- as DIR/<name>.npy in float64: the cells whose outputs are all finite (the NaN cells
@@ -652,7 +658,7 @@ def calib_measure(args, ctx, rank, world_size, dist, torch, backend, log):
     else:
         result['roofline']['valu_issue'] = {'frac': None, 'refused': 'no counter pass of k_calib_march_m for this configuration in {}'
                                             .format(insts_src)}
-    if rank == 0 and world_size == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world_size == 1 and args.full and not args.no_cpu_baseline:
         from oracle import calib as o_calib, de as o_de
         pop, en = de.state(0)
         lo, hi = np.array([b[0] for b in cfg_bounds()]), np.array([b[1] for b in cfg_bounds()])
@@ -802,13 +808,17 @@ def main():
     ap.add_argument('--replicas', action='store_true',
                     help='N > 1: every rank runs its own whole world (weak scaling) instead of sharding ONE world')
     ap.add_argument('--strong', action='store_true', help='(default for N > 1; kept for compatibility)')
-    ap.add_argument('--no-replica-figure', action='store_true', help='N > 1: skip the secondary replica measurement')
+    ap.add_argument('--no-replica-figure', action='store_true', help='N > 1, --full: skip the secondary replica measurement')
     ap.add_argument('--check-gather', action='store_true',
                     help='N > 1: rank 0 also runs the WHOLE world unsharded and compares the gathered arrays bit for bit')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-end-to-end', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps, also measure and check what takes runs of its own: stand-alone kernel times '
+                         'of a fed step, the routing forms, the PCIe-inclusive rates, the CPU baseline with the parity gate, '
+                         'the secondary lines (N = 1), the replica figure (N > 1)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip the CPU baseline and its parity gate')
+    ap.add_argument('--no-end-to-end', action='store_true', help='--full: skip the routing forms and the PCIe-inclusive rates')
     ap.add_argument('--no-secondary', action='store_true',
-                    help='skip the secondary lines of the default run (BASELINE configs[1]: 10 steps of pm_abcd; configs[4]: 3 '
+                    help='--full: skip the secondary lines (BASELINE configs[1]: 10 steps of pm_abcd; configs[4]: 3 '
                          'generations of the calibration)')
     ap.add_argument('--cpu-full', action='store_true', help='(the default now; kept for compatibility)')
     ap.add_argument('--cpu-pm-years', type=int, default=5)
@@ -1025,7 +1035,9 @@ def main():
              'note': ('the routing kernel is launched after the first max(spin-ups) months of PM and ABCD and fed the other '
                       'months, produced beside it on a second stream (xh_run_fused mode 1): kernel times below overlap, their '
                       'sum exceeds the step' if n_fed else 'the three stages strictly one after the other')}
-    if n_fed:
+    if n_fed and not args.full:
+        order['kernel_times'] = 'as timed inside the fed steps; --full adds each kernel\'s stand-alone time'
+    if n_fed and args.full:
         # PM and ABCD share the chip with the routing kernel in a fed step: their stand-alone times (the figures their
         # rooflines are about) come from three stage-by-stage steps outside the timed region
         gate_ms = ctx.timing('feed_gate')[0] / n_fed
@@ -1157,7 +1169,9 @@ def main():
                                           'slowest rank\'s networks + the gather of ChStorage / Avg_ChFlow behind it',
             'term1_front_ms': term1, 'term2_route_ms': term2, 'term4_gather_tail_ms': term4,
             'modelled_step_ms': (term1 + term2 + (term4 or 0.0) + 0.1) if term4 is not None else None,
-            'measured_step_ms': ms_per_step, 'terms_from': 'rank 0 of this run (HIP events)',
+            'measured_step_ms': ms_per_step,
+            'terms_from': 'rank 0 of this run (HIP events{})'.format(
+                '; PM and ABCD as timed inside the fed steps' if n_fed and not args.full else ''),
             'sequential_substeps': int(sum(int(d * 86400 / 10800) for d in pipe.ndays) +
                                        sum(int(d * 86400 / 10800) for d in pipe.ndays[:args.routing_spinup])) if 'mrtm' in args.stages else 0,
             'note': 'strong scaling of one world is flat by construction (the sub-steps of the routing are sequential whatever the '
@@ -1192,7 +1206,7 @@ def main():
             result['gather']['equals_unsharded_by_output'] = diff
             if rank == 0 and not ok:
                 gate_failed = not args.no_gate
-        if not args.no_replica_figure:
+        if args.full and not args.no_replica_figure:
             # secondary figure: N independent whole-world scenarios, one per GPU (no collective on the data path)
             gather.close()
             for a in list(pipe.out.values()) + list(pipe.forcing.values()):
@@ -1202,7 +1216,7 @@ def main():
             result['replicas'] = {'value': NCELL * args.months * world_size * args.steps / r_elapsed,
                                   'unit': 'cell-months/s', 'ms_per_step': 1e3 * r_elapsed / args.steps,
                                   'scaling': 'weak', 'note': '{} independent scenarios, one per GPU'.format(world_size)}
-    if rank == 0 and world_size == 1:
+    if rank == 0 and world_size == 1 and args.full:
         if 'mrtm' in args.stages and not args.no_end_to_end:
             nsub_all = int(sum(int(d * 86400 / 10800) for d in pipe.ndays)) + \
                 int(sum(int(d * 86400 / 10800) for d in pipe.ndays[:args.routing_spinup]))

@@ -284,6 +284,17 @@ def test_bench_starts_its_own_ranks_without_a_launcher():
         assert got['MASTER_ADDR'] == '127.0.0.1' and int(got['MASTER_PORT']) > 0
 
 
+def test_bench_has_a_full_option():
+    """``bench.py --full`` is the switch for everything beyond the headline figure (CPU baseline, parity gate, secondary
+    measurements); a plain run leaves it off."""
+    import subprocess
+    import sys
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--help'], stdout=subprocess.PIPE,
+                         stderr=subprocess.PIPE, text=True, timeout=120)
+    assert out.returncode == 0, out.stderr[-500:]
+    assert '--full' in out.stdout
+
+
 def test_bench_dump_outputs_sample(tmp_path, monkeypatch):
     """bench.py --dump-outputs: every output as <name>.npy in float64, every value finite.  Rows (cells) with a NaN or an
     inf in any per-cell output are left out of all of them and counted; above the byte budget the finite rows keep the same

@@ -2,7 +2,7 @@
 config 3 timings.  usage: pm_ab.py libA.so libB.so [workload]"""
 import os, subprocess, sys, json
 root = os.path.join(os.path.dirname(os.path.abspath(__file__)), '..')
-code = ("import sys, json; sys.path.insert(0, %r); from xanthos_amd import _hip; _hip.LIB_PATH = sys.argv[1]; sys.argv = ['bench.py', '--workload', sys.argv[2], '--steps', '20', '--warmup', '5', '--no-cpu-baseline', '--no-end-to-end']; "
+code = ("import sys, json; sys.path.insert(0, %r); from xanthos_amd import _hip; _hip.LIB_PATH = sys.argv[1]; sys.argv = ['bench.py', '--full', '--workload', sys.argv[2], '--steps', '20', '--warmup', '5', '--no-cpu-baseline', '--no-end-to-end']; "
         "import runpy; runpy.run_path(%r, run_name='__main__')") % (root, os.path.join(root, 'bench.py'))
 workload = sys.argv[3] if len(sys.argv) > 3 else 'pm_abcd'
 for rep in range(3):

@@ -5,7 +5,7 @@ cd /root/repo
 for rep in 1 2; do
 for v in "XH_RSUM_SEAL=1 XH_FEED_FIRST=192" "XH_RSUM_SEAL=1 XH_FEED_FIRST=256" "XH_RSUM_SEAL=0"; do
   echo "== $v" >> $out/fed_penalty2.txt
-  env $v timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-end-to-end --no-secondary 2>/dev/null | python -c "
+  env $v timeout 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-end-to-end --no-secondary 2>/dev/null | python -c "
 import json,sys
 r=json.loads(sys.stdin.read())
 k=r['kernels']
