@@ -355,12 +355,15 @@ int xh_calib_objective(xh_ctx *ctx, int64_t ncell_b, int32_t nmonths, int32_t sp
 /* ------------------------------------------------------------------ output aggregation
  * xh_agg_time replaces data_writer/out_writer.py:agg_to_year (:237-248) and the mm -> km3 scaling of write()
  * (:111-112): out[c, g] = f(in[c, g*group .. (g+1)*group)) x (d_scale ? d_scale[c] : 1), with f = NaN-skipping sum
- * (mode 0; an all-NaN block gives 0, as pandas does) or NaN-skipping mean (mode 1; all-NaN gives NaN).
+ * (mode 0; an all-NaN block gives 0, as pandas does) or NaN-skipping mean (mode 1; all-NaN gives NaN), both in
+ * pandas' compensated order (groupby.pyx group_sum / group_mean, columns ascending), bit for bit.
  * group = 12 aggregates months to years; group = 1, mode 0 is a plain per-cell scaling (NaN kept).  Mode 2 is
  * np.sum over the block in numpy's own order (eight accumulators, NaN propagates): the yearly totals of
  * accessible/accessible.py:41-42, bit for bit.
- * xh_agg_spatial replaces out_writer.py:agg_spatial (:250-265): out[k, t] = NaN-skipping sum over the cells with
- * h_group[c] == k (h_group is 0-based, -1 = cell not aggregated); groups without cells give NaN.            */
+ * xh_agg_spatial: out[k, t] = plain NaN-skipping sum (ascending cells, from 0.0) over the cells with h_group[c] == k
+ * (h_group is 0-based, -1 = cell not aggregated); groups without cells give NaN.  The order of the plain loops of
+ * time_series.py:Aggregation_Map and accessible.py:50-53; out_writer.py:agg_spatial (pandas' groupby('id').sum(),
+ * compensated) uses xh_diag_group_sum.                                                                       */
 int xh_agg_time(xh_ctx *ctx, int64_t ncell, int32_t ncols, int32_t group, int32_t mode, const double *d_scale,
                 const double *d_in, double *d_out);
 int xh_agg_spatial(xh_ctx *ctx, int64_t ncell, int32_t ncols, int32_t n_groups, const int32_t *h_group,

@@ -17,6 +17,8 @@ Fixtures written:
   mrtm.npz    streamrouting for 28/29/30/31-day months + Components.calculate_routing (3 spin-up + 5 months)
   kge.npz     objective_kge(basin_runoff) for 16 parameter vectors x 2 basins, both units, with / without tmin
   writer.npz  OutWriter.agg_to_year (sum / mean), mm -> km3 conversion, agg_spatial with an empty id and NaN cells
+  writer_hostile.npz  the same on 224 cells x 48 months of values where the summation order shows (pandas' compensated
+              sums: cancellations, NaN, +/-inf, -0.0, subnormals), agg_spatial with names from 1 and from 0
   drought.npz DroughtStats.getthresh / calculate_thresholds (nper 1 and 12) and droughtstats (K = 1 and 12) on 80 cells
               x 30 years with NaN, constant and zero-threshold cells
   accessible.npz  AccessibleWater end to end (its csv) + RollingWindowFilter / QInGCAMYears / accessible_water pieces
@@ -288,6 +290,40 @@ def golden_writer():
     print('writer.npz', ysum.shape, spatial.shape, int(np.isnan(spatial).sum()))
 
 
+def golden_writer_hostile():
+    """The same OutWriter methods on values where the summation order shows (tests/writer_np.py:hostile): sums and means
+    of years with exact cancellations, NaN / inf / -0.0 / subnormals, and spatial sums with names without cells, ids
+    0, -9999 and beyond the names, +inf with -inf in one basin and a lone inf in another, names from 1 and from 0."""
+    import pandas as pd
+    from xanthos.data_writer.out_writer import OutWriter
+    sys.path.insert(0, os.path.join(HERE, '..'))
+    from writer_np import hostile
+    rng = np.random.default_rng(4242)
+    ncell, nm, nnames = 224, 48, 12
+    q = hostile(rng, ncell, nm)
+    area = rng.uniform(800, 3100, ncell)
+    ids = rng.integers(1, nnames + 3, ncell)          # 13, 14: beyond the names (both numberings)
+    ids[ids == 5] = 6                                 # name 5 (and 4 when numbered from 0) without cells
+    ids[::17] = 0                                     # a name only when numbered from 0
+    ids[3::29] = -9999
+    for c, v in ((100, np.inf), (101, -np.inf), (102, 1e16), (103, 1.0), (104, 1.0)):
+        q[c, 40], ids[c] = v, 2                       # +inf with -inf in name 2 (name 1 from 0), month 40
+    q[105, 41], ids[105] = np.inf, 3                  # a lone inf in name 3, month 41
+    ow = object.__new__(OutWriter)
+    ysum = ow.agg_to_year(pd.DataFrame(q), 'sum').values
+    ymean = ow.agg_to_year(pd.DataFrame(q), 'mean').values
+    km3 = pd.DataFrame(q).multiply(area / 1e6, axis=0).values
+    ysum_km3 = pd.DataFrame(ysum).multiply(area / 1e6, axis=0).values
+    names = np.array(['n%d' % i for i in range(nnames)])
+    sp = lambda a, inc: ow.agg_spatial(pd.DataFrame(a), ids, names, inc_name_idx=inc).drop(columns='name').values
+    spatial1, spatial0, spatial_year = sp(q, True), sp(q, False), sp(ysum_km3, True)
+    np.savez_compressed(os.path.join(HERE, 'writer_hostile.npz'), q=q, area=area, ids=ids, n_names=nnames, ysum=ysum,
+                        ymean=ymean, km3=km3, ysum_km3=ysum_km3, spatial1=spatial1.astype(float),
+                        spatial0=spatial0.astype(float), spatial_year=spatial_year.astype(float))
+    print('writer_hostile.npz', ysum.shape, spatial1.shape, int(np.isnan(ysum).sum()), int(np.isinf(ysum).sum()),
+          int(np.isnan(spatial1).sum()), int(np.isinf(spatial1).sum()))
+
+
 # ----------------------------------------------------------------------------------------------------- drought
 def golden_drought():
     """drought_stats.py:69-171 on a crafted [ntime, ngrid] series."""
@@ -438,6 +474,7 @@ if __name__ == '__main__':
     golden_mrtm(topo, w)
     golden_kge()
     golden_writer()
+    golden_writer_hostile()
     golden_drought()
     golden_accessible()
     golden_loader()

@@ -3,6 +3,8 @@
 tests/golden/make_golden.py imported JGCRI/xanthos v2.4.1 in the build container and stored crafted inputs with
 the reference's outputs.  These tests pin every oracle function to those outputs (CPU only).
 """
+import os
+import sys
 from types import SimpleNamespace
 
 import numpy as np
@@ -165,14 +167,50 @@ def test_kge_objective_matches_reference(golden, basin, unit, tag):
 
 
 def test_writer_aggregation_matches_reference(golden):
+    """oracle/writer.py (pandas' compensated sums restated) equals the reference's OutWriter bit for bit."""
     from oracle import writer as o_writer
+    eq = lambda a, b: np.array_equal(a, b, equal_nan=True)
     g = golden('writer')
-    assert np.allclose(o_writer.agg_to_year(g['q'], 'sum'), g['ysum'], rtol=1e-13, atol=0)
-    assert np.allclose(o_writer.agg_to_year(g['q'], 'mean'), g['ymean'], rtol=1e-13, atol=0, equal_nan=True)
-    assert np.allclose(o_writer.mm_to_km3(g['q'], g['area']), g['km3'], rtol=1e-15, atol=0, equal_nan=True)
+    assert eq(o_writer.agg_to_year(g['q'], 'sum'), g['ysum'])
+    assert eq(o_writer.agg_to_year(g['q'], 'mean'), g['ymean'])
+    assert eq(o_writer.mm_to_km3(g['q'], g['area']), g['km3'])
+    assert eq(o_writer.mm_to_km3(o_writer.agg_to_year(g['q'], 'sum'), g['area']), g['ysum_km3'])
     sp = o_writer.agg_spatial(o_writer.mm_to_km3(o_writer.agg_to_year(g['q'], 'sum'), g['area']), g['ids'], 8)
-    assert np.allclose(sp, g['spatial'], rtol=1e-13, atol=0, equal_nan=True)
+    assert eq(sp, g['spatial'])
     assert np.isnan(sp[4]).all() and np.isnan(sp[7]).all()          # ids 5 and 8 have no cells
+    # values where the order shows: cancellations, NaN / +-inf / -0.0 / subnormals, names from 1 and from 0
+    h = golden('writer_hostile')
+    q, ids, n = h['q'], h['ids'], int(h['n_names'])
+    ysum = o_writer.agg_to_year(q, 'sum')
+    assert eq(ysum, h['ysum']) and eq(o_writer.agg_to_year(q, 'mean'), h['ymean'])
+    assert ysum[0, 0] == 10.0                                       # [1e16, 1, 1, -1e16, 1 x 8]: a plain sum gives 8.0
+    assert eq(o_writer.mm_to_km3(q, h['area']), h['km3'])
+    assert eq(o_writer.mm_to_km3(ysum, h['area']), h['ysum_km3'])
+    assert eq(o_writer.agg_spatial(q, ids, n, first_id=1), h['spatial1'])
+    assert eq(o_writer.agg_spatial(q, ids, n, first_id=0), h['spatial0'])
+    assert eq(o_writer.agg_spatial(h['ysum_km3'], ids, n, first_id=1), h['spatial_year'])
+    assert np.isnan(h['spatial1'][1, 40]) and h['spatial1'][2, 41] == np.inf     # +inf with -inf; a lone inf
+
+
+@pytest.mark.parametrize('seed', [1, 2, 3])
+def test_writer_oracle_matches_pandas(seed):
+    """The oracle's restatement against pandas itself, the library the reference aggregates with (groupby sum / mean over
+    blocks of 12 columns, groupby('id').sum() over cells), on seeded hostile values."""
+    pytest.importorskip('pandas')
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import writer_np as W
+    from oracle import writer as o_writer
+    rng = np.random.default_rng(seed)
+    ncell, nm = (1, 257, 3000)[seed - 1], (12, 48, 120)[seed - 1]
+    q = W.hostile(rng, ncell, nm)
+    for func in ('sum', 'mean'):
+        assert np.array_equal(o_writer.agg_to_year(q, func), W.pandas_agg_to_year(q, func), equal_nan=True), func
+    nn = max(2, ncell // 40)
+    ids = rng.integers(-2, nn + 3, ncell)
+    ids[ids == nn // 2] = -9999                                     # a name without cells
+    for first in (0, 1):
+        assert np.array_equal(o_writer.agg_spatial(q, ids, nn, first_id=first), W.pandas_agg_spatial(q, ids, nn, first),
+                              equal_nan=True), first
 
 
 def test_drought_matches_reference(golden):

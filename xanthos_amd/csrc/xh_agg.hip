@@ -1,15 +1,27 @@
 // Output aggregation on the device (first "next" row after the hot path).
 //
 // Replaces the array math of xanthos/data_writer/out_writer.py: agg_to_year (:237-248, pandas groupby over blocks of
-// 12 month columns: NaN-skipping sum, or mean for channel flow), the mm -> km3 conversion of write() (:111-112,
-// rows x area / 1e6) and agg_spatial (:250-265, NaN-skipping sum of the cells of each basin / country / region;
-// ids without cells give NaN rows).  The six outputs are already in HBM after the pipeline, yearly aggregation
-// shrinks what crosses PCIe (or the multi-GPU gather) 12x.
+// 12 month columns: NaN-skipping sum, or mean for channel flow) and the mm -> km3 conversion of write() (:111-112,
+// rows x area / 1e6).  The six outputs are already in HBM after the pipeline, yearly aggregation shrinks what crosses
+// PCIe (or the multi-GPU gather) 12x.
+//
+//   k_agg_time     modes 0 / 1: pandas' compensated group sum / mean (xh_kahan.h) over each block, columns in
+//                  ascending order, the value the reference writes bit for bit.  Mode 2: np.sum's pairwise order
+//                  (accessible water).  group = 1, mode 0: the plain conversion, NaN kept.
+//   k_agg_spatial  per group, the cells in ascending order added to 0.0, NaN skipped, groups without cells NaN: the
+//                  plain loops of time_series.py:Aggregation_Map and of accessible water's basin totals.  The writer's
+//                  agg_spatial (pandas' groupby('id').sum(), compensated) runs on xh_diag_group_sum instead.
+//
+// The compensated update depends on the absence of fp contraction (the Makefile builds with -ffp-contract=off; the
+// pragma keeps it so if the file is ever compiled on its own).
 #include <algorithm>
 #include <cmath>
 #include <vector>
 
 #include "xh_common.h"
+#include "xh_kahan.h"
+
+#pragma clang fp contract(off)
 
 namespace {
 
@@ -46,14 +58,12 @@ __global__ void __launch_bounds__(256) k_agg_time(int64_t ncell, int ncols, int 
         const int64_t c = i / ng;
         const int g = (int)(i - c * ng);
         const double *p = in + c * (int64_t)ncols + (int64_t)g * group;
-        double sum = 0.0;
+        double sum = 0.0, comp = 0.0;
         int cnt = 0;
         for (int j = 0; j < group; ++j) {
             const double v = p[j];
-            if (v == v) {
-                sum += v;
-                ++cnt;
-            }
+            cnt += v == v;
+            kahan_add(sum, comp, v);
         }
         double r = mode == 0 ? sum : (cnt ? sum / (double)cnt : NAN);     // pandas: sum skips NaN (all-NaN -> 0), mean -> NaN
         if (group == 1 && mode == 0) r = p[0];                             // plain conversion keeps NaN
@@ -63,7 +73,7 @@ __global__ void __launch_bounds__(256) k_agg_time(int64_t ncell, int ncols, int 
     }
 }
 
-// block <-> (group id, tile of 256 columns); cells of the group are summed in index order
+// block <-> (group id, tile of 256 columns); cells of the group are summed in index order, plainly (not pandas' order)
 __global__ void __launch_bounds__(256) k_agg_spatial(int ncols, const int *__restrict__ ptr, const int *__restrict__ cells,
                                                      const double *__restrict__ in, double *__restrict__ out) {
     const int k = blockIdx.x;

@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "xh_common.h"
+#include "xh_kahan.h"
 
 #pragma clang fp contract(off)
 
@@ -123,17 +124,6 @@ __global__ void __launch_bounds__(TOTAL_THREADS) k_diag_cell_total(int64_t ncell
         }
         __syncthreads();                                   // the next cell overwrites the LDS
     }
-}
-
-// pandas' compensated add (groupby.pyx group_sum; the same update as xh_hydro.hip's): NaN skipped, a NaN compensation
-// (an infinite value went in) reset to 0
-__device__ __forceinline__ void kahan_add(double &s, double &comp, double v) {
-    if (v != v) return;
-    const double y = v - comp;
-    const double t = s + y;
-    comp = t - s - y;
-    if (comp != comp) comp = 0.0;
-    s = t;
 }
 
 // thread <-> (group, column); the group's cells in ascending order (CSR from the host)

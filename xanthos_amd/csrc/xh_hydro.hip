@@ -27,6 +27,7 @@
 #include <cstdint>
 
 #include "xh_common.h"
+#include "xh_kahan.h"
 
 #pragma clang fp contract(off)
 
@@ -45,7 +46,7 @@ __device__ __forceinline__ double key_value(uint64_t k) {
     return __longlong_as_double((long long)b);
 }
 
-// pandas' compensated add (groupby.pyx group_sum / group_mean): NaN skipped, an infinite compensation reset to 0
+// pandas' compensated add (xh_kahan.h) with the count of the values that went in (group_mean divides by it)
 struct Kahan {
     double s, c;
     int n;
@@ -53,11 +54,7 @@ struct Kahan {
     __device__ void add(double v) {
         if (v != v) return;
         ++n;
-        const double y = v - c;
-        const double t = s + y;
-        c = t - s - y;
-        if (c != c) c = 0.0;
-        s = t;
+        kahan_add(s, c, v);
     }
 };
 

@@ -3,7 +3,8 @@
 Same constructor and methods as the reference class (:33-265): ``OutWriter(settings, grid_areas, all_outputs)``,
 ``write()``, ``get(var)``, ``write_aggregates(ref, values, basin, country, region)``.  Month -> year aggregation
 (sum; mean for ``avgchflow``, :100-108), the mm -> km3 conversion (:111-112) and the basin / country / region sums
-(:250-265) run as HIP kernels (csrc/xh_agg.hip) on arrays that may already be resident in HBM; only the (12x smaller
+(:250-265) run as HIP kernels (csrc/xh_agg.hip, xh_diag.hip) on arrays that may already be resident in HBM, adding in
+pandas' compensated order so that the values written equal the reference's bit for bit; only the (12x smaller
 for yearly output) results cross PCIe.  Files are written as ``.csv`` (OutputFormat 1, the reference's layout:
 an ``id`` column of 1-based cell ids and one column per time step) or ``.npy`` (4); NetCDF / MATLAB / parquet
 (0, 2, 3) need pandas writers outside the hot path and raise.
@@ -73,17 +74,22 @@ class OutWriter:
         return out
 
     def agg_spatial(self, arr, id_map, n_ids, first_id=1):
-        """[ncell, t] -> [n_ids, t]: NaN-skipping sums per id (:250-265); ids first_id .. first_id + n_ids - 1."""
+        """[ncell, t] -> [n_ids, t]: per id, pandas' compensated NaN-skipping sum over its cells in ascending order
+        (groupby('id').sum(), :250-265) on xh_diag_group_sum; ids first_id .. first_id + n_ids - 1, the others dropped;
+        an id without cells gives NaN (the left merge of the names)."""
         src, mine = self._on_device(arr)
         ncell, ncols = src.shape
-        idx = np.asarray(id_map).astype(np.int64) - first_id
+        idx = np.asarray(id_map).reshape(-1).astype(np.int64) - first_id
+        if idx.shape != (ncell,):
+            raise ValueError('the id map holds {} cells, the data {}'.format(idx.shape[0], ncell))
         idx[(idx < 0) | (idx >= n_ids)] = -1
-        dst = self.ctx.empty((n_ids, ncols))
-        self.ctx.agg_spatial(ncell, ncols, n_ids, idx, src, dst)
-        out = dst.download()
-        dst.free()
-        if mine:
-            src.free()
+        dst, d_counts = self.ctx.empty((n_ids, ncols)), self.ctx.empty((n_ids,), dtype=np.int64)
+        self.ctx.diag_group_sum(ncell, ncols, n_ids, idx, src, dst, d_counts)
+        out, counts = dst.download(), d_counts.download()
+        for b in (dst, d_counts, src if mine else None):
+            if b is not None:
+                b.free()
+        out[counts == 0] = np.nan
         return out
 
     # ---- the reference's write() (:81-125)
