@@ -20,7 +20,7 @@
 #include <cstdlib>
 
 #include "xh_abcd_dev.h"
-#include "xh_common.h"
+#include "xh_launch.h"
 #include "xh_stage.h"
 
 namespace {
@@ -450,35 +450,26 @@ int xh_abcd_enqueue_spinup(xh_ctx *ctx, hipStream_t st, const xh_abcd_setup &s, 
                            const double *d_pet, const double *d_precip, const double *d_tmin) {
     if (s.ncell == 0) return XH_OK;
     const int64_t ncell = s.ncell;
-    const unsigned blocks = (unsigned)((ncell + 63) / 64), blocks32 = (unsigned)((ncell + 31) / 32);
+    const unsigned blocks = xh_grid(ctx, ncell, 64), blocks32 = xh_grid(ctx, ncell, 32);
     const int mode = abcd_env() < 0 ? 0 : abcd_env();
-    {
-        xh_span sp = xh_span_begin_on(ctx, "abcd_spinup", st);
-        if (mode == 32)
-            hipLaunchKernelGGL((k_abcd_tile<true, 32>), dim3(blocks32), dim3(64), 0, st, ncell, s.nmonths, s.spinup, 0,
-                               s.spinup, (double *)nullptr, s.d_pidx, s.d_bidx, d_pars, d_pet, d_precip, d_tmin,
-                               (const double *)nullptr, (const double *)nullptr, s.d_dec, (double *)nullptr,
-                               (double *)nullptr, (double *)nullptr, (double *)nullptr);
-        else if (mode == 64)
-            hipLaunchKernelGGL((k_abcd_tile<true, 64>), dim3(blocks), dim3(64), 0, st, ncell, s.nmonths, s.spinup, 0,
-                               s.spinup, (double *)nullptr, s.d_pidx, s.d_bidx, d_pars, d_pet, d_precip, d_tmin,
-                               (const double *)nullptr, (const double *)nullptr, s.d_dec, (double *)nullptr,
-                               (double *)nullptr, (double *)nullptr, (double *)nullptr);
-        else
-            hipLaunchKernelGGL(k_abcd<true>, dim3(blocks), dim3(64), 0, st, ncell, s.nmonths, s.spinup, s.d_pidx,
-                               s.d_bidx, d_pars, d_pet, d_precip, d_tmin, (const double *)nullptr,
-                               (const double *)nullptr, s.d_dec, (double *)nullptr, (double *)nullptr,
-                               (double *)nullptr);
-        xh_span_end(sp);
-    }
-    {
-        xh_span sp = xh_span_begin_on(ctx, "abcd_basin_mean", st);
-        hipLaunchKernelGGL(k_abcd_basin_mean, dim3((unsigned)s.n_groups), dim3(256), 0, st, s.d_ptr, s.d_cells, ncell,
-                           s.d_dec, s.d_sm0, s.d_gw0);
-        xh_span_end(sp);
-    }
-    XH_HIP(ctx, hipGetLastError());
-    return XH_OK;
+    int rc;
+    if (mode == 32)
+        rc = xh_launch(ctx, "abcd_spinup", st, k_abcd_tile<true, 32>, blocks32, 64, 0, ncell, s.nmonths, s.spinup, 0,
+                       s.spinup, (double *)nullptr, s.d_pidx, s.d_bidx, d_pars, d_pet, d_precip, d_tmin,
+                       (const double *)nullptr, (const double *)nullptr, s.d_dec, (double *)nullptr, (double *)nullptr,
+                       (double *)nullptr, (double *)nullptr);
+    else if (mode == 64)
+        rc = xh_launch(ctx, "abcd_spinup", st, k_abcd_tile<true, 64>, blocks, 64, 0, ncell, s.nmonths, s.spinup, 0,
+                       s.spinup, (double *)nullptr, s.d_pidx, s.d_bidx, d_pars, d_pet, d_precip, d_tmin,
+                       (const double *)nullptr, (const double *)nullptr, s.d_dec, (double *)nullptr, (double *)nullptr,
+                       (double *)nullptr, (double *)nullptr);
+    else
+        rc = xh_launch(ctx, "abcd_spinup", st, k_abcd<true>, blocks, 64, 0, ncell, s.nmonths, s.spinup, s.d_pidx, s.d_bidx,
+                       d_pars, d_pet, d_precip, d_tmin, (const double *)nullptr, (const double *)nullptr, s.d_dec,
+                       (double *)nullptr, (double *)nullptr, (double *)nullptr);
+    if (rc) return rc;
+    return xh_launch(ctx, "abcd_basin_mean", st, k_abcd_basin_mean, s.n_groups, 256, 0, s.d_ptr, s.d_cells, ncell, s.d_dec,
+                     s.d_sm0, s.d_gw0);
 }
 
 int xh_abcd_enqueue_sim(xh_ctx *ctx, hipStream_t st, const xh_abcd_setup &s, int m_begin, int m_end,
@@ -487,7 +478,7 @@ int xh_abcd_enqueue_sim(xh_ctx *ctx, hipStream_t st, const xh_abcd_setup &s, int
     if (s.ncell == 0 || m_end <= m_begin) return XH_OK;
     XH_REQUIRE(ctx, m_begin >= 0 && m_end <= s.nmonths && m_begin % 2 == 0 && m_end % 2 == 0, "xh_abcd: bad month block");
     const int64_t ncell = s.ncell;
-    const unsigned blocks = (unsigned)((ncell + 63) / 64);
+    const unsigned blocks = xh_grid(ctx, ncell, 64);
     const bool whole = m_begin == 0 && m_end == s.nmonths;
     int mode = abcd_env() < 0 ? 32 : abcd_env();
     if (mode == 0 && (!whole || d_q_staged)) mode = 32;          // only the tiled kernel marches blocks of months / stages the runoff
@@ -505,30 +496,19 @@ int xh_abcd_enqueue_sim(xh_ctx *ctx, hipStream_t st, const xh_abcd_setup &s, int
                 break;
             }
     }
-    const unsigned blocks_cpw = (unsigned)((ncell + cpw - 1) / cpw);
+    const unsigned blocks_cpw = xh_grid(ctx, ncell, cpw);
     double *state = whole ? nullptr : s.d_state;
-    xh_span sp = xh_span_begin_on(ctx, "abcd_sim", st);
-#define XH_ABCD_TILE_SIM(CPWV)                                                                                                  \
-    hipLaunchKernelGGL((k_abcd_tile<false, CPWV>), dim3(blocks_cpw), dim3(64), 0, st, ncell, s.nmonths, s.nmonths, m_begin, m_end, \
-                       state, s.d_pidx, s.d_bidx, d_pars, d_pet, d_precip, d_tmin, s.d_sm0, s.d_gw0, (double *)nullptr, d_aet,  \
-                       d_q, d_sav, d_q_staged)
-    if (mode == 32 && cpw == 40)
-        XH_ABCD_TILE_SIM(40);
-    else if (mode == 32 && cpw == 48)
-        XH_ABCD_TILE_SIM(48);
-    else if (mode == 32)
-        XH_ABCD_TILE_SIM(32);
-#undef XH_ABCD_TILE_SIM
-    else if (mode == 64)
-        hipLaunchKernelGGL((k_abcd_tile<false, 64>), dim3(blocks), dim3(64), 0, st, ncell, s.nmonths, s.nmonths, m_begin,
-                           m_end, state, s.d_pidx, s.d_bidx, d_pars, d_pet, d_precip, d_tmin, s.d_sm0, s.d_gw0,
-                           (double *)nullptr, d_aet, d_q, d_sav, d_q_staged);
-    else
-        hipLaunchKernelGGL(k_abcd<false>, dim3(blocks), dim3(64), 0, st, ncell, s.nmonths, s.nmonths, s.d_pidx, s.d_bidx,
-                           d_pars, d_pet, d_precip, d_tmin, s.d_sm0, s.d_gw0, (double *)nullptr, d_aet, d_q, d_sav);
-    xh_span_end(sp);
-    XH_HIP(ctx, hipGetLastError());
-    return XH_OK;
+    auto tile = [&](auto k, unsigned grid) {      // the tiled kernels of every width take the same arguments
+        return xh_launch(ctx, "abcd_sim", st, k, grid, 64, 0, ncell, s.nmonths, s.nmonths, m_begin, m_end, state, s.d_pidx,
+                         s.d_bidx, d_pars, d_pet, d_precip, d_tmin, s.d_sm0, s.d_gw0, (double *)nullptr, d_aet, d_q, d_sav,
+                         d_q_staged);
+    };
+    if (mode == 32 && cpw == 40) return tile(k_abcd_tile<false, 40>, blocks_cpw);
+    if (mode == 32 && cpw == 48) return tile(k_abcd_tile<false, 48>, blocks_cpw);
+    if (mode == 32) return tile(k_abcd_tile<false, 32>, blocks_cpw);
+    if (mode == 64) return tile(k_abcd_tile<false, 64>, blocks);
+    return xh_launch(ctx, "abcd_sim", st, k_abcd<false>, blocks, 64, 0, ncell, s.nmonths, s.nmonths, s.d_pidx, s.d_bidx, d_pars,
+                     d_pet, d_precip, d_tmin, s.d_sm0, s.d_gw0, (double *)nullptr, d_aet, d_q, d_sav);
 }
 
 extern "C" int xh_abcd(xh_ctx *ctx, int64_t ncell, int32_t nmonths, int32_t spinup, int32_t n_groups,

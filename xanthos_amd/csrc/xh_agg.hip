@@ -18,7 +18,7 @@
 #include <cmath>
 #include <vector>
 
-#include "xh_common.h"
+#include "xh_launch.h"
 #include "xh_kahan.h"
 
 #pragma clang fp contract(off)
@@ -104,12 +104,7 @@ extern "C" int xh_nan_to_num(xh_ctx *ctx, double *d_arr, int64_t n) {
     if (!ctx) return XH_ERR_ARG;
     XH_REQUIRE(ctx, n >= 0 && (d_arr || n == 0), "xh_nan_to_num: bad argument");
     if (n == 0) return XH_OK;
-    int64_t blocks = (n + 255) / 256;
-    const int64_t cap = (int64_t)ctx->prop.multiProcessorCount * 16;
-    if (blocks > cap) blocks = cap;
-    hipLaunchKernelGGL(k_nan_to_num, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, d_arr, n);
-    XH_HIP(ctx, hipGetLastError());
-    return XH_OK;
+    return xh_launch(ctx, nullptr, ctx->stream, k_nan_to_num, xh_grid(ctx, n, 256, 16), 256, 0, d_arr, n);
 }
 
 extern "C" int xh_agg_time(xh_ctx *ctx, int64_t ncell, int32_t ncols, int32_t group, int32_t mode, const double *d_scale,
@@ -121,15 +116,8 @@ extern "C" int xh_agg_time(xh_ctx *ctx, int64_t ncell, int32_t ncols, int32_t gr
     XH_REQUIRE(ctx, mode != 2 || group <= 128, "xh_agg_time: numpy-order sums are implemented for blocks of <= 128 values");
     if (ncell == 0) return XH_OK;
     const int64_t total = ncell * (int64_t)(ncols / group);
-    int64_t blocks = (total + 255) / 256;
-    const int64_t cap = (int64_t)ctx->prop.multiProcessorCount * 16;
-    if (blocks > cap) blocks = cap;
-    xh_span sp = xh_span_begin(ctx, "agg_time");
-    hipLaunchKernelGGL(k_agg_time, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, ncell, (int)ncols, (int)group, (int)mode,
-                       d_scale, d_in, d_out);
-    xh_span_end(sp);
-    XH_HIP(ctx, hipGetLastError());
-    return XH_OK;
+    return xh_launch(ctx, "agg_time", ctx->stream, k_agg_time, xh_grid(ctx, total, 256, 16), 256, 0, ncell, (int)ncols,
+                     (int)group, (int)mode, d_scale, d_in, d_out);
 }
 
 extern "C" int xh_agg_spatial(xh_ctx *ctx, int64_t ncell, int32_t ncols, int32_t n_groups, const int32_t *h_group,
@@ -150,19 +138,10 @@ extern "C" int xh_agg_spatial(xh_ctx *ctx, int64_t ncell, int32_t ncols, int32_t
         for (int64_t c = 0; c < ncell; ++c)
             if (h_group[c] >= 0) cells[fill[h_group[c]]++] = (int)c;
     }
-    void *buf = nullptr;
-    const size_t bytes = (ptr.size() + cells.size()) * sizeof(int) + 64;
-    int rc = xh_scratch(ctx, 2, bytes, &buf);
+    void *at[3];
+    const int rc =
+        xh_stage(ctx, 2, {{ptr.data(), ptr.size() * sizeof(int)}, {cells.data(), cells.size() * sizeof(int)}}, 0, at);
     if (rc) return rc;
-    int *d_ptr = static_cast<int *>(buf), *d_cells = d_ptr + ptr.size();
-    XH_HIP(ctx, hipMemcpyAsync(d_ptr, ptr.data(), ptr.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-    if (!cells.empty())
-        XH_HIP(ctx, hipMemcpyAsync(d_cells, cells.data(), cells.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-    XH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    xh_span sp = xh_span_begin(ctx, "agg_spatial");
-    hipLaunchKernelGGL(k_agg_spatial, dim3((unsigned)n_groups, (unsigned)((ncols + 255) / 256)), dim3(256), 0, ctx->stream,
-                       (int)ncols, d_ptr, d_cells, d_in, d_out);
-    xh_span_end(sp);
-    XH_HIP(ctx, hipGetLastError());
-    return XH_OK;
+    return xh_launch(ctx, "agg_spatial", ctx->stream, k_agg_spatial, dim3((unsigned)n_groups, xh_grid(ctx, ncols, 256)), 256, 0,
+                     (int)ncols, static_cast<const int *>(at[0]), static_cast<const int *>(at[1]), d_in, d_out);
 }

@@ -20,7 +20,7 @@
 
 #include "xh_abcd_dev.h"
 #include "xh_calib.h"
-#include "xh_common.h"
+#include "xh_launch.h"
 
 namespace {
 
@@ -569,42 +569,41 @@ static int calib_enqueue_m(xh_ctx *ctx, const xh_calib_problem &P, const double 
                            double *d_ed) {
     const size_t nbm = (size_t)P.nbasins * P.nmembers;
     const dim3 grid((unsigned)P.nchunks, (unsigned)((P.nmembers + 63) / 64)), block(64);
-    {
-        xh_span sp = xh_span_begin(ctx, "calib_abcd");
+    hipStream_t st = ctx->stream;
+    const int rc = xh_timed(ctx, "calib_abcd", st, [&] {
         if (!P.split_done) {
-            hipLaunchKernelGGL(k_calib_split, dim3(256, (unsigned)P.nbasins), dim3(256), 0, ctx->stream, P.d_basins, P.nmonths);
+            const int rc = xh_launch(ctx, nullptr, st, k_calib_split, dim3(256, (unsigned)P.nbasins), 256, 0, P.d_basins,
+                                     P.nmonths);
+            if (rc) return rc;
             P.split_done = true;
         }
-        hipLaunchKernelGGL(k_calib_march_m<true>, grid, block, 0, ctx->stream, P.d_basins, P.d_chunk_basin, d_active,
-                           P.spinup, P.nmembers, P.npar, d_pars, (const double *)nullptr, (const double *)nullptr,
-                           P.d_dec, P.d_cnt, (double *)nullptr);
-        hipLaunchKernelGGL(k_calib_init_m, dim3((unsigned)((nbm + 63) / 64)), dim3(64), 0, ctx->stream, P.d_basins,
-                           d_active, P.nbasins, P.nmembers, P.d_dec, P.d_cnt, P.d_sm0, P.d_gw0);
-        hipLaunchKernelGGL(k_calib_march_m<false>, grid, block, 0, ctx->stream, P.d_basins, P.d_chunk_basin, d_active,
+        int rc = xh_launch(ctx, nullptr, st, k_calib_march_m<true>, grid, block, 0, P.d_basins, P.d_chunk_basin, d_active,
+                           P.spinup, P.nmembers, P.npar, d_pars, (const double *)nullptr, (const double *)nullptr, P.d_dec,
+                           P.d_cnt, (double *)nullptr);
+        if (!rc)
+            rc = xh_launch(ctx, nullptr, st, k_calib_init_m, xh_grid(ctx, nbm, 64), 64, 0, P.d_basins, d_active, P.nbasins,
+                           P.nmembers, P.d_dec, P.d_cnt, P.d_sm0, P.d_gw0);
+        if (!rc)
+            rc = xh_launch(ctx, nullptr, st, k_calib_march_m<false>, grid, block, 0, P.d_basins, P.d_chunk_basin, d_active,
                            P.nmonths, P.nmembers, P.npar, d_pars, P.d_sm0, P.d_gw0, (double *)nullptr, (int *)nullptr,
                            P.d_part);
-        xh_span_end(sp);
-    }
-    {
-        xh_span sp = xh_span_begin(ctx, "calib_kge");
-        const int64_t n = (int64_t)nbm * P.nmonths;
-        hipLaunchKernelGGL(k_calib_series_m, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, P.d_basins,
-                           d_active, P.nbasins, P.nmembers, P.nmonths, P.d_part, P.d_series_m);
-        hipLaunchKernelGGL(k_calib_kge_m, dim3((unsigned)((P.nmembers + 63) / 64), (unsigned)P.nbasins), dim3(64), 0,
-                           ctx->stream, d_active, P.nbasins, P.nmonths, P.nmembers, P.d_series_m, P.d_obs, d_ed);
-        xh_span_end(sp);
-    }
-    XH_HIP(ctx, hipGetLastError());
-    return XH_OK;
+        return rc;
+    });
+    if (rc) return rc;
+    return xh_timed(ctx, "calib_kge", st, [&] {
+        const int rc = xh_launch(ctx, nullptr, st, k_calib_series_m, xh_grid(ctx, (int64_t)nbm * P.nmonths, 256), 256, 0,
+                                 P.d_basins, d_active, P.nbasins, P.nmembers, P.nmonths, P.d_part, P.d_series_m);
+        if (rc) return rc;
+        return xh_launch(ctx, nullptr, st, k_calib_kge_m, dim3(xh_grid(ctx, P.nmembers, 64), (unsigned)P.nbasins), 64, 0,
+                         d_active, P.nbasins, P.nmonths, P.nmembers, P.d_series_m, P.d_obs, d_ed);
+    });
 }
 
 int xh_calib_series_out(xh_ctx *ctx, const xh_calib_problem &P) {
     if (!P.member_lanes) return XH_OK;
     const int64_t n = (int64_t)P.nbasins * P.nmembers * P.nmonths;
-    hipLaunchKernelGGL(k_calib_series_out, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, P.nbasins,
-                       P.nmembers, P.nmonths, P.d_series_m, P.d_series);
-    XH_HIP(ctx, hipGetLastError());
-    return XH_OK;
+    return xh_launch(ctx, nullptr, ctx->stream, k_calib_series_out, xh_grid(ctx, n, 256), 256, 0, P.nbasins, P.nmembers,
+                     P.nmonths, P.d_series_m, P.d_series);
 }
 
 int xh_calib_enqueue(xh_ctx *ctx, const xh_calib_problem &P, const double *d_pars, const int *d_active, double *d_ed) {
@@ -612,29 +611,28 @@ int xh_calib_enqueue(xh_ctx *ctx, const xh_calib_problem &P, const double *d_par
     const int nmblocks = (P.nmembers + MB - 1) / MB;
     const size_t nbm = (size_t)P.nbasins * P.nmembers;
     const dim3 grid((unsigned)P.nchunks, (unsigned)nmblocks), block(64);
-    {
-        xh_span sp = xh_span_begin(ctx, "calib_abcd");
-        hipLaunchKernelGGL(k_calib_march<true>, grid, block, 0, ctx->stream, P.d_basins, P.d_chunk_basin, d_active,
-                           P.spinup, P.nmembers, P.npar, d_pars, (const double *)nullptr, (const double *)nullptr,
-                           P.d_dec, P.d_cnt, (double *)nullptr);
-        hipLaunchKernelGGL(k_calib_init, dim3((unsigned)((nbm + 63) / 64)), dim3(64), 0, ctx->stream, P.d_basins,
-                           d_active, P.nbasins, P.nmembers, P.d_dec, P.d_cnt, P.d_sm0, P.d_gw0);
-        hipLaunchKernelGGL(k_calib_march<false>, grid, block, 0, ctx->stream, P.d_basins, P.d_chunk_basin, d_active,
+    hipStream_t st = ctx->stream;
+    const int rc = xh_timed(ctx, "calib_abcd", st, [&] {
+        int rc = xh_launch(ctx, nullptr, st, k_calib_march<true>, grid, block, 0, P.d_basins, P.d_chunk_basin, d_active,
+                           P.spinup, P.nmembers, P.npar, d_pars, (const double *)nullptr, (const double *)nullptr, P.d_dec,
+                           P.d_cnt, (double *)nullptr);
+        if (!rc)
+            rc = xh_launch(ctx, nullptr, st, k_calib_init, xh_grid(ctx, nbm, 64), 64, 0, P.d_basins, d_active, P.nbasins,
+                           P.nmembers, P.d_dec, P.d_cnt, P.d_sm0, P.d_gw0);
+        if (!rc)
+            rc = xh_launch(ctx, nullptr, st, k_calib_march<false>, grid, block, 0, P.d_basins, P.d_chunk_basin, d_active,
                            P.nmonths, P.nmembers, P.npar, d_pars, P.d_sm0, P.d_gw0, (double *)nullptr, (int *)nullptr,
                            P.d_part);
-        xh_span_end(sp);
-    }
-    {
-        xh_span sp = xh_span_begin(ctx, "calib_kge");
-        const int64_t n = (int64_t)nbm * P.nmonths;
-        hipLaunchKernelGGL(k_calib_series, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, P.d_basins,
-                           d_active, P.nbasins, P.nmembers, P.nmonths, P.d_part, P.d_series);
-        hipLaunchKernelGGL(k_calib_kge, dim3((unsigned)nbm), dim3(256), 0, ctx->stream, d_active, P.nmonths,
-                           P.nmembers, P.d_series, P.d_obs, d_ed);
-        xh_span_end(sp);
-    }
-    XH_HIP(ctx, hipGetLastError());
-    return XH_OK;
+        return rc;
+    });
+    if (rc) return rc;
+    return xh_timed(ctx, "calib_kge", st, [&] {
+        const int rc = xh_launch(ctx, nullptr, st, k_calib_series, xh_grid(ctx, (int64_t)nbm * P.nmonths, 256), 256, 0,
+                                 P.d_basins, d_active, P.nbasins, P.nmembers, P.nmonths, P.d_part, P.d_series);
+        if (rc) return rc;
+        return xh_launch(ctx, nullptr, st, k_calib_kge, dim3((unsigned)nbm), 256, 0, d_active, P.nmonths, P.nmembers,
+                         P.d_series, P.d_obs, d_ed);
+    });
 }
 
 extern "C" int xh_calib_objective_multi(xh_ctx *ctx, int32_t nbasins, const int64_t *h_ncell, int32_t nmonths,

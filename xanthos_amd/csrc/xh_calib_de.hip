@@ -24,6 +24,7 @@
 #include <cmath>
 
 #include "xh_calib.h"
+#include "xh_launch.h"
 
 struct xh_calib_de {
     xh_ctx *ctx = nullptr;
@@ -345,22 +346,13 @@ int xh_calib_de_init(xh_calib_de *de) {
     XH_HIP(ctx, hipMemsetAsync(de->d_nit, 0, 4 * (size_t)de->nb, ctx->stream));
     XH_HIP(ctx, hipMemsetAsync(de->d_n_active, 0, 4, ctx->stream));
     de->generation = 0;
-    {
-        xh_span sp = xh_span_begin(ctx, "calib_de");
-        hipLaunchKernelGGL(k_de_init, dim3(de->nb), dim3(256), sizeof(double) * de->n, ctx->stream, de->n, de->d,
-                           de->seed, de->d_key, de->d_lo, de->d_hi, de->d_pop, de->d_x);
-        xh_span_end(sp);
-    }
-    rc = xh_calib_enqueue(ctx, de->P, de->d_x, de->d_active, de->d_e_trial);
+    rc = xh_launch(ctx, "calib_de", ctx->stream, k_de_init, de->nb, 256, sizeof(double) * de->n, de->n, de->d, de->seed,
+                   de->d_key, de->d_lo, de->d_hi, de->d_pop, de->d_x);
+    if (!rc) rc = xh_calib_enqueue(ctx, de->P, de->d_x, de->d_active, de->d_e_trial);
+    if (!rc)
+        rc = xh_launch(ctx, "calib_de", ctx->stream, k_de_select, de->nb, 256, 0, de->n, de->d, 1, 0.0, 0.0, de->d_active,
+                       de->d_pop, de->d_trial, de->d_energy, de->d_e_trial, de->d_nit, de->d_nfev, de->d_n_active);
     if (rc) return rc;
-    {
-        xh_span sp = xh_span_begin(ctx, "calib_de");
-        hipLaunchKernelGGL(k_de_select, dim3(de->nb), dim3(256), 0, ctx->stream, de->n, de->d, 1, 0.0, 0.0,
-                           de->d_active, de->d_pop, de->d_trial, de->d_energy, de->d_e_trial, de->d_nit, de->d_nfev,
-                           de->d_n_active);
-        xh_span_end(sp);
-    }
-    XH_HIP(ctx, hipGetLastError());
     XH_HIP(ctx, hipMemcpyAsync(de->h_n_active, de->d_n_active, 4, hipMemcpyDeviceToHost, ctx->stream));
     XH_HIP(ctx, hipStreamSynchronize(ctx->stream));
     de->initialised = true;
@@ -392,21 +384,16 @@ int xh_calib_de_step(xh_calib_de *de, int32_t ngen, double tol, double atol, dou
                "xh_calib_de_step: bad argument");
     for (int g = 0; g < ngen; ++g) {
         const int gen = de->generation++;
-        xh_span sp = xh_span_begin(ctx, "calib_de");
-        hipLaunchKernelGGL(k_de_trial, dim3(de->nb), dim3(256), 0, ctx->stream, de->n, de->d, de->seed, gen, mut_lo,
+        int rc = xh_launch(ctx, "calib_de", ctx->stream, k_de_trial, de->nb, 256, 0, de->n, de->d, de->seed, gen, mut_lo,
                            mut_hi, recombination, de->d_key, de->d_active, de->d_lo, de->d_hi, de->d_pop, de->d_energy,
                            de->d_trial, de->d_x);
-        xh_span_end(sp);
-        int rc = xh_calib_enqueue(ctx, de->P, de->d_x, de->d_active, de->d_e_trial);
+        if (!rc) rc = xh_calib_enqueue(ctx, de->P, de->d_x, de->d_active, de->d_e_trial);
         if (rc) return rc;
         XH_HIP(ctx, hipMemsetAsync(de->d_n_active, 0, 4, ctx->stream));
-        xh_span sp2 = xh_span_begin(ctx, "calib_de");
-        hipLaunchKernelGGL(k_de_select, dim3(de->nb), dim3(256), 0, ctx->stream, de->n, de->d, 0, tol, atol,
-                           de->d_active, de->d_pop, de->d_trial, de->d_energy, de->d_e_trial, de->d_nit, de->d_nfev,
-                           de->d_n_active);
-        xh_span_end(sp2);
+        rc = xh_launch(ctx, "calib_de", ctx->stream, k_de_select, de->nb, 256, 0, de->n, de->d, 0, tol, atol, de->d_active,
+                       de->d_pop, de->d_trial, de->d_energy, de->d_e_trial, de->d_nit, de->d_nfev, de->d_n_active);
+        if (rc) return rc;
     }
-    XH_HIP(ctx, hipGetLastError());
     if (ngen > 0) XH_HIP(ctx, hipMemcpyAsync(de->h_n_active, de->d_n_active, 4, hipMemcpyDeviceToHost, ctx->stream));
     XH_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (h_n_active) *h_n_active = *de->h_n_active;
@@ -423,9 +410,9 @@ int xh_calib_de_result(xh_calib_de *de, double *h_x, double *h_fun, int64_t *h_n
     int rc = xh_scratch(ctx, 2, 8 * nb * (de->d + 1), &buf);
     if (rc) return rc;
     double *d_x = static_cast<double *>(buf), *d_fun = d_x + nb * de->d;
-    hipLaunchKernelGGL(k_de_best, dim3(de->nb), dim3(256), 0, ctx->stream, de->n, de->d, de->d_lo, de->d_hi, de->d_pop,
-                       de->d_energy, d_x, d_fun);
-    XH_HIP(ctx, hipGetLastError());
+    rc = xh_launch(ctx, nullptr, ctx->stream, k_de_best, de->nb, 256, 0, de->n, de->d, de->d_lo, de->d_hi, de->d_pop,
+                   de->d_energy, d_x, d_fun);
+    if (rc) return rc;
     if (h_x) XH_HIP(ctx, hipMemcpyAsync(h_x, d_x, 8 * nb * de->d, hipMemcpyDeviceToHost, ctx->stream));
     if (h_fun) XH_HIP(ctx, hipMemcpyAsync(h_fun, d_fun, 8 * nb, hipMemcpyDeviceToHost, ctx->stream));
     if (h_nfev) XH_HIP(ctx, hipMemcpyAsync(h_nfev, de->d_nfev, 8 * nb, hipMemcpyDeviceToHost, ctx->stream));

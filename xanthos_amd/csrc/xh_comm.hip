@@ -21,7 +21,7 @@
 #include <mutex>
 #include <rccl/rccl.h>
 
-#include "xh_common.h"
+#include "xh_launch.h"
 
 namespace {
 
@@ -211,7 +211,7 @@ static int gather_rows_on(xh_ctx *ctx, hipStream_t st, xh_comm *c, int32_t root,
     const int64_t n_local = h_counts[c->rank];
     XH_REQUIRE(ctx, n_local >= 0, "xh_comm_gather_rows: negative count");
     for (int v = 0; v < nvar; ++v) XH_REQUIRE(ctx, h_d_local[v] || n_local == 0, "xh_comm_gather_rows: NULL local array");
-    ctx->work_seq += 1;      // reads outputs a routing call may still have to recompute (xh_fault_check)
+    xh_note_work(ctx, st);      // reads outputs a routing call may still have to recompute (xh_fault_check)
     // Inside a group the first failure is remembered and the group is still closed: returning between GroupStart and
     // GroupEnd would leave the group open on this thread and break every later RCCL call.
     ncclResult_t first = ncclSuccess;

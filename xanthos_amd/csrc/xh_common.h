@@ -72,7 +72,7 @@ struct xh_ctx {
     unsigned *h_fault = nullptr;
     bool fault_pending = false;
     std::vector<xh_route_record> pending_routes;
-    uint64_t work_seq = 0;         // bumped by every entry point that enqueues work on the stream (kernels, copies, row movers)
+    uint64_t work_seq = 0;         // counts enqueued work (kernels, copies, row movers); written by xh_note_work only (xh_launch.h)
     int64_t reroutes = 0;          // routing calls re-run after a device fault
     // xh_run_fused: side stream [0] (lowest priority: the fillers beside the routing kernel) and events of the pipelines;
     // side stream [1] (highest priority: a queue of its own): the write-out gather of PET / AET / Q / Sav beside the routing

@@ -5,7 +5,7 @@
 #include <cstdlib>
 #include <mutex>
 
-#include "xh_common.h"
+#include "xh_launch.h"
 
 std::string g_xh_create_error;
 
@@ -204,16 +204,42 @@ Roctx &roctx() {
 }
 }  // namespace
 
+void xh_note_work(xh_ctx *ctx, hipStream_t stream) {
+    ctx->work_seq += 1;
+    // new work on the context's stream: the "runoff is final" event a fed call left for a side gather is no longer the
+    // thing to wait for (xh_comm_gather_rows_side then orders itself behind the context's stream)
+    if (stream == ctx->stream) ctx->runoff_event_fresh = false;
+}
+
+int xh_stage(xh_ctx *ctx, int slot, std::initializer_list<xh_host_array> arrays, size_t tail_bytes, void **at) {
+    size_t bytes = 0;
+    for (const xh_host_array &a : arrays)
+        if (!a.dst) bytes += (a.bytes + 255) & ~size_t(255);
+    void *buf = nullptr;
+    int rc = xh_scratch(ctx, slot, bytes + tail_bytes, &buf);
+    if (rc) return rc;
+    char *next = static_cast<char *>(buf);
+    for (const xh_host_array &a : arrays) {
+        void *d = a.dst;
+        if (!d) {
+            d = next;
+            next += (a.bytes + 255) & ~size_t(255);
+        }
+        if (a.bytes) XH_HIP(ctx, hipMemcpyAsync(d, a.src, a.bytes, hipMemcpyHostToDevice, ctx->stream));
+        *at++ = d;
+    }
+    *at = next;
+    XH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return XH_OK;
+}
+
 xh_span xh_span_begin(xh_ctx *ctx, const char *name) { return xh_span_begin_on(ctx, name, ctx->stream); }
 
 xh_span xh_span_begin_on(xh_ctx *ctx, const char *name, hipStream_t stream) {
     xh_span s{ctx, name};
     s.stream = stream;
     if (roctx().on) (void)roctx().push(name);
-    ctx->work_seq += 1;
-    // new work on the context's stream: the "runoff is final" event a fed call left for a side gather is no longer the
-    // thing to wait for (xh_comm_gather_rows_side then orders itself behind the context's stream)
-    if (stream == ctx->stream) ctx->runoff_event_fresh = false;
+    xh_note_work(ctx, stream);
     if (!ctx->timing) return s;
     auto take = [&](hipEvent_t &e) {
         if (!ctx->event_pool.empty()) {
@@ -341,7 +367,7 @@ int xh_memcpy_h2d(xh_ctx *ctx, void *d_dst, const void *h_src, size_t bytes) {
     if (!ctx || (bytes && (!d_dst || !h_src))) return XH_ERR_ARG;
     int rc = XH_OK;
     if (ctx->fault_pending) rc = xh_settle(ctx);      // the copy may overwrite the inputs of a call that must be re-routed
-    ctx->work_seq += 1;
+    xh_note_work(ctx, ctx->stream);
     XH_HIP(ctx, hipMemcpyAsync(d_dst, h_src, bytes, hipMemcpyHostToDevice, ctx->stream));
     XH_HIP(ctx, hipStreamSynchronize(ctx->stream));   // the host buffer may be reused on return
     return rc;
@@ -373,28 +399,28 @@ int xh_host_free(xh_ctx *ctx, void *h_ptr) {
 
 int xh_memcpy_h2d_async(xh_ctx *ctx, void *d_dst, const void *h_src, size_t bytes) {
     if (!ctx || (bytes && (!d_dst || !h_src))) return XH_ERR_ARG;
-    ctx->work_seq += 1;      // work that may read the outputs of a routing call still to be confirmed (xh_fault_check)
+    xh_note_work(ctx, ctx->stream);      // may read the outputs of a routing call still to be confirmed (xh_fault_check)
     XH_HIP(ctx, hipMemcpyAsync(d_dst, h_src, bytes, hipMemcpyHostToDevice, ctx->stream));
     return XH_OK;
 }
 
 int xh_memcpy_d2h_async(xh_ctx *ctx, void *h_dst, const void *d_src, size_t bytes) {
     if (!ctx || (bytes && (!h_dst || !d_src))) return XH_ERR_ARG;
-    ctx->work_seq += 1;      // work that may read the outputs of a routing call still to be confirmed (xh_fault_check)
+    xh_note_work(ctx, ctx->stream);      // may read the outputs of a routing call still to be confirmed (xh_fault_check)
     XH_HIP(ctx, hipMemcpyAsync(h_dst, d_src, bytes, hipMemcpyDeviceToHost, ctx->stream));
     return XH_OK;
 }
 
 int xh_memcpy_d2d(xh_ctx *ctx, void *d_dst, const void *d_src, size_t bytes) {
     if (!ctx || (bytes && (!d_dst || !d_src))) return XH_ERR_ARG;
-    ctx->work_seq += 1;      // work that may read the outputs of a routing call still to be confirmed (xh_fault_check)
+    xh_note_work(ctx, ctx->stream);      // may read the outputs of a routing call still to be confirmed (xh_fault_check)
     XH_HIP(ctx, hipMemcpyAsync(d_dst, d_src, bytes, hipMemcpyDeviceToDevice, ctx->stream));
     return XH_OK;
 }
 
 int xh_memset(xh_ctx *ctx, void *d_ptr, int value, size_t bytes) {
     if (!ctx || (bytes && !d_ptr)) return XH_ERR_ARG;
-    ctx->work_seq += 1;
+    xh_note_work(ctx, ctx->stream);
     XH_HIP(ctx, hipMemsetAsync(d_ptr, value, bytes, ctx->stream));
     return XH_OK;
 }
@@ -494,11 +520,8 @@ int xh_move_rows_on(xh_ctx *ctx, hipStream_t st, const double *d_src, const int6
     if (!ctx) return XH_ERR_ARG;
     XH_REQUIRE(ctx, d_src && d_rows && d_dst && nrows >= 0 && ncols >= 0, "xh_gather/scatter_rows: bad argument");
     if (nrows == 0 || ncols == 0) return XH_OK;
-    ctx->work_seq += 1;
-    int grid = (int)(nrows < 65536 ? nrows : 65536);
-    hipLaunchKernelGGL(k_gather_rows, dim3(grid), dim3(256), 0, st, d_src, d_rows, nrows, ncols, d_dst, scatter);
-    XH_HIP(ctx, hipGetLastError());
-    return XH_OK;
+    const int grid = (int)(nrows < 65536 ? nrows : 65536);
+    return xh_launch(ctx, nullptr, st, k_gather_rows, grid, 256, 0, d_src, d_rows, nrows, ncols, d_dst, scatter);
 }
 
 extern "C" {
@@ -548,12 +571,9 @@ int xh_transpose(xh_ctx *ctx, const double *d_src, int64_t rows, int64_t cols, d
     if (!ctx) return XH_ERR_ARG;
     XH_REQUIRE(ctx, d_src && d_dst && rows >= 0 && cols >= 0, "xh_transpose: bad argument");
     if (rows == 0 || cols == 0) return XH_OK;
-    ctx->work_seq += 1;
-    dim3 grid((unsigned)((cols + 31) / 32), (unsigned)((rows + 31) / 32));
+    const dim3 grid((unsigned)((cols + 31) / 32), (unsigned)((rows + 31) / 32));
     XH_REQUIRE(ctx, grid.y <= 65535u, "xh_transpose: too many rows");
-    hipLaunchKernelGGL(k_transpose, grid, dim3(256), 0, ctx->stream, d_src, rows, cols, d_dst);
-    XH_HIP(ctx, hipGetLastError());
-    return XH_OK;
+    return xh_launch(ctx, nullptr, ctx->stream, k_transpose, grid, 256, 0, d_src, rows, cols, d_dst);
 }
 
 }  // extern "C"

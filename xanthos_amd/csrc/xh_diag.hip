@@ -20,7 +20,7 @@
 #include <cstdint>
 #include <vector>
 
-#include "xh_common.h"
+#include "xh_launch.h"
 #include "xh_kahan.h"
 
 #pragma clang fp contract(off)
@@ -165,29 +165,14 @@ extern "C" int xh_diag_cell_total(xh_ctx *ctx, int64_t ncell, int32_t ncols, con
     XH_REQUIRE(ctx, work <= STAGE_MAX_BYTES, "xh_diag_cell_total: %d values per cell need %d leaves, more than the LDS holds",
                ncols, nleaves);
     const bool stage = work + (size_t)ncols * sizeof(double) <= STAGE_MAX_BYTES;
-    void *buf = nullptr;
-    int rc = xh_scratch(ctx, 2, (leaves.size() + prog.size()) * sizeof(int) + 64, &buf);
+    void *at[3];
+    const int rc = xh_stage(ctx, 2, {{leaves.data(), leaves.size() * sizeof(int)}, {prog.data(), prog.size() * sizeof(int)}},
+                            0, at);
     if (rc) return rc;
-    int *d_leaves = static_cast<int *>(buf), *d_prog = d_leaves + leaves.size();
-    XH_HIP(ctx, hipMemcpyAsync(d_leaves, leaves.data(), leaves.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-    XH_HIP(ctx, hipMemcpyAsync(d_prog, prog.data(), prog.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-    XH_HIP(ctx, hipStreamSynchronize(ctx->stream));                 // the host vectors go out of scope on return
-    int64_t blocks = ncell;
-    const int64_t cap = (int64_t)ctx->prop.multiProcessorCount * 32;
-    if (blocks > cap) blocks = cap;
     const size_t lds = work + (stage ? (size_t)ncols * sizeof(double) : 0);
-    xh_span sp = xh_span_begin(ctx, "diag_cell_total");
-    if (stage)
-        hipLaunchKernelGGL(k_diag_cell_total<true>, dim3((unsigned)blocks), dim3(TOTAL_THREADS), lds, ctx->stream, ncell,
-                           (int)ncols, nleaves, d_leaves, (int)prog.size(), d_prog, d_in, div1, d_scale, div2, d_out,
-                           out_stride);
-    else
-        hipLaunchKernelGGL(k_diag_cell_total<false>, dim3((unsigned)blocks), dim3(TOTAL_THREADS), lds, ctx->stream, ncell,
-                           (int)ncols, nleaves, d_leaves, (int)prog.size(), d_prog, d_in, div1, d_scale, div2, d_out,
-                           out_stride);
-    xh_span_end(sp);
-    XH_HIP(ctx, hipGetLastError());
-    return XH_OK;
+    return xh_launch(ctx, "diag_cell_total", ctx->stream, stage ? k_diag_cell_total<true> : k_diag_cell_total<false>,
+                     xh_grid(ctx, ncell, 1, 32), TOTAL_THREADS, lds, ncell, (int)ncols, nleaves, static_cast<const int *>(at[0]),
+                     (int)prog.size(), static_cast<const int *>(at[1]), d_in, div1, d_scale, div2, d_out, out_stride);
 }
 
 extern "C" int xh_diag_group_sum(xh_ctx *ctx, int64_t ncell, int32_t k, int32_t ngroups, const int32_t *h_group,
@@ -213,21 +198,13 @@ extern "C" int xh_diag_group_sum(xh_ctx *ctx, int64_t ncell, int32_t k, int32_t 
         for (int64_t c = 0; c < ncell; ++c)
             if (h_group[c] >= 0) cells[fill[h_group[c]]++] = (int)c;
     }
-    void *buf = nullptr;
-    const size_t bytes = (ptr.size() + cells.size()) * sizeof(int) + 64;
-    int rc = xh_scratch(ctx, 2, bytes, &buf);
+    void *at[4];
+    const int rc = xh_stage(ctx, 2,
+                            {{ptr.data(), ptr.size() * sizeof(int)},
+                             {cells.data(), cells.size() * sizeof(int)},
+                             {counts.data(), counts.size() * sizeof(int64_t), d_counts}},
+                            0, at);
     if (rc) return rc;
-    int *d_ptr = static_cast<int *>(buf), *d_cells = d_ptr + ptr.size();
-    XH_HIP(ctx, hipMemcpyAsync(d_ptr, ptr.data(), ptr.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-    if (!cells.empty())
-        XH_HIP(ctx, hipMemcpyAsync(d_cells, cells.data(), cells.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-    XH_HIP(ctx, hipMemcpyAsync(d_counts, counts.data(), counts.size() * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
-    XH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    const int64_t n = (int64_t)ngroups * k;
-    xh_span sp = xh_span_begin(ctx, "diag_group_sum");
-    hipLaunchKernelGGL(k_diag_group_sum, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (int)ngroups, (int)k,
-                       d_ptr, d_cells, d_vals, d_sums);
-    xh_span_end(sp);
-    XH_HIP(ctx, hipGetLastError());
-    return XH_OK;
+    return xh_launch(ctx, "diag_group_sum", ctx->stream, k_diag_group_sum, xh_grid(ctx, (int64_t)ngroups * k, 256), 256, 0,
+                     (int)ngroups, (int)k, static_cast<const int *>(at[0]), static_cast<const int *>(at[1]), d_vals, d_sums);
 }

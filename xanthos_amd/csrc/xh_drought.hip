@@ -17,7 +17,7 @@
 // out per cell-month) with the same row-walking access pattern as the ABCD kernel.
 #include <cmath>
 
-#include "xh_common.h"
+#include "xh_launch.h"
 
 namespace {
 
@@ -96,16 +96,8 @@ extern "C" int xh_drought_thresholds(xh_ctx *ctx, int64_t ncell, int32_t nmonths
                "xh_drought_thresholds: order statistics %d, %d / weight %g invalid for %d samples", k_prev, k_next, gamma,
                nyear);
     if (ncell == 0) return XH_OK;
-    const int64_t total = ncell * (int64_t)nper;
-    int64_t blocks = (total + 255) / 256;
-    const int64_t cap = (int64_t)ctx->prop.multiProcessorCount * 32;
-    if (blocks > cap) blocks = cap;
-    xh_span sp = xh_span_begin(ctx, "drought_thresh");
-    hipLaunchKernelGGL(k_drought_thresh, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, ncell, (int)nmonths, (int)month0,
-                       (int)nyear, (int)nper, (int)k_prev, (int)k_next, gamma, d_hydro, d_thresh);
-    xh_span_end(sp);
-    XH_HIP(ctx, hipGetLastError());
-    return XH_OK;
+    return xh_launch(ctx, "drought_thresh", ctx->stream, k_drought_thresh, xh_grid(ctx, ncell * (int64_t)nper, 256, 32), 256, 0,
+                     ncell, (int)nmonths, (int)month0, (int)nyear, (int)nper, (int)k_prev, (int)k_next, gamma, d_hydro, d_thresh);
 }
 
 extern "C" int xh_drought_stats(xh_ctx *ctx, int64_t ncell, int32_t nmonths, int32_t nthresh, const double *d_hydro,
@@ -114,10 +106,6 @@ extern "C" int xh_drought_stats(xh_ctx *ctx, int64_t ncell, int32_t nmonths, int
     XH_REQUIRE(ctx, d_hydro && d_thresh && ncell >= 0 && nmonths > 0 && nthresh >= 1, "xh_drought_stats: bad argument");
     XH_REQUIRE(ctx, nmonths % 2 == 0, "xh_drought_stats: nmonths (%d) must be even (whole years)", nmonths);
     if (ncell == 0) return XH_OK;
-    xh_span sp = xh_span_begin(ctx, "drought_stats");
-    hipLaunchKernelGGL(k_drought_stats, dim3((unsigned)((ncell + 255) / 256)), dim3(256), 0, ctx->stream, ncell, (int)nmonths,
-                       (int)nthresh, d_hydro, d_thresh, d_severity, d_intensity, d_duration);
-    xh_span_end(sp);
-    XH_HIP(ctx, hipGetLastError());
-    return XH_OK;
+    return xh_launch(ctx, "drought_stats", ctx->stream, k_drought_stats, xh_grid(ctx, ncell, 256), 256, 0, ncell, (int)nmonths,
+                     (int)nthresh, d_hydro, d_thresh, d_severity, d_intensity, d_duration);
 }

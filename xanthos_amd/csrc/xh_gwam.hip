@@ -22,7 +22,7 @@
 #include <cstdint>
 #include <vector>
 
-#include "xh_common.h"
+#include "xh_launch.h"
 
 namespace {
 
@@ -229,8 +229,6 @@ __global__ void __launch_bounds__(64) k_gwam_tile(int64_t ncell, int nmonths, in
     if (mine && sm_end) sm_end[c] = st;
 }
 
-bool aligned16(const void *p) { return p == nullptr || ((uintptr_t)p & 15) == 0; }
-
 }  // namespace
 
 extern "C" int xh_hargreaves_pet(xh_ctx *ctx, int64_t ncell, int32_t nmonths, const double *d_temp, const double *d_dtr,
@@ -244,26 +242,18 @@ extern "C" int xh_hargreaves_pet(xh_ctx *ctx, int64_t ncell, int32_t nmonths, co
     std::vector<HgMonth> tab(nmonths);
     for (int m = 0; m < nmonths; ++m)
         tab[m] = HgMonth{std::sin(h_solar_dec[m]), std::cos(h_solar_dec[m]), std::tan(h_solar_dec[m]), h_dr[m], h_ndays[m]};
-    const size_t tab_bytes = (sizeof(HgMonth) * nmonths + 255) & ~size_t(255);
-    void *buf = nullptr;
-    int rc = xh_scratch(ctx, 2, tab_bytes + sizeof(double) * 3 * ncell, &buf);
+    void *at[2];
+    const int rc = xh_stage(ctx, 2, {{tab.data(), sizeof(HgMonth) * nmonths}}, sizeof(double) * 3 * ncell, at);
     if (rc) return rc;
-    HgMonth *d_tab = static_cast<HgMonth *>(buf);
-    double *d_trig = reinterpret_cast<double *>(static_cast<char *>(buf) + tab_bytes);
-    XH_HIP(ctx, hipMemcpyAsync(d_tab, tab.data(), sizeof(HgMonth) * nmonths, hipMemcpyHostToDevice, ctx->stream));
-    XH_HIP(ctx, hipStreamSynchronize(ctx->stream));      // tab is a local
+    const HgMonth *d_tab = static_cast<const HgMonth *>(at[0]);
+    double *d_trig = static_cast<double *>(at[1]);
     const int64_t n = ncell * (int64_t)nmonths;
-    int64_t blocks = (n + 255) / 256;
-    const int64_t cap = (int64_t)ctx->prop.multiProcessorCount * 32;
-    if (blocks > cap) blocks = cap;
-    xh_span sp = xh_span_begin(ctx, "hargreaves_pet");
-    hipLaunchKernelGGL(k_hg_lat, dim3((unsigned)((ncell + 255) / 256)), dim3(256), 0, ctx->stream, ncell, d_lat_rad, d_trig);
-    hipLaunchKernelGGL(k_hargreaves_pet, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, n, (int)nmonths, ncell, d_temp,
-                       d_dtr, (const double *)d_trig, (const HgMonth *)d_tab, d_pet);
-    xh_span_end(sp);
-    XH_HIP(ctx, hipGetLastError());
-    ++ctx->work_seq;
-    return XH_OK;
+    return xh_timed(ctx, "hargreaves_pet", ctx->stream, [&] {
+        const int rc = xh_launch(ctx, nullptr, ctx->stream, k_hg_lat, xh_grid(ctx, ncell, 256), 256, 0, ncell, d_lat_rad, d_trig);
+        if (rc) return rc;
+        return xh_launch(ctx, nullptr, ctx->stream, k_hargreaves_pet, xh_grid(ctx, n, 256, 32), 256, 0, n, (int)nmonths, ncell,
+                         d_temp, d_dtr, d_trig, d_tab, d_pet);
+    });
 }
 
 extern "C" int xh_gwam(xh_ctx *ctx, int64_t ncell, int32_t nmonths, int32_t spinup, int32_t precip_col_spinup,
@@ -276,7 +266,8 @@ extern "C" int xh_gwam(xh_ctx *ctx, int64_t ncell, int32_t nmonths, int32_t spin
     XH_REQUIRE(ctx, precip_col_spinup >= -1 && precip_col_spinup < nmonths && precip_col_sim >= -1 && precip_col_sim < nmonths,
                "xh_gwam: precipitation column outside [-1, nmonths)");
     XH_REQUIRE(ctx, d_pet && d_precip && d_sm_max && d_sm0, "xh_gwam: NULL argument");
-    XH_REQUIRE(ctx, aligned16(d_pet) && aligned16(d_precip) && aligned16(d_aet) && aligned16(d_q) && aligned16(d_sav),
+    XH_REQUIRE(ctx,
+               xh_aligned16(d_pet) && xh_aligned16(d_precip) && xh_aligned16(d_aet) && xh_aligned16(d_q) && xh_aligned16(d_sav),
                "xh_gwam: [ncell, nmonths] arrays must be 16-byte aligned");
     if (ncell == 0) return XH_OK;
     const double k1 = 1.0 - std::exp(-1.0);              // gwam.py:80: 1 - exp(-alpha), alpha = 1
@@ -286,23 +277,12 @@ extern "C" int xh_gwam(xh_ctx *ctx, int64_t ncell, int32_t nmonths, int32_t spin
         int rc = xh_scratch(ctx, 2, sizeof(double) * ncell, &buf);
         if (rc) return rc;
         double *d_state = static_cast<double *>(buf);
-        xh_span sp = xh_span_begin(ctx, "gwam_spinup");
-        hipLaunchKernelGGL(k_gwam_spinup, dim3((unsigned)((ncell + 63) / 64)), dim3(64), 0, ctx->stream, ncell, (int)nmonths,
-                           (int)spinup, (int)precip_col_spinup, indexing, k1, d_pet, d_precip, d_sm_max, d_sm0, d_state);
-        xh_span_end(sp);
-        XH_HIP(ctx, hipGetLastError());
+        rc = xh_launch(ctx, "gwam_spinup", ctx->stream, k_gwam_spinup, xh_grid(ctx, ncell, 64), 64, 0, ncell, (int)nmonths,
+                       (int)spinup, (int)precip_col_spinup, indexing, k1, d_pet, d_precip, d_sm_max, d_sm0, d_state);
+        if (rc) return rc;
         sm_start = d_state;
     }
-    xh_span sp = xh_span_begin(ctx, "gwam_sim");
-    const unsigned blocks = (unsigned)((ncell + CPW - 1) / CPW);
-    if (precip_col_sim < 0)
-        hipLaunchKernelGGL(k_gwam_tile<true>, dim3(blocks), dim3(64), 0, ctx->stream, ncell, (int)nmonths, -1, indexing, k1,
-                           d_pet, d_precip, d_sm_max, sm_start, d_aet, d_q, d_sav, d_sm_end);
-    else
-        hipLaunchKernelGGL(k_gwam_tile<false>, dim3(blocks), dim3(64), 0, ctx->stream, ncell, (int)nmonths,
-                           (int)precip_col_sim, indexing, k1, d_pet, d_precip, d_sm_max, sm_start, d_aet, d_q, d_sav, d_sm_end);
-    xh_span_end(sp);
-    XH_HIP(ctx, hipGetLastError());
-    ++ctx->work_seq;
-    return XH_OK;
+    return xh_launch(ctx, "gwam_sim", ctx->stream, precip_col_sim < 0 ? k_gwam_tile<true> : k_gwam_tile<false>,
+                     xh_grid(ctx, ncell, CPW), 64, 0, ncell, (int)nmonths, (int)precip_col_sim, indexing, k1, d_pet, d_precip,
+                     d_sm_max, sm_start, d_aet, d_q, d_sav, d_sm_end);
 }

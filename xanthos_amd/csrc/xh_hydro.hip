@@ -26,7 +26,7 @@
 #include <cmath>
 #include <cstdint>
 
-#include "xh_common.h"
+#include "xh_launch.h"
 #include "xh_kahan.h"
 
 #pragma clang fp contract(off)
@@ -356,8 +356,6 @@ __global__ void __launch_bounds__(256) k_hact_sim(int nmonths, int ndams, int ny
     bad_month[d] = first_bad;
 }
 
-int blocks_for(int64_t n, int threads) { return (int)((n + threads - 1) / threads); }
-
 }  // namespace
 
 extern "C" int xh_hpot_qmax(xh_ctx *ctx, int64_t ncell, int32_t nmonths, int32_t k_prev, int32_t k_next, double gamma,
@@ -369,15 +367,8 @@ extern "C" int xh_hpot_qmax(xh_ctx *ctx, int64_t ncell, int32_t nmonths, int32_t
     XH_REQUIRE(ctx, k_prev >= 0 && k_prev < nmonths && k_next >= k_prev && k_next < nmonths && gamma >= 0.0 && gamma <= 1.0,
                "xh_hpot_qmax: order statistics %d, %d / weight %g invalid for %d samples", k_prev, k_next, gamma, nmonths);
     if (ncell == 0) return XH_OK;
-    int64_t blocks = ncell;
-    const int64_t cap = (int64_t)ctx->prop.multiProcessorCount * 32;
-    if (blocks > cap) blocks = cap;
-    xh_span sp = xh_span_begin(ctx, "hpot_qmax");
-    hipLaunchKernelGGL(k_hpot_qmax, dim3((unsigned)blocks), dim3(QMAX_THREADS), (size_t)nmonths * sizeof(uint64_t), ctx->stream,
-                       ncell, (int)nmonths, (int)k_prev, (int)k_next, gamma, d_q, d_qmax);
-    xh_span_end(sp);
-    XH_HIP(ctx, hipGetLastError());
-    return XH_OK;
+    return xh_launch(ctx, "hpot_qmax", ctx->stream, k_hpot_qmax, xh_grid(ctx, ncell, 1, 32), QMAX_THREADS,
+                     (size_t)nmonths * sizeof(uint64_t), ncell, (int)nmonths, (int)k_prev, (int)k_next, gamma, d_q, d_qmax);
 }
 
 extern "C" int xh_hpot_energy(xh_ctx *ctx, int64_t ncell, int32_t nmonths, int32_t nyears, const int32_t *d_year_of_month,
@@ -387,12 +378,8 @@ extern "C" int xh_hpot_energy(xh_ctx *ctx, int64_t ncell, int32_t nmonths, int32
     XH_REQUIRE(ctx, d_year_of_month && d_q && d_qmax && d_elev && d_E && ncell >= 0 && nmonths > 0 && nyears > 0,
                "xh_hpot_energy: bad argument");
     if (ncell == 0) return XH_OK;
-    xh_span sp = xh_span_begin(ctx, "hpot_energy");
-    hipLaunchKernelGGL(k_hpot_energy, dim3(blocks_for(ncell, 256)), dim3(256), 0, ctx->stream, ncell, (int)nmonths, (int)nyears,
-                       d_year_of_month, c_ef_sww, c_hours, c_twh, c_ej, d_q, d_qmax, d_elev, d_E);
-    xh_span_end(sp);
-    XH_HIP(ctx, hipGetLastError());
-    return XH_OK;
+    return xh_launch(ctx, "hpot_energy", ctx->stream, k_hpot_energy, xh_grid(ctx, ncell, 256), 256, 0, ncell, (int)nmonths,
+                     (int)nyears, d_year_of_month, c_ef_sww, c_hours, c_twh, c_ej, d_q, d_qmax, d_elev, d_E);
 }
 
 extern "C" int xh_hpot_region(xh_ctx *ctx, int32_t ngroups, int32_t nyears, const int64_t *d_indptr, const int64_t *d_cells,
@@ -400,12 +387,8 @@ extern "C" int xh_hpot_region(xh_ctx *ctx, int32_t ngroups, int32_t nyears, cons
     if (!ctx) return XH_ERR_ARG;
     XH_REQUIRE(ctx, d_indptr && d_cells && d_E && d_R && ngroups >= 0 && nyears > 0, "xh_hpot_region: bad argument");
     if (ngroups == 0) return XH_OK;
-    xh_span sp = xh_span_begin(ctx, "hpot_region");
-    hipLaunchKernelGGL(k_hpot_region, dim3(blocks_for((int64_t)ngroups * nyears, 256)), dim3(256), 0, ctx->stream, (int)ngroups,
-                       (int)nyears, d_indptr, d_cells, d_E, d_R);
-    xh_span_end(sp);
-    XH_HIP(ctx, hipGetLastError());
-    return XH_OK;
+    return xh_launch(ctx, "hpot_region", ctx->stream, k_hpot_region, xh_grid(ctx, (int64_t)ngroups * nyears, 256), 256, 0,
+                     (int)ngroups, (int)nyears, d_indptr, d_cells, d_E, d_R);
 }
 
 extern "C" int xh_hact_inflow(xh_ctx *ctx, int64_t ncell, int32_t nmonths, int32_t ndams, int32_t month0,
@@ -417,14 +400,13 @@ extern "C" int xh_hact_inflow(xh_ctx *ctx, int64_t ncell, int32_t nmonths, int32
                "xh_hact_inflow: bad argument");
     XH_REQUIRE(ctx, nmonths >= 12, "xh_hact_inflow: %d months do not cover every calendar month", nmonths);
     if (ndams == 0) return XH_OK;
-    xh_span sp = xh_span_begin(ctx, "hact_inflow");
-    hipLaunchKernelGGL(k_hact_gather, dim3(blocks_for((int64_t)nmonths * ndams, 256)), dim3(256), 0, ctx->stream, ncell,
-                       (int)nmonths, (int)ndams, d_dam_cell, d_catch, d_assumed, cumecs_to_mm3, d_q, d_inflow);
-    hipLaunchKernelGGL(k_hact_env, dim3(blocks_for(ndams, 256)), dim3(256), 0, ctx->stream, (int)nmonths, (int)ndams,
-                       (int)month0, d_inflow, d_env, d_bad);
-    xh_span_end(sp);
-    XH_HIP(ctx, hipGetLastError());
-    return XH_OK;
+    return xh_timed(ctx, "hact_inflow", ctx->stream, [&] {
+        const int rc = xh_launch(ctx, nullptr, ctx->stream, k_hact_gather, xh_grid(ctx, (int64_t)nmonths * ndams, 256), 256, 0,
+                                 ncell, (int)nmonths, (int)ndams, d_dam_cell, d_catch, d_assumed, cumecs_to_mm3, d_q, d_inflow);
+        if (rc) return rc;
+        return xh_launch(ctx, nullptr, ctx->stream, k_hact_env, xh_grid(ctx, ndams, 256), 256, 0, (int)nmonths, (int)ndams,
+                         (int)month0, d_inflow, d_env, d_bad);
+    });
 }
 
 extern "C" int xh_hact_sim(xh_ctx *ctx, int32_t nmonths, int32_t ndams, int32_t nyears, int32_t month0,
@@ -436,11 +418,7 @@ extern "C" int xh_hact_sim(xh_ctx *ctx, int32_t nmonths, int32_t ndams, int32_t 
                         nmonths > 0 && ndams >= 0 && nyears > 0 && month0 >= 0 && month0 < 12,
                "xh_hact_sim: bad argument");
     if (ndams == 0) return XH_OK;
-    xh_span sp = xh_span_begin(ctx, "hact_sim");
-    hipLaunchKernelGGL(k_hact_sim, dim3(blocks_for(ndams, 256)), dim3(256), 0, ctx->stream, (int)nmonths, (int)ndams,
-                       (int)nyears, (int)month0, d_year_of_month, sww, secs_in_month, d_inflow, d_env, d_rc, d_par, d_power,
-                       d_annual, d_bad_month);
-    xh_span_end(sp);
-    XH_HIP(ctx, hipGetLastError());
-    return XH_OK;
+    return xh_launch(ctx, "hact_sim", ctx->stream, k_hact_sim, xh_grid(ctx, ndams, 256), 256, 0, (int)nmonths, (int)ndams,
+                     (int)nyears, (int)month0, d_year_of_month, sww, secs_in_month, d_inflow, d_env, d_rc, d_par, d_power,
+                     d_annual, d_bad_month);
 }

@@ -19,7 +19,7 @@
 #include <cstring>
 #include <thread>
 
-#include "xh_common.h"
+#include "xh_launch.h"
 
 namespace {
 
@@ -105,7 +105,7 @@ int io_download(xh_ctx *ctx, const IoJob *jobs, int njobs) {
     if (njobs > IO_MAX_FILES) return xh_fail(ctx, XH_ERR_LIMIT, "at most %d files per call", IO_MAX_FILES);
     const int rc = xh_settle(ctx);      // earlier work may still write the sources; a routing call that must be re-run is re-run here
     if (rc != XH_OK && rc != XH_ERR_DEVICE) return rc;
-    ctx->work_seq += 1;
+    xh_note_work(ctx, ctx->stream);
     if (njobs == 0) return rc;
     int fds[IO_MAX_FILES];
     auto close_all = [&](int upto) {
@@ -148,7 +148,7 @@ int xh_upload_file(xh_ctx *ctx, void *d_dst, const char *path, uint64_t offset, 
     if (!ctx || !path || (bytes && !d_dst)) return XH_ERR_ARG;
     const int rc = xh_settle(ctx);                   // earlier work may still read the destination; re-routes happen here
     if (rc != XH_OK && rc != XH_ERR_DEVICE) return rc;
-    ctx->work_seq += 1;
+    xh_note_work(ctx, ctx->stream);
     if (bytes == 0) return rc;
     const int fd = open(path, O_RDONLY);
     if (fd < 0) return xh_fail(ctx, XH_ERR_ARG, "%s: %s", path, strerror(errno));

@@ -21,7 +21,7 @@
 #include <cstdint>
 #include <vector>
 
-#include "xh_common.h"
+#include "xh_launch.h"
 
 namespace {
 
@@ -156,28 +156,20 @@ extern "C" int xh_hs_pet(xh_ctx *ctx, int64_t ncell, int32_t nmonths, const doub
         const double delta = 0.4102 * std::sin(2 * (PI / 365) * (j[m] - 80));
         tab[m] = HsMonth{std::cos(delta), std::tan(delta)};
     }
-    const size_t tab_bytes = (sizeof(HsMonth) * 12 + sizeof(double) * nmonths + 255) & ~size_t(255);
-    void *buf = nullptr;
-    int rc = xh_scratch(ctx, 2, tab_bytes + sizeof(double) * 2 * ncell, &buf);
+    void *at[3];
+    const int rc = xh_stage(ctx, 2, {{tab.data(), sizeof(HsMonth) * 12}, {h_ndays, sizeof(double) * nmonths}},
+                            sizeof(double) * 2 * ncell, at);
     if (rc) return rc;
-    HsMonth *d_tab = static_cast<HsMonth *>(buf);
-    double *d_nd = reinterpret_cast<double *>(d_tab + 12);
-    double *d_trig = reinterpret_cast<double *>(static_cast<char *>(buf) + tab_bytes);
-    XH_HIP(ctx, hipMemcpyAsync(d_tab, tab.data(), sizeof(HsMonth) * 12, hipMemcpyHostToDevice, ctx->stream));
-    XH_HIP(ctx, hipMemcpyAsync(d_nd, h_ndays, sizeof(double) * nmonths, hipMemcpyHostToDevice, ctx->stream));
-    XH_HIP(ctx, hipStreamSynchronize(ctx->stream));      // tab is a local, h_ndays the caller's
+    const HsMonth *d_tab = static_cast<const HsMonth *>(at[0]);
+    const double *d_nd = static_cast<const double *>(at[1]);
+    double *d_trig = static_cast<double *>(at[2]);
     const int64_t n = ncell * (int64_t)nmonths;
-    int64_t blocks = (n + 255) / 256;
-    const int64_t cap = (int64_t)ctx->prop.multiProcessorCount * 32;
-    if (blocks > cap) blocks = cap;
-    xh_span sp = xh_span_begin(ctx, "hs_pet");
-    hipLaunchKernelGGL(k_hs_lat, dim3((unsigned)((ncell + 255) / 256)), dim3(256), 0, ctx->stream, ncell, d_lat_deg, d_trig);
-    hipLaunchKernelGGL(k_hs_pet, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, n, (int)nmonths, ncell, d_tas, d_tmax,
-                       d_tmin, (const double *)d_trig, (const HsMonth *)d_tab, (const double *)d_nd, d_pet);
-    xh_span_end(sp);
-    XH_HIP(ctx, hipGetLastError());
-    ++ctx->work_seq;
-    return XH_OK;
+    return xh_timed(ctx, "hs_pet", ctx->stream, [&] {
+        const int rc = xh_launch(ctx, nullptr, ctx->stream, k_hs_lat, xh_grid(ctx, ncell, 256), 256, 0, ncell, d_lat_deg, d_trig);
+        if (rc) return rc;
+        return xh_launch(ctx, nullptr, ctx->stream, k_hs_pet, xh_grid(ctx, n, 256, 32), 256, 0, n, (int)nmonths, ncell, d_tas,
+                         d_tmax, d_tmin, d_trig, d_tab, d_nd, d_pet);
+    });
 }
 
 extern "C" int xh_thornthwaite_pet(xh_ctx *ctx, int64_t ncell, int32_t nmonths, int32_t start_year, int32_t daylight_mode,
@@ -192,28 +184,15 @@ extern "C" int xh_thornthwaite_pet(xh_ctx *ctx, int64_t ncell, int32_t nmonths, 
     // tan of the solar declination of days 1..366 (thornthwaite.py:29-32) on the host (libm)
     std::vector<double> tdec(366);
     for (int d = 0; d < 366; ++d) tdec[d] = std::tan(0.409 * std::sin(((2 * PI / 365.0) * (d + 1) - 1.39)));
-    const size_t tab_bytes = (sizeof(double) * 366 + 255) & ~size_t(255);
-    void *buf = nullptr;
-    int rc = xh_scratch(ctx, 2, tab_bytes + (d_daylight ? 0 : sizeof(double) * 24 * ncell), &buf);
+    void *at[2];
+    int rc = xh_stage(ctx, 2, {{tdec.data(), sizeof(double) * 366}}, d_daylight ? 0 : sizeof(double) * 24 * ncell, at);
     if (rc) return rc;
-    double *d_tdec = static_cast<double *>(buf);
-    double *d_dl = d_daylight ? d_daylight : reinterpret_cast<double *>(static_cast<char *>(buf) + tab_bytes);
-    XH_HIP(ctx, hipMemcpyAsync(d_tdec, tdec.data(), sizeof(double) * 366, hipMemcpyHostToDevice, ctx->stream));
-    XH_HIP(ctx, hipStreamSynchronize(ctx->stream));      // tdec is a local
-    xh_span sp = xh_span_begin(ctx, "trn_daylight");
-    hipLaunchKernelGGL(k_trn_daylight, dim3((unsigned)((ncell * 24 + 255) / 256)), dim3(256), 0, ctx->stream, ncell,
-                       d_lat_rad, (const double *)d_tdec, d_dl);
-    xh_span_end(sp);
-    XH_HIP(ctx, hipGetLastError());
-    if (nmonths > 0) {
-        const int nyears = nmonths / 12;
-        const int64_t ngroups = ncell * (int64_t)nyears;
-        xh_span sp2 = xh_span_begin(ctx, "trn_pet");
-        hipLaunchKernelGGL(k_trn_pet, dim3((unsigned)((ngroups + TG - 1) / TG)), dim3(TG), 0, ctx->stream, ngroups, nyears,
-                           (int)start_year, (int)(daylight_mode == XH_DAYLIGHT_MONTHLY), d_tas, (const double *)d_dl, d_pet);
-        xh_span_end(sp2);
-        XH_HIP(ctx, hipGetLastError());
-    }
-    ++ctx->work_seq;
-    return XH_OK;
+    double *d_dl = d_daylight ? d_daylight : static_cast<double *>(at[1]);
+    rc = xh_launch(ctx, "trn_daylight", ctx->stream, k_trn_daylight, xh_grid(ctx, ncell * 24, 256), 256, 0, ncell, d_lat_rad,
+                   static_cast<const double *>(at[0]), d_dl);
+    if (rc || nmonths == 0) return rc;
+    const int nyears = nmonths / 12;
+    const int64_t ngroups = ncell * (int64_t)nyears;
+    return xh_launch(ctx, "trn_pet", ctx->stream, k_trn_pet, xh_grid(ctx, ngroups, TG), TG, 0, ngroups, nyears, (int)start_year,
+                     (int)(daylight_mode == XH_DAYLIGHT_MONTHLY), d_tas, d_dl, d_pet);
 }

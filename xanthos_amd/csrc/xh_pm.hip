@@ -16,7 +16,7 @@
 // exp/log/sqrt implementations, from fdiv() below and from those regroupings -- a few ulp each, 5e-13 in PET overall.
 #include <algorithm>
 
-#include "xh_common.h"
+#include "xh_launch.h"
 #include "xh_math.h"
 #include "xh_stage.h"
 
@@ -603,28 +603,21 @@ int xh_pm_enqueue(xh_ctx *ctx, hipStream_t st, xh_pm_setup &s, int m_begin, int 
     // (threads per workgroup: the caller's choice -- one-wave workgroups fit a SIMD's free registers whatever the other SIMDs
     // of the CU hold: the fillers of a fed run --, default 256)
     const int bsz = (s.block == 64 || s.block == 128) ? s.block : 256;
-    const int64_t cap = (int64_t)ctx->prop.multiProcessorCount * 32 * (256 / bsz);
-    const int64_t need = (items + bsz - 1) / bsz;
-    const int64_t passes = (need + cap - 1) / cap;
-    int64_t blocks = (need + passes - 1) / passes;
-    xh_span sp = xh_span_begin_on(ctx, "pm_pet", st);
-    if (!s.pressure_done) {
-        hipLaunchKernelGGL(k_pm_pressure, dim3((unsigned)((s.ncell + 255) / 256)), dim3(256), 0, st, s.ncell, d_elev,
-                           s.d_pressure);
-        s.pressure_done = true;
-    }
-    // the caller's choice of variant (xh_pm_setup::paired: the fillers of a fed run), default k_pm_pet
-    if (s.paired)
-        hipLaunchKernelGGL(k_pm_pet2, dim3((unsigned)blocks), dim3(bsz), 0, st, static_cast<const PmTablesDev *>(s.d_tab),
-                           s.d_lcy, s.ncell, s.nmonths, m_begin, m_count, d_tas, d_tmin, d_rhs, d_wind, d_rsds, d_rlds,
-                           d_tairprev, d_lct, s.d_pressure, d_pet);
-    else
-        hipLaunchKernelGGL(k_pm_pet, dim3((unsigned)blocks), dim3(bsz), 0, st, static_cast<const PmTablesDev *>(s.d_tab),
-                           s.d_lcy, s.ncell, s.nmonths, m_begin, m_count, d_tas, d_tmin, d_rhs, d_wind, d_rsds, d_rlds,
-                           d_tairprev, d_lct, s.d_pressure, d_pet);
-    xh_span_end(sp);
-    XH_HIP(ctx, hipGetLastError());
-    return XH_OK;
+    const int64_t need = (items + bsz - 1) / bsz, capped = xh_grid(ctx, items, bsz, 32 * (256 / bsz));
+    const int64_t passes = (need + capped - 1) / capped;
+    const unsigned blocks = (unsigned)((need + passes - 1) / passes);
+    return xh_timed(ctx, "pm_pet", st, [&] {
+        if (!s.pressure_done) {
+            const int rc = xh_launch(ctx, nullptr, st, k_pm_pressure, xh_grid(ctx, s.ncell, 256), 256, 0, s.ncell, d_elev,
+                                     s.d_pressure);
+            if (rc) return rc;
+            s.pressure_done = true;
+        }
+        // the caller's choice of variant (xh_pm_setup::paired: the fillers of a fed run), default k_pm_pet
+        return xh_launch(ctx, nullptr, st, s.paired ? k_pm_pet2 : k_pm_pet, blocks, bsz, 0,
+                         static_cast<const PmTablesDev *>(s.d_tab), s.d_lcy, s.ncell, s.nmonths, m_begin, m_count, d_tas,
+                         d_tmin, d_rhs, d_wind, d_rsds, d_rlds, d_tairprev, d_lct, s.d_pressure, d_pet);
+    });
 }
 
 extern "C" int xh_pm_pet(xh_ctx *ctx, const xh_pm_tables *t, int64_t ncell, int32_t nmonths, int32_t start_year,

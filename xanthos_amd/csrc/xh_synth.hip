@@ -6,7 +6,7 @@
 // arrays to the HIP path and to the oracle, so the two generators never need to agree exactly.
 #include <cmath>
 
-#include "xh_common.h"
+#include "xh_launch.h"
 
 namespace {
 
@@ -73,12 +73,6 @@ extern "C" int xh_synth_forcing(xh_ctx *ctx, uint64_t seed, double nan_frac, int
     XH_REQUIRE(ctx, d_lat && d_tas && (all || none), "xh_synth_forcing: NULL argument (all eight arrays, or d_tas only)");
     XH_REQUIRE(ctx, ncell >= 0 && nmonths > 0 && nmonths < 4096, "xh_synth_forcing: bad size");
     if (ncell == 0) return XH_OK;
-    const int64_t total = ncell * (int64_t)nmonths;
-    int64_t blocks = (total + 255) / 256;
-    const int64_t cap = (int64_t)ctx->prop.multiProcessorCount * 16;
-    if (blocks > cap) blocks = cap;
-    hipLaunchKernelGGL(k_synth, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, seed, nan_frac, ncell, (int)nmonths, d_lat,
-                       d_cell_ids, d_tas, d_tmin, d_rhs, d_wind, d_rsds, d_rlds, d_precip, d_abcd_tmin);
-    XH_HIP(ctx, hipGetLastError());
-    return XH_OK;
+    return xh_launch(ctx, nullptr, ctx->stream, k_synth, xh_grid(ctx, ncell * (int64_t)nmonths, 256, 16), 256, 0, seed, nan_frac,
+                     ncell, (int)nmonths, d_lat, d_cell_ids, d_tas, d_tmin, d_rhs, d_wind, d_rsds, d_rlds, d_precip, d_abcd_tmin);
 }
