@@ -22,8 +22,17 @@ from xanthos_amd import synth
 from xanthos_amd.dist import make_shards, host_gather
 from xanthos_amd.pipeline import topology_from_world
 if sys.argv[2] == 'gloo':              # torch.distributed (gloo) behind the same small interface: bench.py's adapter
-    import torch, torch.distributed as dist
-    dist.init_process_group(backend='gloo', rank=int(os.environ['RANK']), world_size=int(os.environ['WORLD_SIZE']))
+    import datetime, torch, torch.distributed as dist
+    rank, size = int(os.environ['RANK']), int(os.environ['WORLD_SIZE'])
+    # rank 0's store listens on a port the system picks (MASTER_PORT=0) and writes it to sys.argv[3] before rank 1 is
+    # started with it; a rendezvous that fails ends in two minutes rather than torch's thirty
+    limit = datetime.timedelta(seconds=120)
+    store = dist.TCPStore('127.0.0.1', int(os.environ['MASTER_PORT']), size, rank == 0, timeout=limit, wait_for_workers=False)
+    if rank == 0:
+        with open(sys.argv[3] + '.tmp', 'w') as f:
+            f.write(str(store.port))
+        os.replace(sys.argv[3] + '.tmp', sys.argv[3])
+    dist.init_process_group(backend='gloo', store=store, rank=rank, world_size=size, timeout=limit)
     import bench
     group = bench.TorchGroup(dist, torch, 'gloo')
 else:                                  # the package's own TCP rendezvous (no torch anywhere in this process)
@@ -79,18 +88,34 @@ import pytest
 def test_host_gather_two_ranks(tmp_path, kind):
     """The fall-back of the write-out gather (rows through the process group) and the group's small collectives, with two
     rank processes on the CPU: through the package's own TCP rendezvous (launch.SocketGroup: what run_model() uses, no
-    torch in the process) and through torch.distributed's gloo backend behind bench.py's adapter."""
+    torch in the process) and through torch.distributed's gloo backend behind bench.py's adapter.  With gloo, rank 0's store
+    takes a port of the system's choosing and rank 1 starts once it is known: a port found free beforehand can be taken in
+    between, and a rank that keeps dialling a port nobody listens on yet can end up connected to itself."""
     script = tmp_path / 'worker.py'
     script.write_text(WORKER)
-    with socket.socket() as s:
-        s.bind(('127.0.0.1', 0))
-        port = s.getsockname()[1]
+    port_file = tmp_path / 'store_port'
+    port = 0
+    if kind == 'socket':
+        with socket.socket() as s:
+            s.bind(('127.0.0.1', 0))
+            port = s.getsockname()[1]
     procs = []
-    for rank in range(2):
-        env = dict(os.environ, RANK=str(rank), WORLD_SIZE='2', MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port))
-        procs.append(subprocess.Popen([sys.executable, str(script), ROOT, kind], env=env, stdout=subprocess.PIPE,
-                                      stderr=subprocess.STDOUT, text=True))
-    outs = [p.communicate(timeout=300)[0] for p in procs]
+    try:
+        for rank in range(2):
+            if rank == 1 and kind == 'gloo':
+                t_end = time.time() + 240
+                while not port_file.exists() and procs[0].poll() is None and time.time() < t_end:
+                    time.sleep(0.05)
+                assert port_file.exists(), 'rank 0 published no store port (exit status {})'.format(procs[0].poll())
+                port = int(port_file.read_text())
+            env = dict(os.environ, RANK=str(rank), WORLD_SIZE='2', MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port))
+            procs.append(subprocess.Popen([sys.executable, str(script), ROOT, kind, str(port_file)], env=env,
+                                          stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True))
+        outs = [p.communicate(timeout=300)[0] for p in procs]
+    finally:
+        for p in procs:                                   # nothing is left running when the test fails
+            if p.poll() is None:
+                p.kill()
     assert all(p.returncode == 0 for p in procs), outs
     assert 'GATHER_OK' in outs[0]
 

@@ -170,7 +170,7 @@ def test_model_matches_reference_run(golden, tmp_path, tag):
     from xanthos_amd.model import Xanthos
     g, ini = _tree(golden, tmp_path, tag)
     c = Xanthos(ini).execute()
-    assert c.pipe is not None                                        # the device-resident HgmPipeline ran it
+    assert c.pipe is not None                                        # the device-resident pipeline ran it
     for name in ('PET', 'AET', 'Q', 'Sav'):
         _close(name, getattr(c, name), g[tag + '_' + name], 1e-10, 1e-12, zeros=False)
     for name in ('ChStorage', 'Avg_ChFlow'):
@@ -204,6 +204,38 @@ def test_calibration_with_thornthwaite(tmp_path):
         kge = np.load(str(tmp_path / 'calib_out' / 'kge_result_basin_{}.npy'.format(b)))
         assert np.isfinite(kge).all()
         assert np.load(str(tmp_path / 'calib_out' / 'abcdm_parameters_basin_{}.npy'.format(b))).shape == (1, 5)
+
+
+@pytest.mark.parametrize('pet', ['hargreaves', 'hs', 'thornthwaite'])
+def test_pipeline_pet_only_matches_plugin(pet):
+    """The device-resident pipeline with runoff_module='none' and no routing: PET bit for bit that of the plugin's host
+    entry (the same kernel; NaN holes in every forcing go through the pipeline's own NaN rules), AET / Q / Sav zero."""
+    from xanthos_amd import _hip
+    from xanthos_amd.pet import hargreaves, hargreaves_samani as hs, thornthwaite as trn
+    from xanthos_amd.pipeline import DevicePipeline
+    w = synth.make_world(nrow=36, ncol=72, ncell=300, n_basins=3, seed=21)
+    y0, y1, nm = 1975, 1977, 36
+    base = synth.make_forcing(w, nm, nan_precip=False)
+    f = synth.hgm_forcing(w, base) if pet == 'hargreaves' else synth.pet_ext_forcing(w, base)
+    f = {k: np.array(v, dtype=np.float64) for k, v in f.items() if k not in ('precip', 'abcd_tmin')}
+    for i, v in enumerate(f.values()):
+        v[i::37, 5 + i] = np.nan
+    lat_deg = np.asarray(w.latitude, dtype=np.float64)
+    pipe = DevicePipeline(_hip.get_context(0), ncell=w.ncell, nmonths=nm, start_year=y0, pet_module=pet,
+                          runoff_module='none', lat_radians=np.radians(lat_deg), lat_degrees=lat_deg)
+    pipe.set_forcing(f)
+    pipe.run()
+    got = pipe.download(('pet', 'aet', 'q', 'sav'))
+    if pet == 'hargreaves':
+        want = hargreaves.run_hargreaves(f['temp'], f['dtr'], np.radians(lat_deg), y0, y1)
+    elif pet == 'hs':
+        want = hs.run_hs(f['tas'], f['tmax'], f['tmin'], lat_deg, y0, y1)
+    else:
+        want = trn.execute(f['tas'], np.radians(lat_deg), y0, y1)
+    assert np.array_equal(got['pet'], want, equal_nan=True)
+    assert np.isfinite(want).any()
+    for k in ('aet', 'q', 'sav'):
+        assert np.array_equal(got[k], np.zeros((w.ncell, nm))), k
 
 
 # ---------------------------------------------------------------------------------------------- full size

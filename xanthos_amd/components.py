@@ -10,17 +10,25 @@ the stages one by one (the calibration routing callback, components.py:486-497).
 """
 import logging
 import time
+from types import SimpleNamespace
 
 import numpy as np
 
-from . import _hip, launch
+from . import _hip, dist, launch
 from .calibrate import calibrate_abcd as calib_mod
 from .data_load import DataLoader
 from .ini_reader import ValidationException, check_modules
 from .pipeline import DevicePipeline
 from .utils import set_month_arrays
 
-HGM_PET = ('hargreaves', 'hs', 'thornthwaite')      # PET modules of the HgmPipeline (pipeline.py)
+HGM_PET = ('hargreaves', 'hs', 'thornthwaite')      # PET modules that run device resident with any runoff module
+
+# DevicePipeline forcing name -> DataLoader attribute, per PET / runoff module
+_FORCING_DATA = {'pm': {'tas': 'tair_load', 'tmin': 'TMIN_load', 'rhs': 'rhs_load', 'wind': 'wind_load',
+                        'rsds': 'rsds_load', 'rlds': 'rlds_load'},
+                 'hargreaves': {'temp': 'temp', 'dtr': 'dtr'}, 'hs': {'tas': 'hs_tas', 'tmax': 'hs_tmax', 'tmin': 'hs_tmin'},
+                 'thornthwaite': {'tas': 'tair'}, 'abcd': {'precip': 'precip', 'abcd_tmin': 'tmin'},
+                 'gwam': {'precip': 'precip'}, 'none': {}}
 
 pet_mod = runoff_mod = routing_mod = None
 
@@ -185,65 +193,137 @@ class Components:
     # ------------------------------------------------------------------ whole simulation, device resident
     def simulation(self, run_pet=True, run_runoff=True, run_routing=True, pet_num_steps=0, runoff_num_steps=0,
                    routing_num_steps=0, notify='simulation'):
-        """Run the configured stages (components.py:298-384)."""
+        """Run the configured stages (components.py:298-384).  Hargreaves, Hargreaves-Samani or Thornthwaite PET (-> GWAM /
+        ABCD / no runoff) and PM -> ABCD run device resident: one upload of the forcing, the outputs left in HBM.  GWAM's
+        spin-up pass and its simulation are one xh_gwam call; the spin-up pass's routing is skipped -- it changes nothing
+        (streamrouting does not mutate its inputs and calculate_routing starts again from data.chs_prev).  Anything else
+        runs stage by stage on host arrays.
+        On several ranks (PM -> ABCD only) ``dist.make_shards`` deals connected components of (same basin) U (flow edge)
+        onto the ranks -- the reference's only parallel seam is the basin chunking of abcd.py:369-389; every rank reads
+        only its rows of the forcing, runs the pipeline, and the six outputs travel to rank 0 in one RCCL gather (PET /
+        AET / Q / Sav beside the routing, ChStorage / Avg_ChFlow behind it), where they sit in HBM in grid order exactly
+        as a one-rank run leaves them."""
         if self.s.calibrate:
             self.calibrate()
             return
         logging.info('---{} in progress...'.format(notify))
         t0 = time.time()
-        s, d = self.s, self.data
-        if s.pet_module in HGM_PET and run_pet:
-            return self._simulation_hgm(run_runoff, run_routing, t0, notify)
-        full = (s.pet_module == 'pm' and s.runoff_module == 'abcd' and run_pet and run_runoff)
-        if not full:
+        s, group = self.s, self.group
+        hgm = s.pet_module in HGM_PET
+        if not run_pet or not (hgm or (s.pet_module == 'pm' and s.runoff_module == 'abcd' and run_runoff)):
             pet_out = self.calculate_pet()
             if run_runoff:
                 self.calculate_runoff(pet=pet_out)
             if run_routing and s.routing_module == 'mrtm':
                 self.calculate_routing(self.Q)
             return
+        runoff = s.runoff_module if run_runoff else 'none'
+        sharded = group is not None and group.size > 1
+        if hgm:
+            if sharded:
+                raise ValidationException('{}: {} PET and {} runoff run on one GPU; sharding them over several GPUs is not '
+                                          'implemented.'.format(s.mod_cfg, s.pet_module, s.runoff_module))
+            if runoff == 'gwam':
+                self._check_gwam_spinup()
+            elif runoff == 'abcd':
+                from .runoff import abcd as abcd_mod
+                abcd_mod._check_spinup(s.runoff_spinup, s.nmonths)
         ctx = _hip.get_context(s.device)
         t = time.time()
         um = self.topology() if (run_routing and s.routing_module == 'mrtm') else None
         self.timings['topology'] = time.time() - t
-        if self.group is not None and self.group.size > 1:
-            return self._simulation_sharded(ctx, um, t0, notify)
         t = time.time()
-        pipe = DevicePipeline(ctx, ncell=s.ncell, nmonths=s.nmonths, start_year=s.StartYear, basin_ids=d.basin_ids,
-                              abcd_pars=np.load(s.calib_file) if not isinstance(s.calib_file, np.ndarray) else s.calib_file,
-                              pm_tables=pet_mod.tables_from(d, s.pm_nlcs), lct=d.lct_load, elev=d.elev,
-                              lc_years=s.pm_lc_years, um=um,
-                              flow_dist=d.flow_dist if um is not None else np.zeros(s.ncell),
-                              velocity=d.str_velocity if um is not None else np.zeros(s.ncell), area=d.area,
-                              abcd_spinup=s.runoff_spinup, routing_spinup=getattr(s, 'routing_spinup', 0),
-                              water_idx=s.pm_water_idx, snow_idx=s.pm_snow_idx, use_snow=d.tmin is not None,
-                              chs_prev=getattr(d, 'chs_prev', None), plan_async=True, route_flags=self.route_flags())
+        shards = cells = None
+        if sharded:
+            shards = dist.make_shards(SimpleNamespace(basin_ids=np.asarray(self.data.basin_ids)), um, group.size)
+            cells = shards[group.rank].cells
+        pipe = DevicePipeline(ctx, **self._pipeline_args(runoff, um, cells))
         ctx.sync()
         self.timings['plan'] = time.time() - t          # static uploads; the routing partition runs on a host thread meanwhile
         t = time.time()
-        pipe.set_forcing({'tas': d.tair_load, 'tmin': d.TMIN_load, 'rhs': d.rhs_load, 'wind': d.wind_load,
-                          'rsds': d.rsds_load, 'rlds': d.rlds_load, 'precip': d.precip, 'abcd_tmin': d.tmin},
-                         tairprev=d._tairprev if hasattr(d, '_tairprev') else d.tairprev_load)
+        pipe.set_forcing(*self._forcing(runoff, cells))
         ctx.sync()
         self.timings['upload'] = time.time() - t
         t = time.time()
-        if um is not None:
-            pipe.plan                                   # waits for the partition if it is still being made
+        gather = None
+        if sharded:
+            gather = dist.OutputGather(ctx, pipe, shards, group, s.ncell,
+                                       names=('pet', 'aet', 'q', 'sav') + (('chs', 'avg') if um is not None else ()))
+        pipe.plan                                       # waits for the partition if it is still being made
         self.timings['plan_wait'] = time.time() - t
         t = time.time()
         ctx.timing_reset()
-        pipe.run_pm()
-        pipe.run_abcd()
-        if um is not None:
-            pipe.run_mrtm()
+        # one rank runs the stages strictly in order; a sharded run leaves XH_FUSED its say
+        pipe.run(fed=False, fused=None if sharded else False, after_runoff=gather.run_side if sharded else None)
+        if sharded:
+            gather.run_tail()
         ctx.sync()
+        if sharded:
+            group.barrier()
         self.timings['kernels'] = time.time() - t
-        logging.info('\tPET + runoff + routing kernels: {:.3f} seconds'.format(time.time() - t))
-        self._log_stage_rates(ctx, pipe, um is not None)
+        where = ' and the gather ({}), {} of {} cells on this rank'.format(gather.kind, pipe.ncell, s.ncell) if sharded else ''
+        logging.info('\tPET + runoff + routing kernels{}: {:.3f} seconds'.format(where, time.time() - t))
+        # one line per stage: kernel time (HIP events on the library's stream) and achieved HBM GB/s against the
+        # algorithmic bytes of the stage
+        for name, nbytes in pipe.stage_traffic():
+            ms, n = ctx.timing(name)
+            if n:
+                logging.info('\t{:14s} {:8.3f} ms, {:7.1f} GB/s of {} MB algorithmic traffic'.format(
+                    name, ms / n, nbytes / (ms / n) / 1e6, nbytes // 1000000))
+                self.timings['kernel_' + name] = ms / n / 1e3
         self._host = {}                    # the six results stay in HBM until they are read (or written)
         self.pipe = pipe
+        if sharded:
+            self.gather, self.shard_pipe = gather, pipe
+            # what the result properties and the writer look at: on the root the gathered arrays, in HBM, in grid order
+            self.pipe = SimpleNamespace(out=gather.out, plan=pipe.plan, ncell=s.ncell, nmonths=s.nmonths) if self.is_root else None
         self.timings['download'] = 0.0
         logging.info('---{0} has finished successfully: {1} seconds ---'.format(notify, time.time() - t0))
+
+    def _pipeline_args(self, runoff, um, cells=None):
+        """DevicePipeline's keyword arguments for this configuration; ``cells``: one rank's rows of the grid."""
+        s, d = self.s, self.data
+
+        def sel(a):
+            return a if cells is None or a is None else np.asarray(a)[cells]
+        kw = dict(ncell=s.ncell if cells is None else len(cells), nmonths=s.nmonths, start_year=s.StartYear,
+                  pet_module=s.pet_module, runoff_module=runoff)
+        if s.pet_module == 'pm':
+            kw.update(pm_tables=pet_mod.tables_from(d, s.pm_nlcs), lct=sel(d.lct_load), elev=sel(d.elev),
+                      lc_years=s.pm_lc_years, water_idx=s.pm_water_idx, snow_idx=s.pm_snow_idx)
+        else:
+            kw.update(lat_radians=sel(d.lat_radians), lat_degrees=sel(d.latitude),
+                      daylight=getattr(s, 'trn_daylight', 'reference'))
+        if runoff == 'abcd':
+            kw.update(basin_ids=sel(d.basin_ids), abcd_spinup=s.runoff_spinup, use_snow=d.tmin is not None,
+                      abcd_pars=s.calib_file if isinstance(s.calib_file, np.ndarray) else np.load(s.calib_file))
+        elif runoff == 'gwam':
+            kw.update(sm_max=sel(d.soil_moisture), sm0=sel(d.sm_prev), gwam_spinup=s.runoff_spinup,
+                      precipitation=s.gwam_precipitation)
+        if um is not None:
+            kw.update(um=um if cells is None else dist.sub_matrix(um, cells), flow_dist=sel(d.flow_dist),
+                      velocity=sel(d.str_velocity), area=sel(d.area), routing_spinup=getattr(s, 'routing_spinup', 0),
+                      chs_prev=sel(getattr(d, 'chs_prev', None)), route_flags=self.route_flags(), plan_async=True)
+        return kw
+
+    def _forcing(self, runoff, cells=None):
+        """(host forcing, tairprev) for DevicePipeline.set_forcing; ``cells``: one rank's rows (of a memory map: only these
+        rows are read)."""
+        s, d = self.s, self.data
+
+        def rows(a):
+            return a if cells is None or a is None else np.ascontiguousarray(a[cells], dtype=np.float64)
+        host = {name: rows(getattr(d, attr, None))
+                for module in (s.pet_module, runoff) for name, attr in _FORCING_DATA[module].items()}
+        tairprev = None
+        if s.pet_module == 'pm' and cells is None:
+            tairprev = d._tairprev if hasattr(d, '_tairprev') else d.tairprev_load
+        elif s.pet_module == 'pm':
+            # the previous CELL's temperature (data_load.py:128-129) of a shard's rows is not the row above: taken from the grid
+            prev = cells - 1
+            tairprev = np.ascontiguousarray(d.tair_load[np.maximum(prev, 0)], dtype=np.float64)
+            tairprev[prev < 0] = 0.0
+        return host, tairprev
 
     def _check_gwam_spinup(self):
         n = self.s.runoff_spinup
@@ -251,155 +331,6 @@ class Components:
             # the reference dies here: an IndexError in its PET step loop beyond the last month (components.py:330-340),
             # an AttributeError with no step at all (:337-340 take the whole-series branch, which Hargreaves lacks)
             raise ValidationException('[[gwam]] runoff_spinup = {} must lie in [1, nmonths = {}].'.format(n, self.s.nmonths))
-
-    def _simulation_hgm(self, run_runoff, run_routing, t0, notify):
-        """Hargreaves, Hargreaves-Samani or Thornthwaite PET -> GWAM (Hargreaves only) / ABCD / no runoff (-> MRTM), device
-        resident (configurations.py:104-121, components.py:298-384).
-        GWAM's spin-up pass and its simulation are one xh_gwam call; the spin-up pass's routing is skipped -- it changes
-        nothing (streamrouting does not mutate its inputs and calculate_routing starts again from data.chs_prev)."""
-        from .pipeline import HgmPipeline
-        from .runoff import abcd as abcd_mod
-        s, d = self.s, self.data
-        if self.group is not None and self.group.size > 1:
-            raise ValidationException('{}: {} PET and {} runoff run on one GPU; sharding them over several GPUs is not '
-                                      'implemented.'.format(s.mod_cfg, s.pet_module, s.runoff_module))
-        runoff = s.runoff_module if run_runoff else 'none'
-        if runoff == 'gwam':
-            self._check_gwam_spinup()
-        elif runoff == 'abcd':
-            abcd_mod._check_spinup(s.runoff_spinup, s.nmonths)
-        ctx = _hip.get_context(s.device)
-        t = time.time()
-        um = self.topology() if (run_routing and s.routing_module == 'mrtm') else None
-        self.timings['topology'] = time.time() - t
-        t = time.time()
-        kw = {}
-        if runoff == 'gwam':
-            kw = dict(sm_max=d.soil_moisture, sm0=d.sm_prev, gwam_spinup=s.runoff_spinup,
-                      precipitation=s.gwam_precipitation)
-        elif runoff == 'abcd':
-            kw = dict(basin_ids=d.basin_ids, abcd_pars=s.calib_file if isinstance(s.calib_file, np.ndarray) else
-                      np.load(s.calib_file), abcd_spinup=s.runoff_spinup, use_snow=d.tmin is not None)
-        pipe = HgmPipeline(ctx, ncell=s.ncell, nmonths=s.nmonths, start_year=s.StartYear, runoff_module=runoff,
-                           pet_module=s.pet_module, lat_radians=d.lat_radians, lat_degrees=d.latitude,
-                           daylight=getattr(s, 'trn_daylight', 'reference'), um=um,
-                           flow_dist=d.flow_dist if um is not None else None,
-                           velocity=d.str_velocity if um is not None else None, area=d.area,
-                           routing_spinup=getattr(s, 'routing_spinup', 0), chs_prev=getattr(d, 'chs_prev', None),
-                           route_flags=self.route_flags(), **kw)
-        self.timings['plan'] = time.time() - t
-        t = time.time()
-        if s.pet_module == 'hs':
-            forcing = {'tas': d.hs_tas, 'tmax': d.hs_tmax, 'tmin': d.hs_tmin}
-        elif s.pet_module == 'thornthwaite':
-            forcing = {'tas': d.tair}
-        else:
-            forcing = {'temp': d.temp, 'dtr': d.dtr}
-        forcing.update(precip=getattr(d, 'precip', None) if runoff != 'none' else None,
-                       abcd_tmin=getattr(d, 'tmin', None) if runoff == 'abcd' else None)
-        pipe.set_forcing(forcing)
-        ctx.sync()
-        self.timings['upload'] = time.time() - t
-        t = time.time()
-        ctx.timing_reset()
-        pipe.run()
-        ctx.sync()
-        self.timings['kernels'] = time.time() - t
-        logging.info('\tPET + runoff + routing kernels: {:.3f} seconds'.format(time.time() - t))
-        cm = pipe.ncell * pipe.nmonths
-        for name, nbytes in (('hargreaves_pet', cm * 24), ('hs_pet', cm * 32), ('trn_daylight', pipe.ncell * 24 * 8),
-                             ('trn_pet', cm * 16), ('gwam_spinup', pipe.ncell * pipe.gwam_spinup * 16),
-                             ('gwam_sim', cm * (40 if s.gwam_precipitation == 'monthly' else 32) if runoff == 'gwam' else 0),
-                             ('abcd_sim', cm * 48), ('mrtm_route', cm * 24 + pipe.ncell * pipe.routing_spinup * 8)):
-            ms, n = ctx.timing(name)
-            if n:
-                logging.info('\t{:14s} {:8.3f} ms, {:7.1f} GB/s of {} MB algorithmic traffic'.format(
-                    name, ms / n, nbytes / (ms / n) / 1e6, nbytes // 1000000))
-                self.timings['kernel_' + name] = ms / n / 1e3
-        self._host = {}
-        self.pipe = pipe
-        self.timings['download'] = 0.0
-        logging.info('---{0} has finished successfully: {1} seconds ---'.format(notify, time.time() - t0))
-
-    def _simulation_sharded(self, ctx, um, t0, notify):
-        """The device-resident simulation on this rank's share of the grid (components.py:298-384 for whole basins only; the
-        reference's only parallel seam is the basin chunking of abcd.py:369-389, whose results it re-scatters by membership --
-        the gather below is that step).  ``dist.make_shards`` deals connected components of (same basin) U (flow edge) onto
-        the ranks; every rank maps only ITS rows of the forcing files (memory maps: the rows are read, the rest of the files
-        is never touched), runs the unchanged pipeline, and the six outputs travel to rank 0 in one RCCL gather (PET / AET /
-        Q / Sav beside the routing, ChStorage / Avg_ChFlow behind it), where they sit in HBM in grid order exactly as a
-        one-rank run leaves them.  Every rank computes the same partition without talking."""
-        from types import SimpleNamespace
-        from . import dist
-        s, d, group = self.s, self.data, self.group
-        t = time.time()
-        shards = dist.make_shards(SimpleNamespace(basin_ids=np.asarray(d.basin_ids)), um, group.size)
-        c = shards[group.rank].cells
-        sub_um = dist.sub_matrix(um, c) if um is not None else None
-        pars = np.load(s.calib_file) if not isinstance(s.calib_file, np.ndarray) else s.calib_file
-        chs_prev = getattr(d, 'chs_prev', None)
-        pipe = DevicePipeline(ctx, ncell=len(c), nmonths=s.nmonths, start_year=s.StartYear, basin_ids=np.asarray(d.basin_ids)[c],
-                              abcd_pars=pars, pm_tables=pet_mod.tables_from(d, s.pm_nlcs), lct=np.asarray(d.lct_load)[c],
-                              elev=np.asarray(d.elev)[c], lc_years=s.pm_lc_years, um=sub_um,
-                              flow_dist=np.asarray(d.flow_dist)[c] if um is not None else np.zeros(len(c)),
-                              velocity=np.asarray(d.str_velocity)[c] if um is not None else np.zeros(len(c)),
-                              area=np.asarray(d.area)[c], abcd_spinup=s.runoff_spinup,
-                              routing_spinup=getattr(s, 'routing_spinup', 0), water_idx=s.pm_water_idx,
-                              snow_idx=s.pm_snow_idx, use_snow=d.tmin is not None,
-                              chs_prev=None if chs_prev is None else np.asarray(chs_prev)[c], plan_async=True,
-                              route_flags=self.route_flags())
-        self.timings['plan'] = time.time() - t
-        t = time.time()
-
-        def rows(a):
-            return None if a is None else np.ascontiguousarray(a[c], dtype=np.float64)      # (a memory map: only these rows are read)
-        # the previous CELL's temperature (data_load.py:128-129) of a shard's rows is not the row above: taken from the grid
-        prev = c - 1
-        tairprev = np.ascontiguousarray(d.tair_load[np.maximum(prev, 0)], dtype=np.float64)
-        tairprev[prev < 0] = 0.0
-        pipe.set_forcing({'tas': rows(d.tair_load), 'tmin': rows(d.TMIN_load), 'rhs': rows(d.rhs_load), 'wind': rows(d.wind_load),
-                          'rsds': rows(d.rsds_load), 'rlds': rows(d.rlds_load), 'precip': rows(d.precip),
-                          'abcd_tmin': rows(d.tmin)}, tairprev=tairprev)
-        ctx.sync()
-        self.timings['upload'] = time.time() - t
-        t = time.time()
-        names = ('pet', 'aet', 'q', 'sav') + (('chs', 'avg') if um is not None else ())
-        gather = dist.OutputGather(ctx, pipe, shards, group, s.ncell, names=names)
-        if um is not None:
-            pipe.plan
-        self.timings['plan_wait'] = time.time() - t
-        t = time.time()
-        ctx.timing_reset()
-        pipe.run(('pm', 'abcd', 'mrtm') if um is not None else ('pm', 'abcd'), fed=False, after_runoff=gather.run_side)
-        gather.run_tail()
-        ctx.sync()
-        group.barrier()
-        self.timings['kernels'] = time.time() - t
-        logging.info('\tPET + runoff + routing kernels and the gather ({}), {} of {} cells on this rank: {:.3f} seconds'.format(
-            gather.kind, len(c), s.ncell, time.time() - t))
-        self._log_stage_rates(ctx, pipe, um is not None)
-        self._host = {}
-        self.gather = gather
-        self.shard_pipe = pipe
-        # what the result properties and the writer look at: on the root the gathered arrays, in HBM, in grid order
-        self.pipe = SimpleNamespace(out=gather.out, plan=pipe.plan, ncell=s.ncell, nmonths=s.nmonths) if self.is_root else None
-        self.timings['download'] = 0.0
-        logging.info('---{0} has finished successfully: {1} seconds ---'.format(notify, time.time() - t0))
-
-    def _log_stage_rates(self, ctx, pipe, routed):
-        """One log line per stage: kernel time (HIP events on the library's stream) and achieved HBM GB/s against the
-        algorithmic bytes of the stage (PM 6 reads + 1 write + land cover, ABCD 3 + 3, MRTM 1 + 2)."""
-        cm = pipe.ncell * pipe.nmonths
-        stages = [('pm_pet', cm * 56 + pipe.ncell * (pipe.nmonths // 12) * self.s.pm_nlcs * 8),
-                  ('abcd_spinup', pipe.ncell * pipe.abcd_spinup * 24), ('abcd_sim', cm * 48)]
-        if routed:
-            stages.append(('mrtm_route', cm * 24 + pipe.ncell * pipe.routing_spinup * 8))
-        for name, nbytes in stages:
-            ms, n = ctx.timing(name)
-            if n:
-                logging.info('\t{:12s} {:8.3f} ms, {:7.1f} GB/s of {} MB algorithmic traffic'.format(
-                    name, ms / n, nbytes / (ms / n) / 1e6, nbytes // 1000000))
-                self.timings['kernel_' + name] = ms / n / 1e3
 
     def calibrate(self):
         """Calibrate the ABCD parameters per basin (components.py:486-497)."""
@@ -467,7 +398,6 @@ class Components:
         d = self.data
         if self.s.runoff_module != 'gwam' or d.country_ids is None:
             return d
-        from types import SimpleNamespace
         invalid = (np.asarray(d.soil_moisture) == 0) | (d.country_ids == 0) | (d.basin_ids == 0)
         view = SimpleNamespace(**vars(d))
         view.country_ids, view.basin_ids = d.country_ids.copy(), d.basin_ids.copy()

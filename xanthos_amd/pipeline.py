@@ -1,21 +1,30 @@
 """Device-resident PET -> runoff -> routing pipeline.
 
-One object owns the static grid data and the six output arrays in HBM and enqueues the three stages back to back
-on the context's stream; nothing crosses PCIe between stages.  ``components.Components`` (the reference-shaped
-harness), ``bench.py`` and the multi-GPU sharding all drive this class; the per-stage plugin functions in
-``pet/``, ``runoff/`` and ``routing/`` are the host-array entry points around the same C-ABI calls.
+One object owns the static grid data and the six output arrays in HBM and enqueues the stages back to back on the
+context's stream; nothing crosses PCIe between stages.  ``components.Components`` (the reference-shaped harness),
+``bench.py`` and the multi-GPU sharding all drive this class; the per-stage plugin functions in ``pet/``, ``runoff/``
+and ``routing/`` are the host-array entry points around the same C-ABI calls.
 """
 import os
+import threading
 
 import numpy as np
 
-from . import _hip
-from .pet import penman_monteith as pm_mod
+from .pet import hargreaves as hg_mod, hargreaves_samani as hs_mod, penman_monteith as pm_mod, thornthwaite as trn_mod
 from .routing import mrtm as mrtm_mod
+from .runoff import gwam as gwam_mod
 from .utils import set_month_arrays
 
 FEED_DEFAULT = '1'      # measured on MI355X: 26.4 -> 25.35 ms per full-grid step (profiles/round4/feed_first_block.txt)
-FORCING = ('tas', 'tmin', 'rhs', 'wind', 'rsds', 'rlds', 'precip', 'abcd_tmin')
+# forcing of each PET / runoff module, in upload order
+MODULE_FORCING = {'pm': ('tas', 'tmin', 'rhs', 'wind', 'rsds', 'rlds'), 'hargreaves': ('temp', 'dtr'),
+                  'hs': ('tas', 'tmax', 'tmin'), 'thornthwaite': ('tas',), 'abcd': ('precip', 'abcd_tmin'),
+                  'gwam': ('precip',), 'none': ()}
+# the names that lose their NaNs on the device right after the upload, as the loader's nan_to_num (data_load.py:120-125,
+# :137-138, :194-195); Hargreaves' and Hargreaves-Samani's forcing goes up as it is (the kernels clean it or keep NaN as
+# the reference does) and precipitation keeps NaN
+NAN_TO_NUM = {'pm': MODULE_FORCING['pm'], 'thornthwaite': ('tas',), 'abcd': ('abcd_tmin',)}
+FORCING = MODULE_FORCING['pm'] + MODULE_FORCING['abcd']
 OUTPUTS = ('pet', 'aet', 'q', 'sav', 'chs', 'avg')
 
 
@@ -36,55 +45,93 @@ def file_range_of(arr):
 
 
 class DevicePipeline:
-    """PM -> ABCD -> MRTM for one set of cells (the whole grid, or one rank's shard) on one GPU."""
+    """PET -> runoff (-> MRTM) for one set of cells (the whole grid, or one rank's shard) on one GPU.  PET: Penman-Monteith
+    (``pm``), Hargreaves, Hargreaves-Samani (``hs``) or Thornthwaite; runoff: ABCD, GWAM or none (AET / Q / Sav stay zero,
+    as the reference's arrays); routing when ``um`` is given.  Only the selected modules' arguments are needed."""
 
-    def __init__(self, ctx, *, ncell, nmonths, start_year, basin_ids, abcd_pars, pm_tables, lct, elev, lc_years,
-                 um, flow_dist, velocity, area, abcd_spinup, routing_spinup, water_idx=0, snow_idx=6, use_snow=True,
-                 route_flags=0, chs_prev=None, plan_async=False):
+    def __init__(self, ctx, *, ncell, nmonths, start_year, pet_module='pm', runoff_module='abcd',
+                 pm_tables=None, lct=None, elev=None, lc_years=(), water_idx=0, snow_idx=6,
+                 lat_radians=None, lat_degrees=None, daylight='reference',
+                 sm_max=None, sm0=None, gwam_spinup=0, precipitation='reference',
+                 basin_ids=None, abcd_pars=None, abcd_spinup=0, use_snow=True,
+                 um=None, flow_dist=None, velocity=None, area=None, routing_spinup=0, chs_prev=None, route_flags=0,
+                 plan_async=False):
+        if pet_module not in ('pm', 'hargreaves', 'hs', 'thornthwaite') or runoff_module not in ('abcd', 'gwam', 'none'):
+            raise ValueError("unknown pet_module '{}' or runoff_module '{}'".format(pet_module, runoff_module))
         self.ctx = ctx
         self.ncell, self.nmonths, self.start_year = int(ncell), int(nmonths), int(start_year)
         self.end_year = self.start_year + self.nmonths // 12 - 1
-        self.abcd_spinup, self.routing_spinup = int(abcd_spinup), int(routing_spinup)
-        self.water_idx, self.snow_idx, self.use_snow = water_idx, snow_idx, use_snow
-        self.lc_years = sorted(lc_years)
-        self.pm_tables = pm_tables
-        self.route_flags = route_flags
+        self.pet_module, self.runoff_module = pet_module, runoff_module
+        self.abcd_spinup, self.gwam_spinup, self.routing_spinup = int(abcd_spinup), int(gwam_spinup), int(routing_spinup)
+        self.use_snow, self.precipitation, self.route_flags = use_snow, precipitation, route_flags
+        self.ndays = set_month_arrays(self.nmonths, self.start_year, self.end_year)[:, 2]      # routing's days per month
+        self.forcing_names = MODULE_FORCING[pet_module] + MODULE_FORCING[runoff_module]
+        self._nan_to_num = NAN_TO_NUM.get(pet_module, ()) + NAN_TO_NUM.get(runoff_module, ())
+        self.forcing = {}
+        self.d_tairprev = None
+        self._setup_pet(pm_tables, lct, elev, lc_years, water_idx, snow_idx, lat_radians, lat_degrees, daylight)
+        if runoff_module == 'abcd':
+            self._setup_abcd(basin_ids, abcd_pars)
+        elif runoff_module == 'gwam':
+            self.d_sm_max, self.d_sm0 = ctx.upload(sm_max), ctx.upload(sm0)
+        self.out = {k: ctx.empty((self.ncell, self.nmonths)) for k in OUTPUTS}
+        if runoff_module == 'none':
+            for k in ('aet', 'q', 'sav'):
+                self.out[k].zero()
+        self.um = um
+        self.d_flow_dist = self.d_velocity = self.d_area = self.d_S0 = None
+        self._plan, self._plan_thread, self._plan_error = None, None, None
+        if um is not None:
+            self._setup_routing(flow_dist, velocity, area, chs_prev, plan_async)
+
+    def _setup_pet(self, pm_tables, lct, elev, lc_years, water_idx, snow_idx, lat_radians, lat_degrees, daylight):
+        up = self.ctx.upload
+        if self.pet_module == 'pm':
+            self.pm_tables, self.lc_years, self.water_idx, self.snow_idx = pm_tables, sorted(lc_years), water_idx, snow_idx
+            self.nlcs = len(pm_tables['cL'])                    # land-cover classes the PM kernel reads
+            self.d_lct = up(lct)
+            self.d_elev = up(np.asarray(elev, dtype=np.float64).reshape(-1))
+        elif self.pet_module == 'hs':                                 # latitude in degrees (hargreaves_samani.py:105)
+            if lat_degrees is None:
+                raise ValueError('Hargreaves-Samani PET needs lat_degrees')
+            self.hs_ndays = hs_mod.days_per_month(self.start_year, self.end_year)
+            self.d_lat = up(np.asarray(lat_degrees, dtype=np.float64).reshape(-1))
+        else:
+            if self.pet_module == 'hargreaves':
+                self.solar_dec, self.dr, self.ndays_f = hg_mod.month_factors(self.start_year, self.end_year)
+            else:
+                trn_mod.daylight_mode(daylight)                      # (a bad name fails here, not at run time)
+                self.daylight = daylight
+            self.d_lat = up(np.asarray(lat_radians, dtype=np.float64).reshape(-1))
+
+    def _setup_abcd(self, basin_ids, abcd_pars):
         basin_ids = np.asarray(basin_ids)
         uniq, inv = np.unique(basin_ids, return_inverse=True)
         self.basin_index = inv.astype(np.int32)
         self.n_groups = len(uniq)
         self.par_index = (basin_ids - 1).astype(np.int32)          # row of abcd_pars = basin id - 1 (abcd.py:332)
         self.npar_rows = int(np.asarray(abcd_pars).shape[0])
-        up = ctx.upload
-        self.d_pars = up(np.asarray(abcd_pars, dtype=np.float64))
-        self.d_lct = up(lct)
-        self.d_elev = up(np.asarray(elev, dtype=np.float64).reshape(-1))
-        self.um = um
+        self.d_pars = self.ctx.upload(np.asarray(abcd_pars, dtype=np.float64))
+
+    def _setup_routing(self, flow_dist, velocity, area, chs_prev, plan_async):
+        up, um, ctx = self.ctx.upload, self.um, self.ctx
         self.d_flow_dist, self.d_velocity, self.d_area = up(flow_dist), up(velocity), up(area)
         # initial channel storage (future mode, data_load.py:427-438); None = zeros
         self.d_S0 = up(chs_prev) if chs_prev is not None and np.any(np.asarray(chs_prev) != 0) else None
-        self.ndays = set_month_arrays(self.nmonths, self.start_year, self.end_year)[:, 2]
-        self.forcing = {}
-        self.d_tairprev = None
-        self.out = {k: ctx.empty((self.ncell, self.nmonths)) for k in OUTPUTS}
         # The routing plan (partition of the networks, 50-70 ms of host time at the full grid) touches neither the
-        # context's stream nor the arrays above; with plan_async it is made on a host thread while the caller uploads the
-        # forcing (run_model()), and `plan` waits for it.
-        self._plan, self._plan_thread, self._plan_error = None, None, None
-        if um is not None and plan_async:
-            import threading
+        # context's stream nor the arrays above; it is made on a host thread, and `plan` waits for it: with plan_async
+        # while the caller uploads the forcing (run_model()), otherwise at once.
 
-            def make():
-                try:
-                    self._plan = um.plan(ctx)
-                    self._plan.prepare(flow_dist, velocity, 10800.0)      # selective tables ahead of the first call, if known
-                except BaseException as exc:      # re-raised by `plan`
-                    self._plan_error = exc
-            self._plan_thread = threading.Thread(target=make, name='xh-route-plan')
-            self._plan_thread.start()
-        elif um is not None:
-            self._plan = um.plan(ctx)
-            self._plan.prepare(flow_dist, velocity, 10800.0)
+        def make():
+            try:
+                self._plan = um.plan(ctx)
+                self._plan.prepare(flow_dist, velocity, 10800.0)      # selective tables ahead of the first call, if known
+            except BaseException as exc:      # re-raised by `plan`
+                self._plan_error = exc
+        self._plan_thread = threading.Thread(target=make, name='xh-route-plan')
+        self._plan_thread.start()
+        if not plan_async:
+            self.plan
 
     @property
     def plan(self):
@@ -98,50 +145,64 @@ class DevicePipeline:
 
     # ---- forcing
     def alloc_forcing(self):
-        for k in FORCING:
+        for k in self.forcing_names:
             if k not in self.forcing:
                 self.forcing[k] = self.ctx.empty((self.ncell, self.nmonths))
         return self.forcing
 
     def set_forcing(self, host, tairprev=None):
-        """host: dict of [ncell, nmonths] arrays keyed by FORCING (abcd_tmin optional when use_snow is False).
-        A read-only memory map of a .npy (np.load(mmap_mode='r'), what DataLoader keeps) is copied straight out of the
-        mapping (no host copy: the runtime pins the page-cache pages); tairprev=None leaves the previous-cell temperature to the PM kernel (it reads the row
+        """host: dict of [ncell, nmonths] arrays keyed by the modules' forcing names (MODULE_FORCING; a missing or None
+        entry is left as it is, e.g. abcd_tmin when use_snow is False).  A read-only memory map of a .npy
+        (np.load(mmap_mode='r'), what DataLoader keeps) is copied straight out of the mapping (no host copy: the runtime
+        pins the page-cache pages); tairprev=None leaves PM's previous-cell temperature to the PM kernel (it reads the row
         above of ``tas``, data_load.py:127-128)."""
-        for k in FORCING:
-            if k in host and host[k] is not None:
-                src = host[k]
-                # XH_UPLOAD_FROM_FILE=1: through xh_upload_file (maps the file range itself: 34 GB/s with its own map /
-                # unmap per array); default: xh_memcpy_h2d out of numpy's mapping, which stays alive in the loader (51 GB/s)
-                where = file_range_of(src) if os.environ.get('XH_UPLOAD_FROM_FILE', '0') == '1' else None
-                direct = where is not None
-                arr = src if direct else np.asarray(src, dtype=np.float64)
-                if arr.shape != (self.ncell, self.nmonths):
-                    raise ValueError('forcing {} has shape {}, expected {}'.format(k, arr.shape,
-                                                                                   (self.ncell, self.nmonths)))
-                if k not in self.forcing:
-                    self.forcing[k] = self.ctx.empty((self.ncell, self.nmonths))
-                if direct:
-                    self.ctx.upload_file(self.forcing[k], where[0], where[1], src.nbytes)
-                else:
-                    self.forcing[k].upload(arr)
-                if k != 'precip':                       # loader transform: everything but precipitation loses its NaNs
-                    self.ctx.nan_to_num(self.forcing[k])
+        for k in self.forcing_names:
+            src = host.get(k)
+            if src is None:
+                continue
+            # XH_UPLOAD_FROM_FILE=1: through xh_upload_file (maps the file range itself: 34 GB/s with its own map /
+            # unmap per array); default: xh_memcpy_h2d out of numpy's mapping, which stays alive in the loader (51 GB/s)
+            where = file_range_of(src) if os.environ.get('XH_UPLOAD_FROM_FILE', '0') == '1' else None
+            arr = src if where is not None else np.asarray(src, dtype=np.float64)
+            if arr.shape != (self.ncell, self.nmonths):
+                raise ValueError('forcing {} has shape {}, expected {}'.format(k, arr.shape, (self.ncell, self.nmonths)))
+            if k not in self.forcing:
+                self.forcing[k] = self.ctx.empty((self.ncell, self.nmonths))
+            if where is not None:
+                self.ctx.upload_file(self.forcing[k], where[0], where[1], src.nbytes)
+            else:
+                self.forcing[k].upload(arr)
+            if k in self._nan_to_num:
+                self.ctx.nan_to_num(self.forcing[k])
         if tairprev is not None:
             self.d_tairprev = self.ctx.nan_to_num(self.ctx.upload(tairprev))
 
     # ---- stages (asynchronous; call ctx.sync() or download to wait)
-    def run_pm(self):
-        f = self.forcing
-        pm_mod.run_pmpet_device(self.ctx, self.pm_tables, self.ncell, self.start_year, self.end_year, self.water_idx,
-                                self.snow_idx, self.lc_years, f['tas'], f['tmin'], f['rhs'], f['wind'], f['rsds'],
-                                f['rlds'], self.d_tairprev, self.d_lct, self.d_elev, self.out['pet'])
+    def run_pet(self):
+        f, pet = self.forcing, self.out['pet']
+        if self.pet_module == 'pm':
+            pm_mod.run_pmpet_device(self.ctx, self.pm_tables, self.ncell, self.start_year, self.end_year, self.water_idx,
+                                    self.snow_idx, self.lc_years, f['tas'], f['tmin'], f['rhs'], f['wind'], f['rsds'],
+                                    f['rlds'], self.d_tairprev, self.d_lct, self.d_elev, pet)
+        elif self.pet_module == 'hargreaves':
+            hg_mod.hargreaves_device(self.ctx, self.ncell, self.nmonths, f['temp'], f['dtr'], self.d_lat, self.solar_dec,
+                                     self.dr, self.ndays_f, pet)
+        elif self.pet_module == 'hs':
+            hs_mod.hs_device(self.ctx, self.ncell, self.nmonths, f['tas'], f['tmax'], f['tmin'], self.d_lat, self.hs_ndays,
+                             pet)
+        else:
+            trn_mod.thornthwaite_device(self.ctx, self.ncell, self.nmonths, self.start_year, f['tas'], self.d_lat,
+                                        daylight=self.daylight, d_pet=pet)
 
-    def run_abcd(self):
-        f = self.forcing
-        self.ctx.abcd(self.ncell, self.nmonths, self.abcd_spinup, self.n_groups, self.basin_index, self.par_index,
-                      self.npar_rows, self.d_pars, self.out['pet'], f['precip'],
-                      f['abcd_tmin'] if self.use_snow else None, self.out['aet'], self.out['q'], self.out['sav'])
+    def run_runoff(self):
+        f, o = self.forcing, self.out
+        if self.runoff_module == 'abcd':
+            self.ctx.abcd(self.ncell, self.nmonths, self.abcd_spinup, self.n_groups, self.basin_index, self.par_index,
+                          self.npar_rows, self.d_pars, o['pet'], f['precip'], f['abcd_tmin'] if self.use_snow else None,
+                          o['aet'], o['q'], o['sav'])
+        elif self.runoff_module == 'gwam':
+            gwam_mod.gwam_device(self.ctx, self.ncell, self.nmonths, self.gwam_spinup, o['pet'], f['precip'], self.d_sm_max,
+                                 self.d_sm0, precipitation=self.precipitation, out={k: o[k] for k in ('aet', 'q', 'sav')})
 
     def run_mrtm(self, runoff=None):
         self.ctx.route_series(self.plan, self.nmonths, self.routing_spinup, self.ndays, 10800.0, self.d_flow_dist,
@@ -166,37 +227,57 @@ class DevicePipeline:
                            chs=self.out['chs'] if route else None, avg=self.out['avg'] if route else None,
                            route_flags=self.route_flags, block_months=block_months, mode=mode)
 
-    def run(self, stages=('pm', 'abcd', 'mrtm'), fused=None, fed=None, after_runoff=None):
-        """Enqueue the stages on the context's stream.  With all three stages the default is the FED order (xh_run_fused
-        mode 1): the first max(spin-ups) months of PM and ABCD, then the routing kernel, and the remaining
-        months of PM and ABCD beside it on a second stream -- identical results, the 2.8 ms of PM + ABCD mostly hidden
-        under the routing.  ``fed=False`` (or XH_FEED=0) runs the stages strictly one after the other; ``fused=True`` (or
-        XH_FUSED=1) is round 2's block pipeline of PM and ABCD with the routing behind it (slower on MI355X at the full grid).
+    def run(self, stages=None, fused=None, fed=None, after_runoff=None):
+        """Enqueue ``stages`` (default: the configured ones) on the context's stream, one after the other.  PM + ABCD has
+        two more orders.  With all three stages the default is the FED order (xh_run_fused mode 1): the first
+        max(spin-ups) months of PM and ABCD, then the routing kernel, and the remaining months of PM and ABCD beside it on
+        a second stream -- identical results, the 2.8 ms of PM + ABCD mostly hidden under the routing.  ``fed=False`` (or
+        XH_FEED=0) runs the stages strictly one after the other; ``fused=True`` (or XH_FUSED=1) is round 2's block pipeline
+        of PM and ABCD with the routing behind it (slower on MI355X at the full grid).
         ``after_runoff``: called once PET / AET / Q / Sav have been enqueued and before anything waits for the routing --
         the place for a side gather of the four arrays (dist.OutputGather.run_side)."""
-        if fused is None:
-            fused = os.environ.get('XH_FUSED') == '1'
-        if fed is None:
-            fed = os.environ.get('XH_FEED', FEED_DEFAULT) == '1'
-        whole_years = self.nmonths % 12 == 0
-        if fused and 'pm' in stages and 'abcd' in stages and whole_years:
-            self.run_fused(with_routing='mrtm' in stages, block_months=int(os.environ.get('XH_FUSED_BLOCK', '0')))
-            if after_runoff:
-                after_runoff()
-            return
-        if fed and all(s in stages for s in ('pm', 'abcd', 'mrtm')) and whole_years and self.plan is not None:
-            self.run_fused(with_routing=True, mode=1)
-            if after_runoff:      # the routing kernel is in the queue; a side gather waits for the runoff's side stream only
-                after_runoff()
-            return
-        if 'pm' in stages:
-            self.run_pm()
-        if 'abcd' in stages:
-            self.run_abcd()
+        if stages is None:
+            stages = (self.pet_module, self.runoff_module) + (('mrtm',) if self.um is not None else ())
+        if self.pet_module == 'pm' and self.runoff_module == 'abcd' and 'pm' in stages and 'abcd' in stages:
+            if fused is None:
+                fused = os.environ.get('XH_FUSED') == '1'
+            if fed is None:
+                fed = os.environ.get('XH_FEED', FEED_DEFAULT) == '1'
+            if fused or (fed and 'mrtm' in stages and self.plan is not None):
+                block = int(os.environ.get('XH_FUSED_BLOCK', '0')) if fused else 0
+                self.run_fused(with_routing='mrtm' in stages, block_months=block, mode=0 if fused else 1)
+                if after_runoff:      # the routing kernel is in the queue; a side gather waits for the runoff's side stream only
+                    after_runoff()
+                return
+        if self.pet_module in stages:
+            self.run_pet()
+        if self.runoff_module in stages:
+            self.run_runoff()
         if after_runoff:
             after_runoff()
         if 'mrtm' in stages:
             self.run_mrtm()
+
+    def stage_traffic(self):
+        """[(timer name, algorithmic bytes)] of the configured stages: what each kernel must move through HBM at the least
+        (PM 6 reads + 1 write + land cover, ABCD 3 + 3, MRTM 1 + 2)."""
+        n, cm = self.ncell, self.ncell * self.nmonths
+        if self.pet_module == 'pm':
+            stages = [('pm_pet', cm * 56 + n * (self.nmonths // 12) * self.nlcs * 8)]
+        elif self.pet_module == 'hargreaves':
+            stages = [('hargreaves_pet', cm * 24)]
+        elif self.pet_module == 'hs':
+            stages = [('hs_pet', cm * 32)]
+        else:
+            stages = [('trn_daylight', n * 24 * 8), ('trn_pet', cm * 16)]
+        if self.runoff_module == 'abcd':
+            stages += [('abcd_spinup', n * self.abcd_spinup * 24), ('abcd_sim', cm * 48)]
+        elif self.runoff_module == 'gwam':
+            stages += [('gwam_spinup', n * self.gwam_spinup * 16),
+                       ('gwam_sim', cm * (40 if self.precipitation == 'monthly' else 32))]
+        if self.um is not None:
+            stages.append(('mrtm_route', cm * 24 + n * self.routing_spinup * 8))
+        return stages
 
     def download(self, names=OUTPUTS):
         return {k: self.out[k].download() for k in names}
@@ -242,126 +323,3 @@ def pipeline_from_world(ctx, world, nmonths, start_year, abcd_spinup, routing_sp
                           abcd_pars=world.abcd_pars, pm_tables=tables, lct=world.lct, elev=world.elev,
                           lc_years=world.lc_years, um=um, flow_dist=world.flow_dist, velocity=world.velocity,
                           area=world.area, abcd_spinup=abcd_spinup, routing_spinup=routing_spinup, **kw)
-
-
-class HgmPipeline:
-    """Hargreaves, Hargreaves-Samani (``hs``) or Thornthwaite PET -> GWAM or ABCD runoff (-> MRTM) for the whole grid on one
-    GPU: the device-resident path of the reference's hargreaves_gwam_mrtm, hargreaves_abcd_mrtm, hs_abcd_mrtm and
-    thornthwaite_abcd_mrtm configurations.  Like DevicePipeline it owns the six output arrays in HBM (``out``) and
-    enqueues the stages on the context's stream; nothing crosses PCIe between them."""
-
-    PET_MODULES = ('hargreaves', 'hs', 'thornthwaite')
-
-    def __init__(self, ctx, *, ncell, nmonths, start_year, runoff_module, lat_radians, pet_module='hargreaves',
-                 lat_degrees=None, daylight='reference', um=None, flow_dist=None, velocity=None, area=None,
-                 routing_spinup=0, chs_prev=None, route_flags=0, sm_max=None, sm0=None, gwam_spinup=0,
-                 precipitation='reference', basin_ids=None, abcd_pars=None, abcd_spinup=0, use_snow=False):
-        from .pet import hargreaves as hg_mod, hargreaves_samani as hs_mod, thornthwaite as trn_mod
-        if pet_module not in self.PET_MODULES:
-            raise ValueError("pet_module must be one of {}, not '{}'".format(self.PET_MODULES, pet_module))
-        self.ctx = ctx
-        self.ncell, self.nmonths, self.start_year = int(ncell), int(nmonths), int(start_year)
-        self.end_year = self.start_year + self.nmonths // 12 - 1
-        self.runoff_module, self.pet_module = runoff_module, pet_module
-        # routing's days per month (general.py set_month_arrays) whatever the PET module's own calendar
-        self.solar_dec, self.dr, self.ndays_f = hg_mod.month_factors(self.start_year, self.end_year)
-        self.ndays = self.ndays_f.astype(np.int32)
-        up = ctx.upload
-        if pet_module == 'hs':                                   # latitude in degrees (hargreaves_samani.py:105)
-            if lat_degrees is None:
-                raise ValueError('Hargreaves-Samani PET needs lat_degrees')
-            self.hs_ndays = hs_mod.days_per_month(self.start_year, self.end_year)
-            self.d_lat = up(np.asarray(lat_degrees, dtype=np.float64).reshape(-1))
-        else:
-            self.daylight = daylight
-            trn_mod.daylight_mode(daylight)                      # (a bad name fails here, not at run time)
-            self.d_lat = up(np.asarray(lat_radians, dtype=np.float64).reshape(-1))
-        self.gwam_spinup, self.precipitation = int(gwam_spinup), precipitation
-        self.abcd_spinup, self.use_snow = int(abcd_spinup), use_snow
-        if runoff_module == 'gwam':
-            self.d_sm_max, self.d_sm0 = up(sm_max), up(sm0)
-        elif runoff_module == 'abcd':
-            basin_ids = np.asarray(basin_ids)
-            self.basin_index = np.unique(basin_ids, return_inverse=True)[1].astype(np.int32)
-            self.n_groups = int(self.basin_index.max()) + 1 if self.ncell else 0
-            self.par_index = (basin_ids - 1).astype(np.int32)           # row of abcd_pars = basin id - 1 (abcd.py:332)
-            self.npar_rows = int(np.asarray(abcd_pars).shape[0])
-            self.d_pars = up(np.asarray(abcd_pars, dtype=np.float64))
-        self.forcing = {}
-        self.out = {k: ctx.empty((self.ncell, self.nmonths)) for k in OUTPUTS}
-        if runoff_module not in ('gwam', 'abcd'):             # PET only: no runoff, as the reference's zero arrays
-            for k in ('aet', 'q', 'sav'):
-                self.out[k].zero()
-        self.route_flags = route_flags
-        self.routing_spinup = int(routing_spinup)
-        self._plan = None
-        if um is not None:
-            self.d_flow_dist, self.d_velocity, self.d_area = up(flow_dist), up(velocity), up(area)
-            self.d_S0 = up(chs_prev) if chs_prev is not None and np.any(np.asarray(chs_prev) != 0) else None
-            self._plan = um.plan(ctx)
-            self._plan.prepare(flow_dist, velocity, 10800.0)
-
-    @property
-    def plan(self):
-        return self._plan
-
-    def set_forcing(self, host):
-        """host: the PET module's forcing -- 'temp', 'dtr' (Hargreaves), 'tas', 'tmax', 'tmin' (Hargreaves-Samani) or 'tas'
-        (Thornthwaite) -- (+ 'precip', + 'abcd_tmin' with ABCD and snow) as [ncell, nmonths] arrays or memory maps.
-        Hargreaves' and Hargreaves-Samani's forcing goes up as it is (the kernels clean it or keep NaN as the reference
-        does), precipitation keeps NaN, Thornthwaite's tas and ABCD's tmin pass through nan_to_num (data_load.py:137-138,
-        :194-195)."""
-        for k, src in host.items():
-            if src is None:
-                continue
-            arr = np.asarray(src, dtype=np.float64)
-            if arr.shape != (self.ncell, self.nmonths):
-                raise ValueError('forcing {} has shape {}, expected {}'.format(k, arr.shape, (self.ncell, self.nmonths)))
-            if k not in self.forcing:
-                self.forcing[k] = self.ctx.empty((self.ncell, self.nmonths))
-            self.forcing[k].upload(arr)
-            if k == 'abcd_tmin' or (k == 'tas' and self.pet_module == 'thornthwaite'):
-                self.ctx.nan_to_num(self.forcing[k])
-
-    def run_hargreaves(self):
-        f = self.forcing
-        self.ctx.hargreaves_pet(self.ncell, self.nmonths, f['temp'], f['dtr'], self.d_lat, self.solar_dec, self.dr,
-                                self.ndays_f, self.out['pet'])
-
-    def run_pet(self):
-        f = self.forcing
-        if self.pet_module == 'hargreaves':
-            self.run_hargreaves()
-        elif self.pet_module == 'hs':
-            self.ctx.hs_pet(self.ncell, self.nmonths, f['tas'], f['tmax'], f['tmin'], self.d_lat, self.hs_ndays,
-                            self.out['pet'])
-        else:
-            from .pet import thornthwaite as trn_mod
-            trn_mod.thornthwaite_device(self.ctx, self.ncell, self.nmonths, self.start_year, f['tas'], self.d_lat,
-                                        daylight=self.daylight, d_pet=self.out['pet'])
-
-    def run_gwam(self):
-        from .runoff import gwam as gwam_mod
-        gwam_mod.gwam_device(self.ctx, self.ncell, self.nmonths, self.gwam_spinup, self.out['pet'], self.forcing['precip'],
-                             self.d_sm_max, self.d_sm0, precipitation=self.precipitation,
-                             out={k: self.out[k] for k in ('aet', 'q', 'sav')})
-
-    def run_abcd(self):
-        f = self.forcing
-        self.ctx.abcd(self.ncell, self.nmonths, self.abcd_spinup, self.n_groups, self.basin_index, self.par_index,
-                      self.npar_rows, self.d_pars, self.out['pet'], f['precip'], f['abcd_tmin'] if self.use_snow else None,
-                      self.out['aet'], self.out['q'], self.out['sav'])
-
-    def run_mrtm(self):
-        self.ctx.route_series(self._plan, self.nmonths, self.routing_spinup, self.ndays, 10800.0, self.d_flow_dist,
-                              self.d_velocity, self.d_area, self.out['q'], self.d_S0, self.out['chs'], self.out['avg'],
-                              flags=self.route_flags)
-
-    def run(self):
-        self.run_pet()
-        if self.runoff_module == 'gwam':
-            self.run_gwam()
-        elif self.runoff_module == 'abcd':
-            self.run_abcd()
-        if self._plan is not None:
-            self.run_mrtm()
