@@ -789,6 +789,32 @@ def test_prepared_plan_notices_new_velocities_in_place(hip):
         assert pipe.plan.info()['last_tree_kernel'] == 4 and ri['fold_disabled'] == 1 and ri['pair_cells'] == -1, (fed, ri)
 
 
+def test_guard_trip_bans_the_prepared_plan_with_another_call_behind_it(hip, tmp_path, monkeypatch):
+    """A guard trip of the prepared plan bans it by the record of the call that tripped, not by whatever call of the plan was
+    enqueued last: here one without the dataflow kernels follows it before the synchronisation, which reports the work that
+    read the invalid outputs and leaves the prepared plan switched off."""
+    from xanthos_amd import synth
+    from xanthos_amd.pipeline import pipeline_from_world
+    monkeypatch.setenv('XH_CACHE_DIR', str(tmp_path / 'cache'))
+    ctx = hip.get_context()
+    w = synth.make_world(nrow=60, ncol=120, ncell=3000, n_basins=7, seed=29, outlet_frac=0.02)
+    nm = 48
+    pipe = pipeline_from_world(ctx, w, nm, 1971, 25, 12)
+    ctx.synth_forcing(31, w.ncell, nm, ctx.upload(w.latitude), pipe.alloc_forcing(), nan_frac=0.002)
+    pipe.run(fed=False)          # a clean call first: its first-call cross-check synchronises, the calls below must not
+    ri = pipe.plan.rsum_info()
+    assert pipe.plan.info()['last_tree_kernel'] == 4 and ri['pair_cells'] >= 0 and ri['fold_disabled'] == 0, ri
+    q = pipe.out['q'].download()
+    q[np.nonzero(np.diff(pipe.um.indptr) == 1)[0], 5] = -3.0      # negative runoff in the leaves' rows: the guard trips
+    d_q = ctx.upload(q)
+    for flags in (0, hip.XH_ROUTE_NO_DATAFLOW):
+        ctx.route_series(pipe.plan, nm, 12, pipe.ndays, 10800.0, pipe.d_flow_dist, pipe.d_velocity, pipe.d_area, d_q, None,
+                         pipe.out['chs'], pipe.out['avg'], None, None, flags)
+    with pytest.raises(hip.HipError):
+        ctx.sync()
+    assert pipe.plan.rsum_info()['fold_disabled'] == 1
+
+
 def test_first_dataflow_call_of_a_plan_is_cross_checked(hip, tmp_path, monkeypatch):
     """The dataflow kernels' streams rest on an ordering assumption outside the HIP memory model (xh_mrtm_wave.hip, check();
     the fenced form costs +86 %, profiles/round4/fenced_ab.txt).  So the FIRST dataflow call of a plan on a device / library
@@ -835,6 +861,21 @@ def test_first_dataflow_call_of_a_plan_is_cross_checked(hip, tmp_path, monkeypat
     mrtm.route_series(um4, w.flow_dist, w.velocity, w.area, runoff, ndays, 2)
     assert um4.plan(hip.get_context()).info()['validated'] == 1
     monkeypatch.delenv('XH_TEST_RUNTIME_TAG')
+    # the prepared form's marker also names its partition: a plan of the same topology prepared for velocities under which
+    # other cells can fire is cross-checked again, and leaves a second marker of the same (single-sum) form
+    ratio = w.velocity * 10800.0 / w.flow_dist
+    slow = np.nonzero(ratio <= 1.0)[0][::7]
+    v2 = w.velocity.copy()
+    v2[slow] *= 3.0 / np.maximum(ratio[slow], 0.05)
+    before = {f.name for f in (tmp_path / 'cache').iterdir() if f.name.startswith('route_ok_')}
+    um6 = fresh()
+    ref2 = o_mrtm.route_series(um6.tocsr(), w.flow_dist, v2, w.area, runoff, ndays, 2)
+    got = mrtm.route_series(um6, w.flow_dist, v2, w.area, runoff, ndays, 2)
+    for a, b, atol in zip(got, ref2, (1e-3, 1e-9, 1e-9)):
+        routed_close(a, b, atol)
+    assert um6.plan(hip.get_context()).info()['validated'] == 1
+    new = {f.name for f in (tmp_path / 'cache').iterdir() if f.name.startswith('route_ok_')} - before
+    assert len(new) == 1 and marks[0].name.endswith('_rs') and new.pop().endswith('_rs'), (marks, new)
     # ... and a long-lived plan is cross-checked again every XH_ROUTE_VALIDATE_EVERY-th dataflow call (default 1,000)
     monkeypatch.setenv('XH_ROUTE_VALIDATE_EVERY', '3')
     um5 = fresh()

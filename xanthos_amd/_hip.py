@@ -601,9 +601,10 @@ class RoutePlan:
 
     def prepare(self, flow_dist, velocity, dt):
         """xh_route_plan_prepare: host copies of flow distance and velocity [ncell] and dt.  Makes the PREPARED plan of the
-        default (reassociated) routing form -- folded leaves, single running sums: both rest on which cells can fire -- or, for
-        the bit-exact form, the selective plain tables when this box has learnt the grid's firing cells before.  May be
-        called again: the same data is a cheap no-op, other data replaces the prepared plan."""
+        default (reassociated) routing form -- folded leaves, single running sums: both rest on which cells can fire -- which
+        calls with this dt then route on; a no-op in a process whose default form is the bit-exact one.  May be called again:
+        the same data is a cheap no-op, data that changes which cells can fire replaces the prepared plan (and lifts a guard
+        trip's ban on the old one)."""
         L = np.ascontiguousarray(flow_dist, dtype=np.float64)
         v = np.ascontiguousarray(velocity, dtype=np.float64)
         if L.size != self.ncell or v.size != self.ncell:

@@ -26,11 +26,38 @@ static inline std::string xh_cache_dir() {      // per-box cache of partitions a
 static inline bool xh_plan_cache_on() { return xh_env_on("XH_ROUTE_LEARN_CACHE", true); }      // partitions kept per box
 static inline bool xh_flow_debug() { return getenv("XH_FLOW_DEBUG") != nullptr; }               // partition statistics on stderr
 static inline bool xh_flow_check() { return getenv("XH_FLOW_CHECK") != nullptr; }               // planner invariants on every plan
+// <xh_cache_dir()>/<name>, or "" without a cache directory; for_write: its directories are made first (mkdir -p)
+std::string xh_cache_path(const char *name, bool for_write);
+
+// FNV-1a over bytes, continuing from `h`: the keys of the per-box cache (partitions, first-call markers) and of the month
+// records on the device
+constexpr uint64_t XH_FNV_BASIS = 1469598103934665603ull;
+static inline uint64_t xh_fnv1a(uint64_t h, const void *p, size_t n) {
+    const unsigned char *b = static_cast<const unsigned char *>(p);
+    for (size_t i = 0; i < n; ++i) h = (h ^ b[i]) * 1099511628211ull;
+    return h;
+}
+static inline uint64_t xh_fnv1a(uint64_t h, const char *s) { return xh_fnv1a(h, s, strlen(s)); }
 
 struct xh_timer_slot {
     double done_ms = 0.0;
     int64_t launches = 0;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
+};
+
+// The partitions of a routing plan's tree networks, one per form (xh_mrtm_plan.h): the bit-exact kernels', the reassociated
+// kernel's with every unit in pair form, and the PREPARED one (folded leaves, single sums: xh_route_plan_prepare).
+enum xh_route_form { XH_FORM_EXACT = 0, XH_FORM_PAIRS = 1, XH_FORM_PREPARED = 2, XH_N_FORMS = 3 };
+
+struct FlowPlan;
+// What one routing call ran (route_series_impl): the plan's "last call" that xh_route_plan_info / rsum_info / stats report,
+// and what a record needs to know of it.
+struct xh_route_outcome {
+    int kernel = 0;                  // xh_route_plan_info[13]: 0 no dataflow kernel, 1 lock-step, 2 time-skewed, 4 reassociated
+    int form = XH_FORM_EXACT;        // the form of the partition that ran (XH_FORM_EXACT when none did)
+    const FlowPlan *fp = nullptr;    // that partition (nullptr: none); a re-prepare may replace it, so records go by `key`
+    uint64_t key = 0;                // XH_FORM_PREPARED: the plan's prep_key when the call ran
+    unsigned *place = nullptr;       // placement words of the time-skewed launch (printed by xh_fault_check after a timeout)
 };
 
 // A routing call that ran on the dataflow kernels and has not been confirmed fault-free by a synchronisation yet.
@@ -46,6 +73,7 @@ struct xh_route_record {
     double *chs = nullptr, *avg = nullptr, *S_end = nullptr, *F_end = nullptr;
     uint64_t seq_after = 0;        // ctx->work_seq right after the call was enqueued
     bool fed = false;              // routed while the side stream still produced its runoff (xh_run_fused mode 1)
+    xh_route_outcome ran;          // what the call ran on
 };
 int xh_route_rerun(xh_ctx *ctx, const xh_route_record &r, bool dataflow_pairs);      // xh_mrtm.hip: workgroup per network, or the dataflow kernel with every unit in pair form
 void xh_route_confirm(const xh_route_record &r);                // xh_mrtm.hip: the call's dataflow kernel ran fault-free

@@ -1,5 +1,6 @@
 // Context, device memory, row gather/scatter, transpose and HIP-event timing for libxanthos_hip.so.
 #include <dlfcn.h>
+#include <sys/stat.h>
 
 #include <algorithm>
 #include <cstdlib>
@@ -24,6 +25,15 @@ int xh_fail(xh_ctx *ctx, int code, const char *fmt, ...) {
     else
         g_xh_create_error = buf;
     return code;
+}
+
+std::string xh_cache_path(const char *name, bool for_write) {
+    const std::string dir = xh_cache_dir();
+    if (dir.empty()) return dir;
+    if (for_write)
+        for (size_t i = 1; i <= dir.size(); ++i)
+            if (i == dir.size() || dir[i] == '/') (void)mkdir(dir.substr(0, i).c_str(), 0755);
+    return dir + "/" + name;
 }
 
 int xh_scratch(xh_ctx *ctx, int which, size_t bytes, void **out) {
@@ -114,12 +124,14 @@ int xh_fault_check(xh_ctx *ctx) {
         fprintf(stderr, "[libxanthos_hip] routing fault %u (a bounded wait between routing units timed out: the device is "
                 "shared and the units were not all resident); re-routing %zu call(s) with one workgroup per network\n",
                 code, pending.size());
-        {
-            extern unsigned *xh_wave_last_place();
+        // (diagnosis only: the copy fails harmlessly if the partition has been replaced since, and leaves no error behind for
+        // the re-routes below to report)
+        if (unsigned *place = pending.empty() ? nullptr : pending.back().ran.place) {
             unsigned w[16] = {0};
-            if (xh_wave_last_place() && hipMemcpy(w, xh_wave_last_place(), sizeof(w), hipMemcpyDeviceToHost) == hipSuccess)
+            if (hipMemcpy(w, place, sizeof(w), hipMemcpyDeviceToHost) == hipSuccess)
                 fprintf(stderr, "[libxanthos_hip]   placement words: registered %u seconds %u firsts %u t3 %u decided4 %u c5 %u c6 %u t7 %u | leaders %u t10 %u displaced %u decided12 %u claimed13 %u\n",
                         w[0], w[1], w[2], w[3], w[4], w[5], w[6], w[7], w[9], w[10], w[11], w[12], w[13]);
+            (void)hipGetLastError();
         }
         if (ctx->d_feed) {      // a fed call (xh_run_fused mode 1): how far the side stream had come
             unsigned w[48] = {0};

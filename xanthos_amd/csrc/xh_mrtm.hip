@@ -408,90 +408,69 @@ static int reassoc_env() {
     }();
     return v;
 }
-bool reassoc_wanted(int flags) {
+static bool reassoc_wanted(int flags) {
     if (flags & XH_ROUTE_EXACT) return false;
     if (flags & XH_ROUTE_REASSOC) return true;
     return reassoc_env() >= 0 ? reassoc_env() == 1 : XH_REASSOC_DEFAULT != 0;
 }
 
 // The reassociated partition of the plan's tree networks, from the per-box cache or from the host planner
-// (xh_flow_rsum.cpp).  `foldable` (or nullptr): the leaves the parents' lanes may carry (FlowPlanOptions::foldable).  The
-// partition of a grid is the same every time (topology, planner options, foldable set, library build): it is kept in the
-// cache beside the bit-exact one (flow_plan_build) and held to the planner's own invariant checker before it is used.
-// False: the planner has nothing for this grid.
-static bool rsum_tables_get(xh_ctx *ctx, xh_route_plan *plan, const unsigned char *foldable, const unsigned char *capable,
-                            FlowTables &t, std::vector<char> &handled) {
+// (xh_flow_rsum.cpp), uploaded into *out.  `foldable` / `capable` (or nullptr): the leaves the parents' lanes may carry, the
+// cells that can fire (FlowPlanOptions).  The partition of a grid is the same every time (topology, planner options, sets,
+// library build): it is kept in the cache beside the bit-exact one (flow_plan_build) and held to the planner's own invariant
+// checker before it is used.  *out stays nullptr when the planner has nothing for this grid -- or, given the sets, nothing to
+// fold or single out.
+static int rsum_partition(xh_ctx *ctx, xh_route_plan *plan, const unsigned char *foldable, const unsigned char *capable,
+                          FlowPlan **out) {
     std::string err;
     FlowPlanOptions opt = flow_plan_options(ctx);
     opt.foldable = foldable;
     opt.capable = capable;
     if (const char *e = getenv("XH_RSUM_HALO")) opt.halo = std::max(atoi(e), 0);      // cells in pair form below a cell that may leave negative storage
-    std::string cache;
+    char name[96] = "";
     if (xh_plan_cache_on() && !opt.debug) {
-        const std::string dir = xh_cache_dir();
-        if (!dir.empty()) {
-            uint64_t h = plan->topo_hash;
-            // (the planner's own version: a planner-only rebuild must not find the partitions of the one before it)
-            const int knobs[5] = {opt.simds, opt.piece_cap, opt.halo, opt.pair_imports, flow_rsum_planner_version()};
-            for (size_t i = 0; i < sizeof(knobs); ++i) h = (h ^ reinterpret_cast<const unsigned char *>(knobs)[i]) * 1099511628211ull;
-            for (const char *b = __DATE__ " " __TIME__; *b; ++b) h = (h ^ (unsigned char)*b) * 1099511628211ull;
-            for (const unsigned char *set : {foldable, capable}) {
-                h = (h ^ (set ? 1u : 0u)) * 1099511628211ull;
-                if (set)
-                    for (int64_t c = 0; c < plan->ncell; ++c) h = (h ^ set[c]) * 1099511628211ull;
-            }
-            char name[96];
-            snprintf(name, sizeof(name), "/rsum%s%s_%016llx_%lld.tables", foldable ? "f" : "", capable ? "s" : "", (unsigned long long)h,
-                     (long long)plan->ncell);
-            cache = dir + name;
+        // (the planner's own version: a planner-only rebuild must not find the partitions of the one before it)
+        const int knobs[5] = {opt.simds, opt.piece_cap, opt.halo, opt.pair_imports, flow_rsum_planner_version()};
+        uint64_t h = xh_fnv1a(xh_fnv1a(plan->topo_hash, knobs, sizeof(knobs)), __DATE__ " " __TIME__);
+        for (const unsigned char *set : {foldable, capable}) {
+            const unsigned char given = set ? 1 : 0;
+            h = xh_fnv1a(h, &given, 1);
+            if (set) h = xh_fnv1a(h, set, (size_t)plan->ncell);
         }
+        snprintf(name, sizeof(name), "rsum%s%s_%016llx_%lld.tables", foldable ? "f" : "", capable ? "s" : "", (unsigned long long)h,
+                 (long long)plan->ncell);
     }
-    if (!cache.empty() && flow_tables_load(cache.c_str(), t) && t.rsum && t.n_units > 0 &&
-        (int64_t)t.cell_of_slot.size() == (int64_t)t.n_units * 64 && (foldable || t.n_folded == 0) && (capable || t.n_special < 0)) {
-        handled.assign((size_t)plan->ncell, 0);
-        bool ok = true;
-        auto take = [&](int c) {
-            if (c >= plan->ncell) ok = false;
-            else if (c >= 0) handled[c] = 1;
-        };
-        for (int c : t.cell_of_slot) take(c);
-        for (int c : t.fold_of_slot) take(c);
-        if (ok && flow_tables_check_rsum((int)plan->ncell, plan->h_indptr.data(), plan->h_indices.data(), plan->h_sign.data(),
-                                         handled, t).empty())
-            return true;
-        t = FlowTables();
-    }
-    if (flow_tables_build_rsum((int)plan->ncell, plan->h_indptr.data(), plan->h_indices.data(), plan->h_sign.data(),
-                               plan->h_comp.data(), plan->h_ncomp, opt, handled, t, err) != 0 || t.n_units == 0)
-        return false;
-    if (!cache.empty()) {
-        const std::string dir = cache.substr(0, cache.rfind('/'));
-        for (size_t i = 1; i <= dir.size(); ++i)      // mkdir -p
-            if (i == dir.size() || dir[i] == '/') (void)mkdir(dir.substr(0, i).c_str(), 0755);
-        (void)flow_tables_save(t, cache.c_str());
-    }
-    return true;
-}
-
-// The reassociated plan (host planner + upload).  XH_OK with plan->flow_rsum == nullptr and rsum_failed set when the planner
-// has nothing for this grid; the call then takes the bit-exact path.
-static int rsum_plan_build(xh_ctx *ctx, xh_route_plan *plan) {
-    if (plan->flow_rsum || plan->rsum_failed) return XH_OK;
-    plan->rsum_failed = true;
-    if (!plan->flow || plan->h_indptr.empty()) return XH_OK;
+    auto build = [&](FlowTables &bt, std::vector<char> &bh) {
+        return flow_tables_build_rsum((int)plan->ncell, plan->h_indptr.data(), plan->h_indices.data(), plan->h_sign.data(),
+                                      plan->h_comp.data(), plan->h_ncomp, opt, bh, bt, err);
+    };
     std::vector<char> handled;
     FlowTables t;
-    if (!rsum_tables_get(ctx, plan, nullptr, nullptr, t, handled)) return XH_OK;
-    if (t.n_cells != plan->flow->n_cells) return XH_OK;      // must route exactly the cells the bit-exact plan routes
+    if (flow_tables_cached(name[0] ? name : nullptr, (int)plan->ncell, plan->h_indptr.data(), plan->h_indices.data(),
+                           plan->h_sign.data(), true, foldable != nullptr, capable != nullptr, t, handled, build) != 0 ||
+        t.n_units == 0 || ((foldable || capable) && t.n_folded == 0 && t.n_special < 0))
+        return XH_OK;
+    if (t.n_cells != plan->form[XH_FORM_EXACT].fp->n_cells) return XH_OK;      // must route exactly the cells the bit-exact plan routes
     if (xh_flow_check()) {
         const std::string bad = flow_tables_check_rsum((int)plan->ncell, plan->h_indptr.data(), plan->h_indices.data(),
                                                        plan->h_sign.data(), handled, t);
-        if (!bad.empty()) return xh_fail(ctx, XH_ERR_ARG, "reassociated flow plan check: %s", bad.c_str());
+        if (!bad.empty())
+            return xh_fail(ctx, XH_ERR_ARG, "reassociated flow plan check%s: %s", foldable || capable ? " (prepared plan)" : "",
+                           bad.c_str());
     }
-    const int rc = flow_plan_upload(ctx, t, &plan->flow_rsum);
-    if (rc) return rc;
-    plan->rsum_failed = plan->flow_rsum == nullptr;
-    return XH_OK;
+    return flow_plan_upload(ctx, t, out);
+}
+
+// The reassociated plan of pairs (host planner + upload).  XH_OK with no XH_FORM_PAIRS partition and rsum_failed set when the
+// planner has nothing for this grid; the call then takes the bit-exact path.
+static int rsum_plan_build(xh_ctx *ctx, xh_route_plan *plan) {
+    FlowPlan *&fp = plan->form[XH_FORM_PAIRS].fp;
+    if (fp || plan->rsum_failed) return XH_OK;
+    plan->rsum_failed = true;
+    if (!plan->form[XH_FORM_EXACT].fp || plan->h_indptr.empty()) return XH_OK;
+    const int rc = rsum_partition(ctx, plan, nullptr, nullptr, &fp);
+    plan->rsum_failed = fp == nullptr;
+    return rc;
 }
 
 extern "C" int xh_route_plan_create(xh_ctx *ctx, int64_t ncell, const int64_t *h_indptr, const int32_t *h_indices,
@@ -556,27 +535,20 @@ extern "C" int xh_route_plan_create(xh_ctx *ctx, int64_t ncell, const int64_t *h
     plan->largest_network = ncomp ? *std::max_element(comp_size.begin(), comp_size.end()) : 0;
 
     lap("validation + components");
+    // the topology: the key of the partitions in the per-box cache and of the first-call markers
+    plan->topo_hash = xh_fnv1a(XH_FNV_BASIS, h_indptr, sizeof(int64_t) * (size_t)(n + 1));
+    if (nnz) plan->topo_hash = xh_fnv1a(xh_fnv1a(plan->topo_hash, h_indices, sizeof(int32_t) * (size_t)nnz), h_sign, (size_t)nnz);
     // ---- tree-shaped networks also get a dataflow layout (xh_mrtm_flow.hip)
     std::vector<char> flow_cell;
     {
-        const int frc = flow_plan_build(ctx, n, h_indptr, h_indices, h_sign, comp, ncomp, flow_cell, &plan->flow);
+        const int frc = flow_plan_build(ctx, n, h_indptr, h_indices, h_sign, plan->topo_hash, comp, ncomp, flow_cell,
+                                        &plan->form[XH_FORM_EXACT].fp);
         if (frc) {
             route_plan_free(plan, false);
             return frc;
         }
         if (flow_cell.empty()) flow_cell.assign(n, 0);
-        if (plan->flow) {
-            {
-                uint64_t h = 1469598103934665603ull;      // FNV-1a over the CSR structure
-                auto mix = [&](const void *p, size_t nbytes) {
-                    const unsigned char *b = static_cast<const unsigned char *>(p);
-                    for (size_t i = 0; i < nbytes; ++i) h = (h ^ b[i]) * 1099511628211ull;
-                };
-                mix(h_indptr, sizeof(int64_t) * (size_t)(n + 1));
-                if (nnz) mix(h_indices, sizeof(int32_t) * (size_t)nnz);
-                if (nnz) mix(h_sign, (size_t)nnz);
-                plan->topo_hash = h;
-            }
+        if (plan->form[XH_FORM_EXACT].fp) {
             plan->h_indptr.assign(h_indptr, h_indptr + n + 1);
             plan->h_indices.assign(h_indices, h_indices + nnz);
             plan->h_sign.assign(h_sign, h_sign + nnz);
@@ -694,71 +666,51 @@ extern "C" int xh_route_plan_create(xh_ctx *ctx, int64_t ncell, const int64_t *h
     }
 
     lap("workgroup units + slots");
-    // ---- fallback CSR (subset) and whole-graph CSR
-    auto build_csr = [&](const std::vector<int> &cells, std::vector<int> &ptr, std::vector<int> &col,
-                         std::vector<signed char> &sgn, std::vector<int> &ds, bool &single) {
-        ptr.assign(cells.size() + 1, 0);
-        col.clear();
-        sgn.clear();
-        for (size_t i = 0; i < cells.size(); ++i) {
-            const int c = cells[i];
+    // ---- fallback CSR: every cell, the cells no workgroup unit routes, and those of them the dataflow kernels do not route
+    // downstream cell of each cell = the row in which it appears with +1 (atomic variant needs exactly <= 1, and every row's
+    // only negative term on its diagonal)
+    std::vector<int> ds_cell(n, -1);
+    bool single_ds = true;
+    for (int r = 0; r < n; ++r) {
+        int ndiag = 0;
+        for (int64_t j = h_indptr[r]; j < h_indptr[r + 1]; ++j) {
+            const int c = h_indices[j];
+            if (h_sign[j] > 0) {
+                if (ds_cell[c] >= 0) single_ds = false;
+                ds_cell[c] = r;
+            } else if (c != r) {
+                single_ds = false;
+            } else {
+                ++ndiag;
+            }
+        }
+        if (ndiag != 1) single_ds = false;
+    }
+    int rc = XH_OK;
+    UploadPool pool;
+    std::vector<int> all(n);
+    std::iota(all.begin(), all.end(), 0);
+    const std::pair<FbCsr *, const std::vector<int> *> sets[3] = {{&plan->fb, &fb_cells}, {&plan->fb_rest, &fb_rest_cells},
+                                                                   {&plan->fb_all, &all}};
+    for (const auto &[f, cells] : sets) {
+        std::vector<int> ptr(cells->size() + 1, 0), col, ds(cells->size());
+        std::vector<signed char> sgn;
+        for (size_t i = 0; i < cells->size(); ++i) {
+            const int c = (*cells)[i];
             for (int64_t j = h_indptr[c]; j < h_indptr[c + 1]; ++j) {
                 col.push_back(h_indices[j]);
                 sgn.push_back((signed char)h_sign[j]);
             }
             ptr[i + 1] = (int)col.size();
+            ds[i] = ds_cell[c];
         }
-        // downstream cell of each cell = the row in which it appears with +1 (atomic variant needs exactly <= 1,
-        // and every row's only negative term on its diagonal)
-        std::vector<int> ds_cell(n, -1);
-        single = true;
-        for (int r = 0; r < n; ++r)
-            for (int64_t j = h_indptr[r]; j < h_indptr[r + 1]; ++j) {
-                const int c = h_indices[j];
-                if (h_sign[j] > 0) {
-                    if (ds_cell[c] >= 0) single = false;
-                    ds_cell[c] = r;
-                } else if (c != r) {
-                    single = false;
-                }
-            }
-        for (int r = 0; r < n; ++r) {
-            int ndiag = 0;
-            for (int64_t j = h_indptr[r]; j < h_indptr[r + 1]; ++j)
-                if (h_indices[j] == r && h_sign[j] < 0) ++ndiag;
-            if (ndiag != 1) single = false;
-        }
-        ds.resize(cells.size());
-        for (size_t i = 0; i < cells.size(); ++i) ds[i] = ds_cell[cells[i]];
-    };
-    int rc = XH_OK;
-    UploadPool pool;
-    {
-        std::vector<int> ptr, col, ds;
-        std::vector<signed char> sgn;
-        build_csr(fb_cells, ptr, col, sgn, ds, plan->fb_single_ds);
-        plan->n_fb = (int64_t)fb_cells.size();
-        pool.add(plan->d_fb_cells, fb_cells);
-        pool.add(plan->d_fb_ptr, ptr);
-        pool.add(plan->d_fb_col, col);
-        pool.add(plan->d_fb_sgn, sgn);
-        pool.add(plan->d_fb_ds, ds);
-        build_csr(fb_rest_cells, ptr, col, sgn, ds, plan->fb_rest_single_ds);
-        plan->n_fb_rest = (int64_t)fb_rest_cells.size();
-        pool.add(plan->d_fbr_cells, fb_rest_cells);
-        pool.add(plan->d_fbr_ptr, ptr);
-        pool.add(plan->d_fbr_col, col);
-        pool.add(plan->d_fbr_sgn, sgn);
-        pool.add(plan->d_fbr_ds, ds);
-        std::vector<int> all(n);
-        std::iota(all.begin(), all.end(), 0);
-        build_csr(all, ptr, col, sgn, ds, plan->all_single_ds);
-        plan->all_nnz = (int64_t)col.size();
-        pool.add(plan->d_all_cells, all);
-        pool.add(plan->d_all_ptr, ptr);
-        pool.add(plan->d_all_col, col);
-        pool.add(plan->d_all_sgn, sgn);
-        pool.add(plan->d_all_ds, ds);
+        f->n = (int64_t)cells->size();
+        f->single_ds = single_ds;
+        pool.add(f->cells, *cells);
+        pool.add(f->ptr, ptr);
+        pool.add(f->col, col);
+        pool.add(f->sgn, sgn);
+        pool.add(f->ds, ds);
     }
     pool.add(plan->d_cell_of_slot, cell_of_slot);
     pool.add(plan->d_ent, ent);
@@ -797,39 +749,40 @@ static void route_plan_free(xh_route_plan *plan, bool settle) {
     if (plan->ev_fork) (void)hipEventDestroy(plan->ev_fork);
     for (int k = 0; k <= N_CLASS; ++k)
         if (plan->ev_join[k]) (void)hipEventDestroy(plan->ev_join[k]);
-    DevBuf *bufs[] = {&plan->d_cell_of_slot, &plan->d_ent, &plan->d_cnt, &plan->d_fb_cells, &plan->d_fb_ptr,
-                      &plan->d_fb_col, &plan->d_fb_sgn, &plan->d_fb_ds, &plan->d_all_cells, &plan->d_all_ptr,
-                      &plan->d_all_col, &plan->d_all_sgn, &plan->d_all_ds, &plan->d_fbr_cells, &plan->d_fbr_ptr,
-                      &plan->d_fbr_col, &plan->d_fbr_sgn, &plan->d_fbr_ds};
-    for (DevBuf *b : bufs) free_buf(*b);
+    for (DevBuf *b : {&plan->d_cell_of_slot, &plan->d_ent, &plan->d_cnt}) free_buf(*b);
+    for (FbCsr *f : {&plan->fb, &plan->fb_rest, &plan->fb_all})
+        for (DevBuf *b : {&f->cells, &f->ptr, &f->col, &f->sgn, &f->ds}) free_buf(*b);
     if (plan->d_pool) (void)hipFree(plan->d_pool);
-    flow_plan_destroy(plan->flow);
-    flow_plan_destroy(plan->flow_rsum);
-    flow_plan_destroy(plan->flow_rsum_fold);
+    for (RouteForm &f : plan->form) flow_plan_destroy(f.fp);
     delete plan;
 }
 
 extern "C" void xh_route_plan_destroy(xh_route_plan *plan) { route_plan_free(plan, true); }
+
+// the reassociated partition the last call ran on, or nullptr (the bit-exact kernels, or none)
+static const FlowPlan *last_reassoc(const xh_route_plan *plan) {
+    return plan->last.form != XH_FORM_EXACT ? plan->last.fp : nullptr;
+}
 
 extern "C" int xh_route_plan_info(const xh_route_plan *plan, int64_t info[16]) {
     if (!plan || !info) return XH_ERR_ARG;
     info[0] = plan->n_networks;
     info[1] = plan->largest_network;
     info[2] = plan->n_units;
-    info[3] = plan->n_fb;
+    info[3] = plan->fb.n;
     info[4] = plan->largest_unit;
     info[5] = plan->total_slots;
-    info[6] = plan->all_single_ds ? 1 : 0;
+    info[6] = plan->fb_all.single_ds ? 1 : 0;
+    const FlowPlan *exact = plan->form[XH_FORM_EXACT].fp, *rsum = last_reassoc(plan);
     int64_t fi[5];
-    flow_plan_info(plan->last_rsum ? plan->last_rsum_plan : plan->flow, fi);
+    flow_plan_info(rsum ? rsum : exact, fi);
     info[7] = fi[0];                  // dataflow units
     info[8] = fi[1];                  // stream edges
     info[9] = fi[2];                  // pipeline depth
     info[10] = fi[3];                 // cells routed by the dataflow kernel
     info[11] = fi[4];                 // most imported streams of a unit
-    info[12] = (plan->last_rsum && plan->last_rsum_plan) ? plan->last_rsum_plan->skew_lmax
-                                                    : ((plan->flow && plan->flow->skew_ok) ? plan->flow->skew_lmax : -1);     // deepest lane lag (sub-steps)
-    info[13] = plan->last_tree_kernel;
+    info[12] = rsum ? rsum->skew_lmax : ((exact && exact->skew_ok) ? exact->skew_lmax : -1);     // deepest lane lag (sub-steps)
+    info[13] = plan->last.kernel;
     info[14] = plan->reroutes;
     info[15] = plan->validated;
     return XH_OK;
@@ -838,7 +791,8 @@ extern "C" int xh_route_plan_info(const xh_route_plan *plan, int64_t info[16]) {
 extern "C" int xh_route_plan_stats(xh_route_plan *plan, int64_t max_words, uint64_t *h_words, int64_t *n_words) {
     if (!plan || !n_words) return XH_ERR_ARG;
     std::vector<unsigned long long> st;
-    int rc = flow_stats_fetch(plan->ctx, plan->last_rsum ? plan->last_rsum_plan : plan->flow, st);
+    const FlowPlan *rsum = last_reassoc(plan);
+    int rc = flow_stats_fetch(plan->ctx, const_cast<FlowPlan *>(rsum ? rsum : plan->form[XH_FORM_EXACT].fp), st);
     if (rc) return rc;
     *n_words = (int64_t)st.size();
     if (h_words)
@@ -866,54 +820,43 @@ extern "C" int xh_route_plan_prepare(xh_ctx *ctx, xh_route_plan *plan, const dou
         // A plan may be prepared again: other velocities, lengths or dt that change WHICH cells can fire replace the prepared
         // plan (and lift a guard trip's ban, which was about the old one); the same sets are a cheap no-op.
         static const bool fold_on = xh_env_on("XH_FLOW_FOLD", true), single_on = xh_env_on("XH_RSUM_SINGLE", true);
-        if ((!fold_on && !single_on) || !plan->flow || plan->h_indptr.empty()) return XH_OK;
+        if ((!fold_on && !single_on) || !plan->form[XH_FORM_EXACT].fp || plan->h_indptr.empty()) return XH_OK;
         const size_t n = (size_t)plan->ncell;
         std::vector<unsigned char> foldable(n, 0), capable(n, 0);
         size_t nfold = 0;
-        uint64_t key = 1469598103934665603ull;
+        uint64_t key = XH_FNV_BASIS;
         for (size_t c = 0; c < n; ++c) {
             const double tauinv = h_velocity[c] / h_flow_dist[c];
             const bool leaf = plan->h_indptr[c + 1] - plan->h_indptr[c] == 1;
             capable[c] = (tauinv * dt <= CAPABLE_THRESHOLD) ? 0 : 1;                                    // (NaN: can fire)
             foldable[c] = (leaf && tauinv >= 0.0 && tauinv * dt <= CAPABLE_THRESHOLD) ? 1 : 0;          // (NaN: not foldable)
             nfold += foldable[c];
-            key = (key ^ (unsigned)(capable[c] | (foldable[c] << 1))) * 1099511628211ull;
+            const unsigned char sets = (unsigned char)(capable[c] | (foldable[c] << 1));
+            key = xh_fnv1a(key, &sets, 1);
         }
-        {
-            unsigned char b[sizeof(double)];
-            memcpy(b, &dt, sizeof(dt));
-            for (unsigned char x : b) key = (key ^ x) * 1099511628211ull;
-            if (key == 0) key = 1;
-        }
+        key = xh_fnv1a(key, &dt, sizeof(dt));
+        if (key == 0) key = 1;
         if (plan->fold_tried && key == plan->prep_key) return XH_OK;
-        if (plan->flow_rsum_fold) {      // prepared for other data: the old plan may still be routing
+        RouteForm &prepared = plan->form[XH_FORM_PREPARED];
+        if (prepared.fp) {      // prepared for other data: the old plan may still be routing
             XH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            if (plan->last_rsum_plan == plan->flow_rsum_fold) {
-                plan->last_rsum_plan = nullptr;
-                plan->last_rsum = false;
+            if (plan->last.fp == prepared.fp) {
+                plan->last.form = XH_FORM_EXACT;
+                plan->last.fp = nullptr;
             }
-            flow_plan_destroy(plan->flow_rsum_fold);
-            plan->flow_rsum_fold = nullptr;
-            plan->first_checked_fold = false;
+            flow_plan_destroy(prepared.fp);
+            prepared.fp = nullptr;
+            prepared.first_checked = false;
         }
         plan->fold_tried = true;
         plan->prep_key = key;
         plan->fold_disabled = false;
         const bool fold = fold_on && nfold > 0;
         if (!fold && !single_on) return XH_OK;
-        std::vector<char> handled;
-        FlowTables t;
-        if (!rsum_tables_get(ctx, plan, fold ? foldable.data() : nullptr, single_on ? capable.data() : nullptr, t, handled) ||
-            (t.n_folded == 0 && t.n_special < 0))
-            return XH_OK;
-        if (t.n_cells != plan->flow->n_cells) return XH_OK;
-        if (xh_flow_check()) {
-            const std::string bad = flow_tables_check_rsum((int)plan->ncell, plan->h_indptr.data(), plan->h_indices.data(),
-                                                           plan->h_sign.data(), handled, t);
-            if (!bad.empty()) return xh_fail(ctx, XH_ERR_ARG, "reassociated flow plan check (prepared plan): %s", bad.c_str());
-        }
-        const int rcu = flow_plan_upload(ctx, t, &plan->flow_rsum_fold);
-        if (rcu) return rcu;
+        const int rcu = rsum_partition(ctx, plan, fold ? foldable.data() : nullptr, single_on ? capable.data() : nullptr,
+                                       &prepared.fp);
+        if (rcu || !prepared.fp) return rcu;
+        prepared.suffix = prepared.fp->n_special >= 0 ? "_rs" : "_rf";
         plan->fold_dt = dt;
         return XH_OK;
     }
@@ -927,22 +870,42 @@ void xh_route_backoff(xh_route_plan *plan) {      // once per fault event and pl
 
 extern "C" int xh_route_plan_rsum_info(const xh_route_plan *plan, int64_t info[8]) {
     if (!plan || !info) return XH_ERR_ARG;
-    const FlowPlan *fp = plan->last_rsum ? plan->last_rsum_plan : nullptr;
+    const FlowPlan *fp = last_reassoc(plan), *prep = plan->form[XH_FORM_PREPARED].fp;
     info[0] = fp ? fp->n_units : 0;
     info[1] = fp ? fp->n_folded : 0;
     info[2] = plan->fold_disabled ? 1 : 0;
-    info[3] = plan->flow_rsum_fold ? plan->flow_rsum_fold->n_folded : 0;
+    info[3] = prep ? prep->n_folded : 0;
     info[4] = fp ? fp->n_special : -1;
-    info[5] = plan->flow_rsum_fold ? plan->flow_rsum_fold->n_special : -1;
+    info[5] = prep ? prep->n_special : -1;
     info[6] = plan->guard_trips;
     info[7] = fp ? fp->n_pair_units : 0;
     return XH_OK;
 }
 
+RouteChoice route_choose(const xh_route_plan *plan, int flags, double dt, bool fed) {
+    RouteChoice c;
+    c.whole_graph = (flags & XH_ROUTE_FORCE_FALLBACK) != 0;
+    c.atomic = (flags & XH_ROUTE_ATOMIC) != 0;
+    c.dataflow = !c.whole_graph && plan->form[XH_FORM_EXACT].fp && (flags & XH_ROUTE_NO_DATAFLOW) == 0;
+    c.skew = (flags & XH_ROUTE_NO_SKEW) == 0;
+    c.checkable = c.dataflow && !c.atomic && (flags & XH_ROUTE_TEST_FAULT) == 0;
+    // Reassociated form (XH_ROUTE_REASSOC, flag or environment): the time-skewed kernel on a partition of its own -- the
+    // prepared one (leaves that cannot fire carried by their parents' lanes, single sums: guarded in the kernel) when it was
+    // made for this dt and not banned by a guard trip, else the plan of pairs
+    if (c.dataflow && c.skew && !c.atomic && reassoc_wanted(flags) && !plan->rsum_failed) {
+        c.form = XH_FORM_PAIRS;
+        if (plan->form[XH_FORM_PREPARED].fp && !plan->fold_disabled && dt == plan->fold_dt && (flags & XH_ROUTE_NO_PLAIN) == 0)
+            c.form = XH_FORM_PREPARED;
+    }
+    // a fed call: every cell must be routed by the time-skewed kernel (the others read the runoff array itself, at once)
+    c.refuse_fed = fed && (!c.dataflow || !c.skew || c.atomic || plan->n_rest_units > 0 || plan->fb_rest.n > 0);
+    return c;
+}
+
 int route_series_impl(xh_ctx *ctx, xh_route_plan *plan, int32_t nmonths, int32_t spinup_months,
                              const int32_t *h_ndays, double dt, const double *d_flow_dist, const double *d_velocity,
                              const double *d_area, const double *d_runoff, const double *d_S0, double *d_chstorage,
-                             double *d_avgchflow, double *d_S_end, double *d_F_end, int32_t flags, bool *used_flow,
+                             double *d_avgchflow, double *d_S_end, double *d_F_end, int32_t flags, xh_route_outcome *out,
                              const FlowFeed *feed) {
     if (!ctx || !plan) return XH_ERR_ARG;
     XH_REQUIRE(ctx, plan->ctx == ctx, "xh_route_series: plan belongs to another context");
@@ -995,35 +958,25 @@ int route_series_impl(xh_ctx *ctx, xh_route_plan *plan, int32_t nmonths, int32_t
         XH_HIP(ctx, hipMemcpyAsync(d_wr, swr.data(), (size_t)nit, hipMemcpyHostToDevice, ctx->stream));
         return XH_OK;
     };
-    // Reassociated form (XH_ROUTE_REASSOC, flag or environment): a partition of its own, nothing to learn -- the typed / adaptive
-    // machinery below is for the bit-exact kernel only.
-    bool use_rsum = reassoc_wanted(flags) && plan->flow &&
-                    (flags & (XH_ROUTE_FORCE_FALLBACK | XH_ROUTE_NO_DATAFLOW | XH_ROUTE_NO_SKEW | XH_ROUTE_ATOMIC)) == 0;
-    if (use_rsum) {
+    *out = xh_route_outcome();
+    RouteChoice c = route_choose(plan, flags, dt, feed != nullptr);
+    if (c.form != XH_FORM_EXACT && !plan->form[XH_FORM_PAIRS].fp) {      // made on the first call that asks for the form
         if ((rc = rsum_plan_build(ctx, plan)) != XH_OK) return rc;
-        use_rsum = plan->flow_rsum != nullptr;
+        c = route_choose(plan, flags, dt, feed != nullptr);
     }
-    flags &= ~(XH_ROUTE_REASSOC | XH_ROUTE_EXACT);
-    FlowPlan *tree_plan = plan->flow;
-    FlowPlan *rsum_plan = plan->flow_rsum;
-    if (use_rsum && plan->flow_rsum_fold && !plan->fold_disabled && dt == plan->fold_dt && (flags & XH_ROUTE_NO_PLAIN) == 0)
-        rsum_plan = plan->flow_rsum_fold;      // leaves that cannot fire carried by their parents' lanes (guarded in the kernel)
-    if (use_rsum) tree_plan = rsum_plan;
+    if (c.refuse_fed) return XH_ERR_LIMIT;
 
-    const bool force_fb = (flags & XH_ROUTE_FORCE_FALLBACK) != 0;
-    const bool atomic = (flags & XH_ROUTE_ATOMIC) != 0;
-    bool use_flow = !force_fb && plan->flow != nullptr && (flags & XH_ROUTE_NO_DATAFLOW) == 0;
-    // fed call: every cell must be routed by k_mrtm_wave (the other kernels read the runoff array itself, at once)
-    if (feed && (!use_flow || plan->n_rest_units > 0 || plan->n_fb_rest > 0)) return XH_ERR_LIMIT;
-
-    xh_span sp = xh_span_begin(ctx, "mrtm_route");
+    // (every return below that does not end the span cancels it: an error, or a fed call nothing was launched for)
+    struct Span {
+        xh_span s;
+        bool open = true;
+        ~Span() { if (open) xh_span_cancel(s); }
+    } span{xh_span_begin(ctx, "mrtm_route")};
     // (kernels on the class streams wait for ev_fork: whatever they read must be in the stream before it is recorded)
-    if (!(use_flow && plan->n_rest_units == 0 && plan->n_fb_rest == 0) && (rc = sched_upload()) != XH_OK) return rc;
+    if (!(c.dataflow && plan->n_rest_units == 0 && plan->fb_rest.n == 0) && (rc = sched_upload()) != XH_OK) return rc;
     XH_HIP(ctx, hipEventRecord(plan->ev_fork, ctx->stream));
     int njoin = 0;
-    plan->last_tree_kernel = 0;
-    plan->last_rsum = false;
-    if (use_flow) {     // tree-shaped networks: single-wave dataflow units on the context's own stream
+    if (c.dataflow) {     // tree-shaped networks: single-wave dataflow units on the context's own stream
         int ntmax = 0, ntmin = INT_MAX;
         bool nt_even = true;
         for (int v : snt) {
@@ -1035,46 +988,42 @@ int route_series_impl(xh_ctx *ctx, xh_route_plan *plan, int32_t nmonths, int32_t
                            (flags & XH_ROUTE_TEST_FAULT) != 0, nt_even, sm.data(), snt.data(), sg.data(), ssecs.data(),
                            swr.data()};
         const FlowIO fio{d_flow_dist, d_velocity, d_area, d_runoff, d_S0, d_chstorage, d_avgchflow, d_S_end, d_F_end, feed};
-        // time-skewed units first; months shorter than the deepest lane lag (long dt) and grids beyond the kernel's 32-bit row
-        // offsets use the lock-step kernel (k_mrtm_flow)
+        // time-skewed units first, on the chosen form's partition, then on the bit-exact one: a month shorter than the
+        // partition's lane lags, the 32-bit row limit or residency send a call from the reassociated partition back to the
+        // bit-exact one; months shorter than the deepest lane lag (long dt) and grids beyond the kernel's 32-bit row offsets
+        // use the lock-step kernel (k_mrtm_flow)
+        FlowPlan *exact = plan->form[XH_FORM_EXACT].fp;
         rc = XH_ERR_LIMIT;
-        plan->last_tree_kernel = 2;
-        if ((flags & XH_ROUTE_NO_SKEW) == 0) rc = wave_launch(ctx, tree_plan, fs, fio, ctx->stream);
-        // (which plan actually ran: a month shorter than the plan's lane lags, the 32-bit row limit or residency send the call
-        // from the reassociated plan back to the bit-exact one -- everything below speaks of THAT plan then)
-        FlowPlan *ran = tree_plan;
-        if (rc == XH_ERR_LIMIT && tree_plan != plan->flow && (flags & XH_ROUTE_NO_SKEW) == 0) {
-            ran = plan->flow;
-            rc = wave_launch(ctx, plan->flow, fs, fio, ctx->stream);
+        if (c.skew) {
+            for (int f : {c.form, (int)XH_FORM_EXACT}) {
+                FlowPlan *fp = plan->form[f].fp;
+                *out = {f == XH_FORM_EXACT ? 2 : 4, f, fp, f == XH_FORM_PREPARED ? plan->prep_key : 0, nullptr};
+                rc = wave_launch(ctx, fp, fs, fio, ctx->stream, &out->place);
+                if (rc != XH_ERR_LIMIT || f == XH_FORM_EXACT) break;
+            }
         }
-        plan->last_rsum = rc == XH_OK && use_rsum && ran == rsum_plan && ran->rsum;
-        if (plan->last_rsum) plan->last_rsum_plan = rsum_plan;
-        if (plan->last_rsum) plan->last_tree_kernel = 4;
-        if (feed && rc == XH_ERR_LIMIT) {      // nothing was launched: the caller completes the runoff and calls again
-            xh_span_cancel(sp);
-            return XH_ERR_LIMIT;
-        }
+        if (feed && rc == XH_ERR_LIMIT) return XH_ERR_LIMIT;      // nothing was launched: the caller completes the runoff and calls again
         if (rc == XH_ERR_LIMIT) {
-            plan->last_tree_kernel = 1;
             if ((rc = sched_upload()) != XH_OK) return rc;
-            rc = flow_launch(ctx, plan->flow, fs, fio, ctx->stream);
+            *out = {1, XH_FORM_EXACT, exact, 0, nullptr};
+            rc = flow_launch(ctx, exact, fs, fio, ctx->stream);
         }
         if (rc == XH_ERR_LIMIT) {
-            use_flow = false;   // units cannot all be resident on this device: one workgroup per network instead
-            plan->last_tree_kernel = 0;
+            c.dataflow = false;   // units cannot all be resident on this device: one workgroup per network instead
+            *out = xh_route_outcome();
         } else if (rc) {
             return rc;
         }
     }
-    const int64_t n_fb = force_fb ? plan->ncell : (use_flow ? plan->n_fb_rest : plan->n_fb);
-    const int64_t n_lds_units = use_flow ? plan->n_rest_units : plan->n_units;
-    if (((!force_fb && n_lds_units > 0) || n_fb > 0) && !sched_on_device) {
+    const FbCsr &fb = c.fallback(plan);
+    const int64_t n_lds_units = c.whole_graph ? 0 : c.dataflow ? plan->n_rest_units : plan->n_units;
+    if ((n_lds_units > 0 || fb.n > 0) && !sched_on_device) {
         // only after the dataflow kernels turned a tree-only grid down: nothing of this call is running yet
         rc = sched_upload();
         if (rc) return rc;
         XH_HIP(ctx, hipEventRecord(plan->ev_fork, ctx->stream));
     }
-    if (!force_fb && n_lds_units > 0) {
+    if (n_lds_units > 0) {
         RouteArgs a;
         a.unit_slot0 = nullptr;
         a.cell_of_slot = static_cast<const int *>(plan->d_cell_of_slot.p);
@@ -1100,19 +1049,19 @@ int route_series_impl(xh_ctx *ctx, xh_route_plan *plan, int32_t nmonths, int32_t
         a.F_end = d_F_end;
         // largest classes first so the long-running workgroups start first
         for (int cls = N_CLASS - 1; cls >= 0; --cls) {
-            if ((use_flow ? plan->rest_units[cls] : plan->class_units[cls]).empty()) continue;
+            if ((c.dataflow ? plan->rest_units[cls] : plan->class_units[cls]).empty()) continue;
             hipStream_t st = nullptr;
             if (!plan->streams[cls]) XH_HIP(ctx, hipStreamCreateWithFlags(&plan->streams[cls], hipStreamNonBlocking));
             st = plan->streams[cls];
             XH_HIP(ctx, hipStreamWaitEvent(st, plan->ev_fork, 0));
             switch (cls) {
-                case 0: launch_units<1, 64>(plan, cls, a, st, use_flow); break;
-                case 1: launch_units<2, 64>(plan, cls, a, st, use_flow); break;
-                case 2: launch_units<4, 64>(plan, cls, a, st, use_flow); break;
-                case 3: launch_units<2, 256>(plan, cls, a, st, use_flow); break;
-                case 4: launch_units<4, 256>(plan, cls, a, st, use_flow); break;
-                case 5: launch_units<2, 1024>(plan, cls, a, st, use_flow); break;
-                case 6: launch_units<4, 768>(plan, cls, a, st, use_flow); break;
+                case 0: launch_units<1, 64>(plan, cls, a, st, c.dataflow); break;
+                case 1: launch_units<2, 64>(plan, cls, a, st, c.dataflow); break;
+                case 2: launch_units<4, 64>(plan, cls, a, st, c.dataflow); break;
+                case 3: launch_units<2, 256>(plan, cls, a, st, c.dataflow); break;
+                case 4: launch_units<4, 256>(plan, cls, a, st, c.dataflow); break;
+                case 5: launch_units<2, 1024>(plan, cls, a, st, c.dataflow); break;
+                case 6: launch_units<4, 768>(plan, cls, a, st, c.dataflow); break;
                 case 7: break;
             }
             XH_HIP(ctx, hipGetLastError());
@@ -1121,29 +1070,21 @@ int route_series_impl(xh_ctx *ctx, xh_route_plan *plan, int32_t nmonths, int32_t
             ++njoin;
         }
     }
-    if (n_fb > 0) {
-        const bool single = force_fb ? plan->all_single_ds : (use_flow ? plan->fb_rest_single_ds : plan->fb_single_ds);
-        const DevBuf &b_cells = force_fb ? plan->d_all_cells : (use_flow ? plan->d_fbr_cells : plan->d_fb_cells);
-        const DevBuf &b_ptr = force_fb ? plan->d_all_ptr : (use_flow ? plan->d_fbr_ptr : plan->d_fb_ptr);
-        const DevBuf &b_col = force_fb ? plan->d_all_col : (use_flow ? plan->d_fbr_col : plan->d_fb_col);
-        const DevBuf &b_sgn = force_fb ? plan->d_all_sgn : (use_flow ? plan->d_fbr_sgn : plan->d_fb_sgn);
-        const DevBuf &b_ds = force_fb ? plan->d_all_ds : (use_flow ? plan->d_fbr_ds : plan->d_fb_ds);
-        if (atomic && !single) {
-            xh_span_end(sp);
+    if (fb.n > 0) {
+        if (c.atomic && !fb.single_ds)
             return xh_fail(ctx, XH_ERR_ARG, "xh_route_series: XH_ROUTE_ATOMIC needs one downstream cell per cell");
-        }
         // work arrays in cell order: S, F, F2, favg, erl, inflow (6 doubles) + sx flag
         void *wbuf = nullptr;
         const size_t nc = (size_t)plan->ncell;
         rc = xh_scratch(ctx, 3, nc * (6 * sizeof(double) + 1) + 64, &wbuf);
         if (rc) return rc;
         FbArgs f;
-        f.n = (int)n_fb;
-        f.cells = static_cast<const int *>(b_cells.p);
-        f.ptr = static_cast<const int *>(b_ptr.p);
-        f.col = static_cast<const int *>(b_col.p);
-        f.sgn = static_cast<const signed char *>(b_sgn.p);
-        f.ds = static_cast<const int *>(b_ds.p);
+        f.n = (int)fb.n;
+        f.cells = static_cast<const int *>(fb.cells.p);
+        f.ptr = static_cast<const int *>(fb.ptr.p);
+        f.col = static_cast<const int *>(fb.col.p);
+        f.sgn = static_cast<const signed char *>(fb.sgn.p);
+        f.ds = static_cast<const int *>(fb.ds.p);
         f.nmonths = nmonths;
         f.dt = dt;
         f.dtinv = 1.0 / dt;
@@ -1157,7 +1098,7 @@ int route_series_impl(xh_ctx *ctx, xh_route_plan *plan, int32_t nmonths, int32_t
         f.F2 = f.F + nc;
         f.favg = f.F2 + nc;
         f.erl = f.favg + nc;
-        f.inflow = atomic ? f.erl + nc : nullptr;
+        f.inflow = c.atomic ? f.erl + nc : nullptr;
         f.sx = reinterpret_cast<unsigned char *>(f.erl + 2 * nc);
         f.chs = d_chstorage;
         f.avg = d_avgchflow;
@@ -1167,12 +1108,12 @@ int route_series_impl(xh_ctx *ctx, xh_route_plan *plan, int32_t nmonths, int32_t
         if (!plan->fb_stream) XH_HIP(ctx, hipStreamCreateWithFlags(&plan->fb_stream, hipStreamNonBlocking));
         st = plan->fb_stream;
         XH_HIP(ctx, hipStreamWaitEvent(st, plan->ev_fork, 0));
-        const dim3 grid((unsigned)((n_fb + 255) / 256)), block(256);
+        const dim3 grid((unsigned)((fb.n + 255) / 256)), block(256);
         hipLaunchKernelGGL(k_fb_init, grid, block, 0, st, f);
         for (int it = 0; it < nit; ++it) {
             hipLaunchKernelGGL(k_fb_month_begin, grid, block, 0, st, f, sm[it], ssecs[it]);
             for (int t = 0; t < snt[it]; ++t) {
-                if (atomic) {
+                if (c.atomic) {
                     hipLaunchKernelGGL(k_fb_scatter, grid, block, 0, st, f, 0);
                     hipLaunchKernelGGL(k_fb_phase_a<true>, grid, block, 0, st, f);
                     hipLaunchKernelGGL(k_fb_scatter, grid, block, 0, st, f, 1);
@@ -1189,7 +1130,7 @@ int route_series_impl(xh_ctx *ctx, xh_route_plan *plan, int32_t nmonths, int32_t
         XH_HIP(ctx, hipEventRecord(plan->ev_join[N_CLASS], st));
         XH_HIP(ctx, hipStreamWaitEvent(ctx->stream, plan->ev_join[N_CLASS], 0));
     }
-    xh_span_end(sp);
-    *used_flow = use_flow;
+    span.open = false;
+    xh_span_end(span.s);
     return XH_OK;
 }

@@ -9,9 +9,6 @@
 //     1e-9 for the reassociated form (the streams between dataflow units rest on an ordering assumption outside the HIP
 //     memory model: xh_mrtm_wave_unit.h, check()).
 // Reference: the month loops of xanthos/components.py:273-294 are what one call replaces; none of this exists there.
-#include <sys/stat.h>
-#include <unistd.h>
-
 #include <algorithm>
 #include <cmath>
 
@@ -48,10 +45,11 @@ __global__ void __launch_bounds__(256) k_count_far(const double *a, const double
 // XH_ROUTE_VALIDATE: the call has just been routed by a dataflow kernel into the caller's arrays; route it again with one
 // workgroup per network (barriers, no streams, no reliance on the ordering of write-through stores) into scratch arrays
 // and compare every output bit.  Synchronous; a debugging / CI mode.
+// by_rsum: the call was routed by the reassociated form (equal to rounding: compared within 1e-9).
 static int route_validate(xh_ctx *ctx, xh_route_plan *plan, int32_t nmonths, int32_t spinup_months, const int32_t *h_ndays,
                           double dt, const double *d_flow_dist, const double *d_velocity, const double *d_area,
                           const double *d_runoff, const double *d_S0, const double *d_chs, const double *d_avg,
-                          const double *d_S_end, const double *d_F_end, int32_t flags) {
+                          const double *d_S_end, const double *d_F_end, int32_t flags, bool by_rsum) {
     int rc = xh_settle(ctx);          // a fault of the dataflow run is settled (re-routed) first: then there is nothing to validate
     if (rc) return rc;
     const size_t nc = (size_t)plan->ncell, big = nc * (size_t)nmonths * sizeof(double);
@@ -71,13 +69,9 @@ static int route_validate(xh_ctx *ctx, xh_route_plan *plan, int32_t nmonths, int
         release();
         return xh_fail(ctx, XH_ERR_HIP, "XH_ROUTE_VALIDATE: no memory for the second set of outputs");
     }
-    bool used = false;
-    const int routed_by = plan->last_tree_kernel;
-    const bool by_rsum = plan->last_rsum;       // routed by the reassociated form: equal to rounding, compared within 1e-9
+    xh_route_outcome second;
     rc = route_series_impl(ctx, plan, nmonths, spinup_months, h_ndays, dt, d_flow_dist, d_velocity, d_area, d_runoff, d_S0,
-                           t_chs, t_avg, t_S, t_F, (flags | XH_ROUTE_NO_DATAFLOW) & ~XH_ROUTE_TEST_FAULT, &used);
-    plan->last_tree_kernel = routed_by;
-    plan->last_rsum = by_rsum;
+                           t_chs, t_avg, t_S, t_F, (flags | XH_ROUTE_NO_DATAFLOW) & ~XH_ROUTE_TEST_FAULT, &second);
     if (!rc) {
         (void)hipMemsetAsync(d_cnt, 0, sizeof(unsigned long long), ctx->stream);
         // (storages in m3, flows in m3/s: the absolute terms are far below anything a grid cell holds or passes)
@@ -132,19 +126,13 @@ int xh_route_series_fed(xh_ctx *ctx, xh_route_plan *plan, int32_t nmonths, int32
                              d_chstorage, d_avgchflow, nullptr, nullptr, flags, feed);
 }
 
-// Marker of a passed first-call check: <dir>/route_ok_<device>_<build>_<topology>; dir = $XH_CACHE_DIR or
-// $HOME/.cache/xanthos_amd.  Failing to read or write it only means the check runs again.
-// (form: 0 the bit-exact kernels, 1 the reassociated form, 2 the prepared reassociated plan: folded leaves "_rf", single sums "_rs")
-static std::string first_check_path(const xh_ctx *ctx, const xh_route_plan *plan, int form) {
-    const std::string dir = xh_cache_dir();
-    if (dir.empty()) return std::string();
-    uint64_t h = 1469598103934665603ull;
-    auto mix = [&](const char *t) {
-        for (; *t; ++t) h = (h ^ (unsigned char)*t) * 1099511628211ull;
-    };
-    mix(ctx->prop.name);
-    mix(ctx->prop.gcnArchName);
-    mix(__DATE__ " " __TIME__);      // this translation unit's build: a new library build checks again
+// Marker of a passed first-call check: <dir>/route_ok_<device>_<build>_<topology>[_<prep_key>]<form>; dir = $XH_CACHE_DIR or
+// $HOME/.cache/xanthos_amd.  The prepared form's partition depends on the data it was prepared for: its marker names the
+// prepare key.  Failing to read or write it only means the check runs again.
+static std::string first_check_path(const xh_ctx *ctx, const xh_route_plan *plan, int form, bool for_write) {
+    uint64_t h = xh_fnv1a(XH_FNV_BASIS, ctx->prop.name);
+    h = xh_fnv1a(h, ctx->prop.gcnArchName);
+    h = xh_fnv1a(h, __DATE__ " " __TIME__);      // this translation unit's build: a new library build checks again
     {   // the HIP runtime and the driver the pass was recorded under: the ordering the streams rely on is theirs as much as
         // the silicon's (XH_TEST_RUNTIME_TAG: appended, so that a test can stand in for "another runtime")
         int rt = 0, drv = 0;
@@ -153,28 +141,22 @@ static std::string first_check_path(const xh_ctx *ctx, const xh_route_plan *plan
         char ver[96];
         const char *tag = getenv("XH_TEST_RUNTIME_TAG");
         snprintf(ver, sizeof(ver), "rt%d drv%d %s", rt, drv, tag ? tag : "");
-        mix(ver);
+        h = xh_fnv1a(h, ver);
     }
+    char key[24] = "";
+    if (form == XH_FORM_PREPARED) snprintf(key, sizeof(key), "_%016llx", (unsigned long long)plan->prep_key);
     char name[160];
-    snprintf(name, sizeof(name), "/route_ok_%016llx_%016llx_%lld_%lld%s", (unsigned long long)h, (unsigned long long)plan->topo_hash,
-             (long long)plan->ncell, (long long)(plan->flow ? plan->flow->n_units : 0),
-             form == 2 ? ((plan->flow_rsum_fold && plan->flow_rsum_fold->n_special >= 0) ? "_rs" : "_rf") : form == 1 ? "_r" : "");
-    return dir + name;
-}
-
-static bool &first_checked_of(xh_route_plan *plan, int form) {
-    return form == 2 ? plan->first_checked_fold : form == 1 ? plan->first_checked_rsum : plan->first_checked;
-}
-
-static int last_form(const xh_route_plan *plan) {
-    return !plan->last_rsum ? 0 : (plan->flow_rsum_fold && plan->last_rsum_plan == plan->flow_rsum_fold) ? 2 : 1;
+    snprintf(name, sizeof(name), "route_ok_%016llx_%016llx_%lld_%lld%s%s", (unsigned long long)h, (unsigned long long)plan->topo_hash,
+             (long long)plan->ncell, (long long)(plan->form[XH_FORM_EXACT].fp ? plan->form[XH_FORM_EXACT].fp->n_units : 0), key,
+             plan->form[form].suffix);
+    return xh_cache_path(name, for_write);
 }
 
 static bool first_check_needed(xh_ctx *ctx, xh_route_plan *plan, int form) {
     static const bool enabled = xh_env_on("XH_ROUTE_VALIDATE_FIRST", true);
-    bool &checked = first_checked_of(plan, form);
-    if (!enabled || checked || !plan->flow) return false;
-    const std::string path = first_check_path(ctx, plan, form);
+    bool &checked = plan->form[form].first_checked;
+    if (!enabled || checked || !plan->form[XH_FORM_EXACT].fp) return false;
+    const std::string path = first_check_path(ctx, plan, form, false);
     if (!path.empty()) {
         if (FILE *f = fopen(path.c_str(), "r")) {
             fclose(f);
@@ -186,12 +168,9 @@ static bool first_check_needed(xh_ctx *ctx, xh_route_plan *plan, int form) {
 }
 
 static void first_check_passed(xh_ctx *ctx, xh_route_plan *plan, int form) {
-    first_checked_of(plan, form) = true;
-    const std::string path = first_check_path(ctx, plan, form);
+    plan->form[form].first_checked = true;
+    const std::string path = first_check_path(ctx, plan, form, true);
     if (path.empty()) return;
-    const std::string dir = path.substr(0, path.rfind('/'));
-    for (size_t i = 1; i <= dir.size(); ++i)      // mkdir -p
-        if (i == dir.size() || dir[i] == '/') (void)mkdir(dir.substr(0, i).c_str(), 0755);
     if (FILE *f = fopen(path.c_str(), "w")) {
         fprintf(f, "dataflow routing equal to the workgroup-per-network kernel, %s, on %s\n", form ? "within 1e-9" : "bit for bit", ctx->prop.name);
         fclose(f);
@@ -203,43 +182,44 @@ static int route_series_call(xh_ctx *ctx, xh_route_plan *plan, int32_t nmonths, 
                              const double *d_velocity, const double *d_area, const double *d_runoff,
                              const double *d_S0, double *d_chstorage, double *d_avgchflow, double *d_S_end,
                              double *d_F_end, int32_t flags, const FlowFeed *feed) {
-    bool used_flow = false;
-    if (plan && plan->skip_calls > 0 && (flags & XH_ROUTE_TEST_FAULT) == 0) {      // recently faulted: see xh_route_plan
+    if (!plan) return XH_ERR_ARG;
+    if (plan->skip_calls > 0 && (flags & XH_ROUTE_TEST_FAULT) == 0) {      // recently faulted: see xh_route_plan
         if (!feed) plan->skip_calls -= 1;      // (a fed call is turned down below and comes back as an ordinary one: counted there)
         flags |= XH_ROUTE_NO_DATAFLOW;
     }
     static const bool validate_env = xh_env_on("XH_ROUTE_VALIDATE", false);
     bool validate = validate_env || (flags & XH_ROUTE_VALIDATE) != 0;
     flags &= ~XH_ROUTE_VALIDATE;
-    // first dataflow call of this plan on a box / build that has not passed the cross-check yet: checked like XH_ROUTE_VALIDATE
-    const bool plain_call = plan && (flags & (XH_ROUTE_NO_DATAFLOW | XH_ROUTE_FORCE_FALLBACK | XH_ROUTE_ATOMIC | XH_ROUTE_TEST_FAULT)) == 0;
-    const bool want_rsum = plan && reassoc_wanted(flags) && (flags & XH_ROUTE_NO_SKEW) == 0;
-    const int want_form = !want_rsum ? 0 : (plan->flow_rsum_fold && !plan->fold_disabled && dt == plan->fold_dt) ? 2 : 1;
-    bool first_check = !validate && plain_call && first_check_needed(ctx, plan, want_form);
-    if (plain_call && plan->flow) {
+    const RouteChoice choice = route_choose(plan, flags, dt, feed != nullptr);
+    // a fed call is checked up front on the form it will try (it cannot be checked after the fact: turned down below); an
+    // ordinary one after it ran, on the form that did
+    bool first_check = feed && !validate && choice.checkable && first_check_needed(ctx, plan, choice.form);
+    bool check_due = false;      // periodic check, or one a fed call left due
+    if (choice.checkable) {
         const char *ev = getenv("XH_ROUTE_VALIDATE_EVERY");      // (read per call: a long-lived caller may change its mind)
         const int64_t every = ev ? (int64_t)atoll(ev) : (int64_t)1000;
         if (plan->validate_due && !feed) {      // the fed call that was due came back as an ordinary one: checked now
-            first_check = first_check || !validate;
+            check_due = !validate;
             plan->validate_due = false;
         } else {
             plan->dataflow_calls += 1;
             if (!validate && !first_check && every > 0 && plan->dataflow_calls % every == 0) {      // handled like the first one
-                first_check = true;
+                check_due = true;
                 plan->validate_due = feed != nullptr;      // (a fed call cannot be checked at once: turned down below)
             }
         }
     }
-    validate = validate || first_check;
     // a fed call cannot be cross-checked at once (the second routing would read runoff that does not exist yet), nor
     // routed by anything but the dataflow kernel that knows how to wait for it
     // (XH_ROUTE_TEST_FAULT is taken: the fault word is raised in front of the launch, the units that have to wait give up, and
     // the call is settled like any faulted one -- routed again from the runoff array, complete by then)
-    if (feed && (validate || (flags & (XH_ROUTE_NO_DATAFLOW | XH_ROUTE_NO_SKEW | XH_ROUTE_FORCE_FALLBACK | XH_ROUTE_ATOMIC)) != 0))
-        return XH_ERR_LIMIT;
+    if (feed && (validate || first_check || check_due || choice.refuse_fed)) return XH_ERR_LIMIT;
+    xh_route_outcome ran;
     int rc = route_series_impl(ctx, plan, nmonths, spinup_months, h_ndays, dt, d_flow_dist, d_velocity, d_area, d_runoff,
-                               d_S0, d_chstorage, d_avgchflow, d_S_end, d_F_end, flags, &used_flow, feed);
-    if (rc || !used_flow) return rc;
+                               d_S0, d_chstorage, d_avgchflow, d_S_end, d_F_end, flags, &ran, feed);
+    if (rc) return rc;
+    plan->last = ran;
+    if (!ran.kernel) return XH_OK;
     // remember the call until a synchronisation has confirmed that no bounded wait timed out (xh_fault_check)
     xh_route_record r;
     r.plan = plan;
@@ -259,20 +239,29 @@ static int route_series_call(xh_ctx *ctx, xh_route_plan *plan, int32_t nmonths, 
     r.F_end = d_F_end;
     r.seq_after = ctx->work_seq;
     r.fed = feed != nullptr;
+    r.ran = ran;
     ctx->pending_routes.push_back(std::move(r));
     rc = xh_fault_collect(ctx);
-    if (rc || !validate) return rc;
-    const int64_t reroutes_before = ctx->reroutes;
+    if (rc) return rc;
+    if (feed) {      // what it ran has no pass on record (it fell back to another form): the next ordinary call is checked
+        if (choice.checkable && first_check_needed(ctx, plan, ran.form)) plan->validate_due = true;
+        return XH_OK;
+    }
+    // first dataflow call on this partition on a box / build that has not passed the cross-check yet: checked like
+    // XH_ROUTE_VALIDATE
+    first_check = !validate && (check_due || (choice.checkable && first_check_needed(ctx, plan, ran.form)));
+    if (!validate && !first_check) return XH_OK;
+    const int64_t reroutes_before = ctx->reroutes, trips_before = plan->guard_trips;
     rc = route_validate(ctx, plan, nmonths, spinup_months, h_ndays, dt, d_flow_dist, d_velocity, d_area, d_runoff, d_S0,
-                        d_chstorage, d_avgchflow, d_S_end, d_F_end, flags);
-    // (a call that had to be re-routed was not routed by the dataflow kernel in the end: nothing was checked)
-    if (rc == XH_OK && ctx->reroutes == reroutes_before && (first_check || !first_checked_of(plan, last_form(plan))))
-        first_check_passed(ctx, plan, last_form(plan));
+                        d_chstorage, d_avgchflow, d_S_end, d_F_end, flags, ran.form != XH_FORM_EXACT);
+    // (a call that had to be re-routed was not routed by this partition in the end: nothing was checked)
+    if (rc == XH_OK && ctx->reroutes == reroutes_before && plan->guard_trips == trips_before &&
+        (first_check || !plan->form[ran.form].first_checked))
+        first_check_passed(ctx, plan, ran.form);
     return rc;
 }
 
 int xh_route_rerun(xh_ctx *ctx, const xh_route_record &r, bool dataflow_pairs) {
-    bool used_flow = false;
     if (!dataflow_pairs) r.plan->reroutes += 1;      // (guard re-runs are counted apart: xh_route_plan_rsum_info[6])
     int flags = r.flags & ~XH_ROUTE_TEST_FAULT;
     if (dataflow_pairs) {
@@ -280,12 +269,16 @@ int xh_route_rerun(xh_ctx *ctx, const xh_route_record &r, bool dataflow_pairs) {
         // negative runoff or initial storage, a negative outflow leaving a halo): the prepared plan is given up until the
         // plan is prepared for other data, XH_ROUTE_NO_PLAIN below routes on the plan of pairs, which assumes nothing
         r.plan->guard_trips += 1;
-        if (r.plan->last_rsum && r.plan->last_rsum_plan == r.plan->flow_rsum_fold) r.plan->fold_disabled = true;
+        if (r.ran.form == XH_FORM_PREPARED && r.ran.key == r.plan->prep_key) r.plan->fold_disabled = true;
         flags |= XH_ROUTE_NO_PLAIN;
     } else {
         flags |= XH_ROUTE_NO_DATAFLOW;
     }
-    return route_series_impl(ctx, r.plan, r.nmonths, r.spinup_months, r.ndays.data(), r.dt, r.flow_dist, r.velocity,
-                             r.area, r.runoff, r.S0, r.chs, r.avg, r.S_end, r.F_end, flags, &used_flow);
+    // (the re-run's outputs replace the call's: what it ran is what the plan reports)
+    xh_route_outcome ran;
+    const int rc = route_series_impl(ctx, r.plan, r.nmonths, r.spinup_months, r.ndays.data(), r.dt, r.flow_dist, r.velocity,
+                                     r.area, r.runoff, r.S0, r.chs, r.avg, r.S_end, r.F_end, flags, &ran);
+    if (rc == XH_OK) r.plan->last = ran;
+    return rc;
 }
 

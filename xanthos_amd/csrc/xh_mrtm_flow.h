@@ -1,6 +1,7 @@
 // Internal interface between xh_mrtm.hip (plan + API), xh_mrtm_flow.hip (tree partition + lock-step dataflow kernel) and the
 // time-skewed dataflow kernels on the same partition (xh_mrtm_wave.hip, xh_mrtm_rsum.hip; launch: xh_mrtm_wave_launch.hip).
 #pragma once
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -71,8 +72,14 @@ struct FlowIO {
 
 // Partition every tree-shaped river network (each cell drains to at most one cell, no cycle, standard UP - I rows)
 // into single-wave units linked by one-way streams (every unit in pair form).  handled[c] = 1 for the cells these units route.
-int flow_plan_build(xh_ctx *ctx, int n, const int64_t *indptr, const int32_t *indices, const int8_t *sign,
+int flow_plan_build(xh_ctx *ctx, int n, const int64_t *indptr, const int32_t *indices, const int8_t *sign, uint64_t topo_hash,
                     const std::vector<int> &comp, int ncomp, std::vector<char> &handled, FlowPlan **out);
+// The per-box cache of partitions (XH_CACHE_DIR; XH_ROUTE_LEARN_CACHE=0: off): the tables saved as `name` under xh_cache_dir()
+// when they load, are of the form asked for (`rsum`; folded leaves / single sums only if `folds` / `singles`) and pass the
+// planner's own checker; else `build`'s, saved there when they have units.  name == nullptr: no cache.  0, or build's error.
+int flow_tables_cached(const char *name, int n, const int64_t *indptr, const int32_t *indices, const int8_t *sign, bool rsum,
+                       bool folds, bool singles, FlowTables &t, std::vector<char> &handled,
+                       const std::function<int(FlowTables &, std::vector<char> &)> &build);
 // The two halves of flow_plan_build.  flow_tables_host is plain host work (no HIP call, no context).  flow_plan_upload
 // allocates and fills the device tables.
 FlowPlanOptions flow_plan_options(const xh_ctx *ctx);      // device size + the XH_FLOW_* switches of the environment
@@ -86,8 +93,8 @@ void flow_plan_info(const FlowPlan *fp, int64_t info[5]);
 int flow_launch(xh_ctx *ctx, FlowPlan *fp, const FlowSched &s, const FlowIO &io, hipStream_t st);
 // Same contract for the time-skewed kernels (k_mrtm_wave / k_mrtm_rsum, by the plan's kind); XH_ERR_LIMIT also when the
 // schedule does not suit them (months shorter than the deepest lane lag, rows wider than 4 + 1 + 4, rows beyond 32-bit
-// offsets) -- the caller then uses flow_launch.
-int wave_launch(xh_ctx *ctx, FlowPlan *fp, const FlowSched &s, const FlowIO &io, hipStream_t st);
+// offsets) -- the caller then uses flow_launch.  *place: the launch's placement words (diagnosis after a fault).
+int wave_launch(xh_ctx *ctx, FlowPlan *fp, const FlowSched &s, const FlowIO &io, hipStream_t st, unsigned **place);
 const void *wave_rsum_kernel();      // k_mrtm_rsum (xh_mrtm_rsum.hip): the kernel wave_launch starts for a reassociated plan
 const void *wave_exact_kernel();     // k_mrtm_wave (xh_mrtm_wave.hip)
 // Per-unit cycle accounting of the last launch (only when XH_FLOW_STATS=1): 6 words per unit

@@ -30,7 +30,6 @@
 //
 // Throughput is then set by the sub-step latency of ONE wave (a few hundred cycles) instead of the instruction
 // issue of the largest network, and the whole chip is busy: 1,121 units over 256 CUs for the 67,420-cell grid.
-#include <sys/stat.h>
 
 #include <algorithm>
 #include <cmath>
@@ -345,7 +344,28 @@ int flow_tables_host(FlowPlanOptions opt, int n, const int64_t *indptr, const in
     return 0;
 }
 
-int flow_plan_build(xh_ctx *ctx, int n, const int64_t *indptr, const int32_t *indices, const int8_t *sign,
+int flow_tables_cached(const char *name, int n, const int64_t *indptr, const int32_t *indices, const int8_t *sign, bool rsum,
+                       bool folds, bool singles, FlowTables &t, std::vector<char> &handled,
+                       const std::function<int(FlowTables &, std::vector<char> &)> &build) {
+    const std::string path = name ? xh_cache_path(name, false) : std::string();
+    if (!path.empty() && flow_tables_load(path.c_str(), t) && t.rsum == rsum && t.n_units > 0 &&
+        (int64_t)t.cell_of_slot.size() == (int64_t)t.n_units * LANES && (folds || t.n_folded == 0) && (singles || t.n_special < 0)) {
+        handled.assign((size_t)n, 0);
+        bool ok = true;
+        for (const std::vector<int> *cells : {&t.cell_of_slot, &t.fold_of_slot})
+            for (int c : *cells) {
+                if (c >= n) ok = false;
+                else if (c >= 0) handled[c] = 1;
+            }
+        if (ok && (rsum ? flow_tables_check_rsum : flow_tables_check)(n, indptr, indices, sign, handled, t).empty()) return 0;
+    }
+    t = FlowTables();
+    const int rc = build(t, handled);
+    if (rc == 0 && t.n_units > 0 && !path.empty()) (void)flow_tables_save(t, xh_cache_path(name, true).c_str());
+    return rc;
+}
+
+int flow_plan_build(xh_ctx *ctx, int n, const int64_t *indptr, const int32_t *indices, const int8_t *sign, uint64_t topo_hash,
                     const std::vector<int> &comp, int ncomp, std::vector<char> &handled, FlowPlan **out) {
     *out = nullptr;
     FlowTables t;
@@ -354,45 +374,17 @@ int flow_plan_build(xh_ctx *ctx, int n, const int64_t *indptr, const int32_t *in
     // The all-pairs partition of a grid is the same every time (topology, planner options, library build): 50-70 ms of host
     // time at the full grid, a few to read back.  Kept in the per-box cache (XH_CACHE_DIR; XH_ROUTE_LEARN_CACHE=0 switches the
     // caches of partitions off) and held to the planner's own invariant checker before it is used.
-    std::string cache;
+    char name[96] = "";
     if (xh_plan_cache_on() && n > 0 && !opt.debug) {
-        const std::string dir = xh_cache_dir();
-        if (!dir.empty()) {
-            uint64_t h = 1469598103934665603ull;
-            auto mix = [&](const void *p, size_t nbytes) {
-                const unsigned char *b = static_cast<const unsigned char *>(p);
-                for (size_t i = 0; i < nbytes; ++i) h = (h ^ b[i]) * 1099511628211ull;
-            };
-            const int64_t nnz = indptr[n];
-            mix(indptr, sizeof(int64_t) * (size_t)(n + 1));
-            if (nnz) mix(indices, sizeof(int32_t) * (size_t)nnz);
-            if (nnz) mix(sign, (size_t)nnz);
-            const int knobs[5] = {opt.simds, opt.piece_cap, opt.chain, opt.cut_rule, opt.tlimit};
-            mix(knobs, sizeof(knobs));
-            const char *stamp = __DATE__ " " __TIME__;
-            mix(stamp, strlen(stamp));
-            char name[96];
-            snprintf(name, sizeof(name), "/pairs_%016llx_%d.tables", (unsigned long long)h, n);
-            cache = dir + name;
-            if (flow_tables_load(cache.c_str(), t) && t.n_units > 0 && (int64_t)t.cell_of_slot.size() == (int64_t)t.n_units * LANES) {
-                handled.assign(n, 0);
-                bool ok = true;
-                for (int c : t.cell_of_slot) {
-                    if (c >= n) ok = false;
-                    else if (c >= 0) handled[c] = 1;
-                }
-                if (ok && flow_tables_check(n, indptr, indices, sign, handled, t).empty()) return flow_plan_upload(ctx, t, out);
-            }
-        }
+        const int knobs[5] = {opt.simds, opt.piece_cap, opt.chain, opt.cut_rule, opt.tlimit};
+        const uint64_t h = xh_fnv1a(xh_fnv1a(topo_hash, knobs, sizeof(knobs)), __DATE__ " " __TIME__);
+        snprintf(name, sizeof(name), "pairs_%016llx_%d.tables", (unsigned long long)h, n);
     }
-    if (flow_tables_host(opt, n, indptr, indices, sign, comp, ncomp, handled, t, err) != 0)
+    auto build = [&](FlowTables &bt, std::vector<char> &bh) {
+        return flow_tables_host(opt, n, indptr, indices, sign, comp, ncomp, bh, bt, err);
+    };
+    if (flow_tables_cached(name[0] ? name : nullptr, n, indptr, indices, sign, false, false, false, t, handled, build) != 0)
         return xh_fail(ctx, XH_ERR_ARG, "%s", err.c_str());
-    if (!cache.empty() && t.n_units > 0) {
-        const std::string dir = cache.substr(0, cache.rfind('/'));
-        for (size_t i = 1; i <= dir.size(); ++i)      // mkdir -p
-            if (i == dir.size() || dir[i] == '/') (void)mkdir(dir.substr(0, i).c_str(), 0755);
-        (void)flow_tables_save(t, cache.c_str());
-    }
     return flow_plan_upload(ctx, t, out);
 }
 

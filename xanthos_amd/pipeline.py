@@ -125,7 +125,7 @@ class DevicePipeline:
         def make():
             try:
                 self._plan = um.plan(ctx)
-                self._plan.prepare(flow_dist, velocity, 10800.0)      # selective tables ahead of the first call, if known
+                self._plan.prepare(flow_dist, velocity, 10800.0)      # the prepared plan (folded leaves, single sums) ahead of the first call
             except BaseException as exc:      # re-raised by `plan`
                 self._plan_error = exc
         self._plan_thread = threading.Thread(target=make, name='xh-route-plan')
