@@ -444,6 +444,40 @@ int xh_calib_objective_multi(xh_ctx *ctx, int32_t nbasins, const int64_t *h_ncel
                              const double *const *h_precip_t, const double *const *h_tmin_t,
                              const double *const *h_area, const double *h_obs, double *h_ed, double *h_series);
 
+/* ------------------------------------------------------------------ streamflow objective (set_calibrate = 1)
+ * ABCD on the basin's cells (spin-up and initial state as above), the runoff scattered onto the basin's upstream
+ * closure through UM (foreign cells of the closure carry zero runoff and their own initial storage), MRTM over the
+ * closure (routing_spinup months, then all nmonths with the carried storage; dt seconds per sub-step, the day counts
+ * of h_ndays), the basin's outlet series = sum of Avg_ChFlow over its outlets in ascending cell order [m3/s], scored
+ * against h_obs with ED = 1 - KGE.  Host tables of every basin's closure, rows concatenated basin after basin:
+ *   h_closure_ptr [nbasins + 1]  first row of each basin's closure; rows in ascending cell order
+ *   h_row_ptr [ncl + 1], h_cols [nnz], h_sign [nnz]   the closure's rows of UM, columns closure-local, stored order
+ *   h_basin_col [ncl]    column of the basin's forcing ([nmonths, ncell_b]) of a closure row, -1 outside the basin
+ *   h_outlet_rank [ncl]  rank of the row among its basin's outlets (0, 1, ... ascending), -1 for other rows
+ *   h_tauinv, h_area, h_s0 [ncl]   ChV / L, cell area (km2), initial channel storage (m3)
+ * A closure holds at most 3072 cells.                                                                          */
+typedef struct {
+    int32_t routing_spinup;
+    double dt;
+    const int32_t *h_ndays;
+    const int64_t *h_closure_ptr;
+    const int64_t *h_row_ptr;
+    const int32_t *h_cols;
+    const int8_t *h_sign;
+    const int32_t *h_basin_col;
+    const int32_t *h_outlet_rank;
+    const double *h_tauinv;
+    const double *h_area;
+    const double *h_s0;
+} xh_calib_flow_desc;
+
+/* As xh_calib_objective_multi (no h_area: the routing tables carry the areas); h_series [nbasins, nmembers, nmonths]
+ * optional out = the outlet series.                                                                            */
+int xh_calib_flow_objective_multi(xh_ctx *ctx, int32_t nbasins, const int64_t *h_ncell, int32_t nmonths, int32_t spinup,
+                                  int32_t nmembers, int32_t npar, const double *h_pars, const double *const *h_pet_t,
+                                  const double *const *h_precip_t, const double *const *h_tmin_t,
+                                  const xh_calib_flow_desc *flow, const double *h_obs, double *h_ed, double *h_series);
+
 /* ------------------------------------------------------------------ differential evolution on the device
  * Replaces the scipy.optimize.differential_evolution call of calibrate/calibrate_abcd.py:calibrate_basin (:103-112,
  * SciPy defaults: best1bin, Latin-hypercube start, dither (0.5, 1), recombination 0.7, tol 0.01, polish off) AND the
@@ -469,6 +503,12 @@ int xh_calib_de_create(xh_ctx *ctx, int32_t nbasins, const int64_t *h_ncell, con
                        const double *const *h_pet_t, const double *const *h_precip_t, const double *const *h_tmin_t,
                        const double *const *h_area, const double *h_obs, const double *h_lo, const double *h_hi,
                        uint64_t seed, xh_calib_de **out);
+/* The same search on the streamflow objective (xh_calib_flow_objective_multi's tables; no h_area).               */
+int xh_calib_de_create_flow(xh_ctx *ctx, int32_t nbasins, const int64_t *h_ncell, const uint64_t *h_basin_key,
+                            int32_t nmonths, int32_t spinup, int32_t nmembers, int32_t npar,
+                            const double *const *h_pet_t, const double *const *h_precip_t,
+                            const double *const *h_tmin_t, const xh_calib_flow_desc *flow, const double *h_obs,
+                            const double *h_lo, const double *h_hi, uint64_t seed, xh_calib_de **out);
 void xh_calib_de_destroy(xh_calib_de *de);
 int xh_calib_de_init(xh_calib_de *de);
 int xh_calib_de_step(xh_calib_de *de, int32_t ngen, double tol, double atol, double mut_lo, double mut_hi,

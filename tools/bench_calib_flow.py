@@ -1,0 +1,96 @@
+"""Streamflow calibration (set_calibrate = 1) at full size: the synthetic 67,420-cell world, 235 basins, 75 members
+(popsize 15 x 5 parameters), 480 months, runoff spin-up 120, routing spin-up 120 months.  Times device DE generations on
+the streamflow objective (csrc/xh_calib_flow.hip) and reports seconds per generation, member-cell-sub-steps per second
+and the fraction of the fp64 issue rate the sub-steps reach (one wave-instruction per SIMD per 4 cycles, 256 CUs x 4
+SIMDs, at the clock given; INSTR fp64 lane-instructions per member-cell-sub-step, counted from the kernel's no-fire
+path: F = S tau, the gather's adds (about two entries per row), + erl, x dt, the compare, S + d, the next F, favg += F).
+
+    python tools/bench_calib_flow.py [--members 75] [--gens 2] [--clock-ghz 2.4] [--instr 9]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+from types import SimpleNamespace
+
+import numpy as np
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
+from xanthos_amd import _hip, synth  # noqa: E402
+from xanthos_amd.calibrate.flow_tables import FlowTables  # noqa: E402
+from xanthos_amd.routing import mrtm  # noqa: E402
+from xanthos_amd.utils import set_month_arrays  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--members', type=int, default=75)
+    ap.add_argument('--gens', type=int, default=2)
+    ap.add_argument('--months', type=int, default=480)
+    ap.add_argument('--spinup', type=int, default=120)
+    ap.add_argument('--routing-spinup', type=int, default=120)
+    ap.add_argument('--clock-ghz', type=float, default=2.4)
+    ap.add_argument('--instr', type=float, default=9.0)
+    a = ap.parse_args()
+    nm, spin, rspin, members = a.months, a.spinup, a.routing_spinup, a.members
+    ctx = _hip.get_context(0)
+    t0 = time.perf_counter()
+    w = synth.make_world()
+    f = {k: ctx.empty((w.ncell, nm)) for k in synth.FORCING_NAMES}
+    ctx.synth_forcing(5, w.ncell, nm, ctx.upload(w.latitude), f, nan_frac=0.0)
+    st = SimpleNamespace(ngridrow=w.nrow, ngridcol=w.ncol)
+    um = mrtm.upstream_genmatrix(mrtm.upstream(w.coords, mrtm.downstream(w.coords, w.flow_dir, st), st))
+    ndays = set_month_arrays(nm, 1971, 1971 + nm // 12 - 1)[:, 2]
+    basins = list(range(1, w.n_basins + 1))
+    rng = np.random.default_rng(0)
+    ft = FlowTables(um, w.basin_ids, basins, w.flow_dist, w.velocity, w.area, None, ndays, nm, rspin)
+    # per basin: forcing rows gathered and transposed to [month, cell] ('rsds', 30..330, stands in for PET)
+    pet_t, pr_t, tn_t = [], [], []
+    for cells in ft.basin_cells:
+        n = cells.size
+        rows = ctx.upload(cells, dtype=np.int64)
+        for k, lst in (('rsds', pet_t), ('precip', pr_t), ('abcd_tmin', tn_t)):
+            tmp = ctx.empty((n, nm))
+            ctx.gather_rows(f[k], rows, n, nm, tmp)
+            t = ctx.empty((nm, n))
+            ctx.transpose(tmp, n, nm, t)
+            tmp.free()
+            lst.append(t)
+        rows.free()
+    ctx.sync()
+    obs = rng.uniform(50, 500, (len(basins), nm))
+    bounds = [(1e-4, 1 - 1e-4), (1e-4, 8 - 1e-4), (1e-4, 1 - 1e-4), (1e-4, 1 - 1e-4), (1e-4, 1 - 1e-4)]
+    setup = time.perf_counter() - t0
+    de = _hip.CalibDE(ctx, [c.size for c in ft.basin_cells], nm, spin, members, bounds, pet_t, pr_t, tn_t, None, obs,
+                      seed=7, keys=basins, flow=ft)
+    t1 = time.perf_counter()
+    de.init()
+    t_init = time.perf_counter() - t1
+    gens = []
+    for _ in range(a.gens):
+        ctx.timing_reset()
+        t1 = time.perf_counter()
+        de.step(1, tol=0.0)
+        gens.append(time.perf_counter() - t1)
+    ms_flow, _ = ctx.timing('calib_flow')
+    ms_spin, _ = ctx.timing('calib_abcd')
+    de.close()
+    nt = np.floor(ndays.astype(np.int64) * 86400 / 10800).astype(np.int64)
+    subs = int(nt[:rspin].sum() + nt.sum())
+    cells = int(sum(c.size for c in ft.closures))
+    mcs = cells * members * subs
+    sec = min(gens)
+    rate = mcs / sec
+    peak = 256 * 4 * 64 * a.clock_ghz * 1e9 / 4             # fp64 lane-instructions per second at full issue
+    res = dict(world_cells=int(w.ncell), basins=len(basins), closure_cells=cells, largest_closure=int(max(c.size for c in ft.closures)),
+               members=members, months=nm, routing_spinup=rspin, substeps=subs, member_cell_substeps=mcs,
+               setup_s=round(setup, 2), init_s=round(t_init, 3), generation_s=[round(g, 3) for g in gens],
+               kernels_last_generation_ms=dict(calib_flow=round(ms_flow, 1), calib_abcd=round(ms_spin, 1)),
+               member_cell_substeps_per_s=float('%.4g' % rate), instr_per_member_cell_substep=a.instr,
+               clock_ghz=a.clock_ghz, fp64_issue_fraction=round(rate * a.instr / peak, 4))
+    print(json.dumps(res))
+
+
+if __name__ == '__main__':
+    main()

@@ -50,6 +50,20 @@ class FusedArgs(Structure):
                 [('block_months', c_int32), ('mode', c_int32)])
 
 
+class CalibFlowDesc(Structure):
+    """xh_calib_flow_desc (include/xanthos_hip.h): closure tables of the streamflow objective."""
+    _fields_ = [('routing_spinup', c_int32), ('dt', c_double)] + [(n, c_void_p) for n in (
+        'h_ndays', 'h_closure_ptr', 'h_row_ptr', 'h_cols', 'h_sign', 'h_basin_col', 'h_outlet_rank', 'h_tauinv', 'h_area',
+        'h_s0')]
+
+
+def flow_desc(tables):
+    """CalibFlowDesc over the arrays of ``tables`` (calibrate.flow_tables.FlowTables); keep ``tables`` alive."""
+    t = tables
+    return CalibFlowDesc(int(t.routing_spinup), float(t.dt), *[_host_ptr(a) for a in (
+        t.ndays, t.closure_ptr, t.row_ptr, t.cols, t.sign, t.basin_col, t.outlet_rank, t.tauinv, t.area, t.s0)])
+
+
 _P = c_void_p
 # name -> (restype, argtypes); mirrors include/xanthos_hip.h one to one
 SIGNATURES = {
@@ -101,6 +115,10 @@ SIGNATURES = {
     'xh_calib_objective_multi': (c_int, [_P, c_int32, _P, c_int32, c_int32, c_int32, c_int32, _P, _P, _P, _P, _P, _P, _P, _P]),
     'xh_calib_de_create': (c_int, [_P, c_int32, _P, _P, c_int32, c_int32, c_int32, c_int32, _P, _P, _P, _P, _P, _P, _P,
                                    c_uint64, POINTER(c_void_p)]),
+    'xh_calib_flow_objective_multi': (c_int, [_P, c_int32, _P, c_int32, c_int32, c_int32, c_int32, _P, _P, _P, _P,
+                                              POINTER(CalibFlowDesc), _P, _P, _P]),
+    'xh_calib_de_create_flow': (c_int, [_P, c_int32, _P, _P, c_int32, c_int32, c_int32, c_int32, _P, _P, _P,
+                                        POINTER(CalibFlowDesc), _P, _P, _P, c_uint64, POINTER(c_void_p)]),
     'xh_calib_de_destroy': (None, [_P]),
     'xh_calib_de_init': (c_int, [_P]),
     'xh_calib_de_step': (c_int, [_P, c_int32, c_double, c_double, c_double, c_double, c_double, POINTER(c_int32)]),
@@ -513,6 +531,26 @@ class Context:
                                                    _host_ptr(series) if want_series else None))
         return (ed, series) if want_series else ed
 
+    def calib_flow_objective_multi(self, ncells, nmonths, spinup, pars, pet_t, precip_t, tmin_t, tables, obs,
+                                   want_series=False):
+        """Streamflow objective (set_calibrate = 1) of several basins at once: as calib_objective_multi, with the
+        closure tables ``tables`` (calibrate.flow_tables.FlowTables) instead of areas. series = outlet flow [m3/s]."""
+        pars = as_f64(pars)
+        nb, nmem, npar = pars.shape
+        obs = as_f64(obs)
+        if obs.shape != (nb, nmonths):
+            raise ValueError('obs must be [nbasins, nmonths]')
+        nc = np.ascontiguousarray(ncells, dtype=np.int64)
+        ptrs = lambda lst: None if lst is None else (c_void_p * nb)(*[_dptr(x) for x in lst])
+        desc = flow_desc(tables)
+        ed = np.empty((nb, nmem))
+        series = np.empty((nb, nmem, nmonths)) if want_series else None
+        self._check(lib().xh_calib_flow_objective_multi(self.handle, nb, _host_ptr(nc), nmonths, spinup, nmem, npar,
+                                                        _host_ptr(pars), ptrs(pet_t), ptrs(precip_t), ptrs(tmin_t),
+                                                        byref(desc), _host_ptr(obs), _host_ptr(ed),
+                                                        _host_ptr(series) if want_series else None))
+        return (ed, series) if want_series else ed
+
     # ---- output aggregation
     def agg_time(self, ncell, ncols, group, mode, scale, src, dst):
         self._check(lib().xh_agg_time(self.handle, ncell, ncols, group, mode, _dptr(scale), _dptr(src), _dptr(dst)))
@@ -707,7 +745,7 @@ class CalibDE:
     stream of each basin (e.g. the basin number) so that a basin's search does not depend on its companions."""
 
     def __init__(self, ctx, ncells, nmonths, spinup, nmembers, bounds, pet_t, precip_t, tmin_t, area, obs, seed=0,
-                 keys=None):
+                 keys=None, flow=None):
         self.ctx = ctx
         nc = np.ascontiguousarray(ncells, dtype=np.int64)
         self.nb, self.n, self.d = int(nc.size), int(nmembers), len(bounds)
@@ -719,6 +757,14 @@ class CalibDE:
         ptrs = lambda lst: None if lst is None else (c_void_p * self.nb)(*[_dptr(x) for x in lst])
         self._keep = (pet_t, precip_t, tmin_t, area)
         h = c_void_p()
+        if flow is not None:        # the streamflow objective: flow = calibrate.flow_tables.FlowTables (copied at creation)
+            ctx._check(lib().xh_calib_de_create_flow(ctx.handle, self.nb, _host_ptr(nc),
+                                                     None if kk is None else _host_ptr(kk), nmonths, spinup, self.n, self.d,
+                                                     ptrs(pet_t), ptrs(precip_t), ptrs(tmin_t), byref(flow_desc(flow)),
+                                                     _host_ptr(obs), _host_ptr(lo), _host_ptr(hi),
+                                                     int(seed) & 0xFFFFFFFFFFFFFFFF, byref(h)))
+            self.handle = h.value
+            return
         ctx._check(lib().xh_calib_de_create(ctx.handle, self.nb, _host_ptr(nc), None if kk is None else _host_ptr(kk),
                                             nmonths, spinup, self.n, self.d, ptrs(pet_t), ptrs(precip_t), ptrs(tmin_t),
                                             ptrs(area), _host_ptr(obs), _host_ptr(lo), _host_ptr(hi),

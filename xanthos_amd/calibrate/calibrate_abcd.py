@@ -12,9 +12,12 @@ like SciPy's ``updating='deferred'``, for ALL requested basins at once instead o
 trajectory is not reproducible; the objective is the parity target (tests/golden/kge.npz) and the generation step is
 checked against a numpy restatement of SciPy's (oracle/de.py).
 
-``set_calibrate = 1`` (calibrate against routed stream flow) is not offered: in the reference that branch hands the
-whole ``[ncell, nmonths]`` Avg_ChFlow array to ``np.corrcoef`` against a 1-D observation series (:165-173, :196-213),
-which cannot produce a basin score.
+``set_calibrate = 1`` calibrates against observed streamflow (``m3_per_sec``) with the objective of DESIGN 4.4: the
+basin's runoff scattered onto its upstream closure through UM, routed by MRTM (routing spin-up, then all months) and
+summed over the basin's outlets.  The reference's branch cannot run (a flat ``np.put`` of the runoff, :170-171, and the
+whole ``[ncell, nmonths]`` Avg_ChFlow handed to ``np.corrcoef``, :173, :196-213); this is its evident intent.  Each
+basin routes its own closure on the device (flow_tables.py, csrc/xh_calib_flow.hip); ``router_func`` is accepted for
+signature compatibility and not called.
 """
 import logging
 import os
@@ -23,6 +26,7 @@ import time
 import numpy as np
 
 from .. import _hip
+from .flow_tables import FlowTables, check_forcing
 
 LB = 1e-4
 UB = 1 - LB
@@ -31,8 +35,12 @@ UB = 1 - LB
 class BasinObjective:
     """ED = 1 - KGE of the basin runoff for batches of parameter vectors (basin_runoff + objective_kge, :134-213)."""
 
-    def __init__(self, pet, precip, tmin, n_months, runoff_spinup, obs_unit, bsn_areas, bsn_robs, device=0):
-        if obs_unit not in ('km3_per_mth', 'mm_per_mth'):
+    def __init__(self, pet, precip, tmin, n_months, runoff_spinup, obs_unit, bsn_areas, bsn_robs, device=0,
+                 set_calibrate=0):
+        if set_calibrate == 1:
+            if obs_unit != 'm3_per_sec':
+                raise ValueError('obs_unit must be m3_per_sec for set_calibrate = 1')
+        elif obs_unit not in ('km3_per_mth', 'mm_per_mth'):
             raise ValueError('obs_unit must be km3_per_mth or mm_per_mth for set_calibrate = 0')
         if runoff_spinup < 25:
             raise IndexError('Spin-up steps must produce at least 25 months of spin-up; got {}'.format(runoff_spinup))
@@ -45,11 +53,14 @@ class BasinObjective:
         self.d_pet, self.d_precip = tr(pet), tr(precip)
         # the loader's np.nan_to_num of TempMinFile (data_load.py:194-195); precipitation keeps its NaNs (:186)
         self.d_tmin = None if self.nosnow else self.ctx.nan_to_num(tr(tmin))
-        self.d_area = self.ctx.upload(bsn_areas) if obs_unit == 'km3_per_mth' else None
+        self.d_area = self.ctx.upload(bsn_areas) if obs_unit == 'km3_per_mth' else None   # (m3_per_sec: in the routing tables)
         self.obs = np.ascontiguousarray(np.asarray(bsn_robs, dtype=np.float64)[:n_months])
+        self.obs_unit = obs_unit
         self.nfev = 0
 
     def __call__(self, pars, want_series=False):
+        if self.obs_unit == 'm3_per_sec':
+            raise TypeError('the streamflow objective needs the routing tables: evaluate through BasinSet')
         pars = np.atleast_2d(np.asarray(pars, dtype=np.float64))[:, :self.npar]
         self.nfev += pars.shape[0]
         return self.ctx.calib_objective(self.ncell, self.n_months, self.spinup, pars, self.d_pet, self.d_precip,
@@ -64,8 +75,15 @@ class BasinObjective:
 class BasinSet:
     """Several basins prepared for the device: forcing transposed to [month, cell] in HBM, observations, bounds."""
 
-    def __init__(self, cals, n_months, runoff_spinup, obs_unit, device=0):
+    def __init__(self, cals, n_months, runoff_spinup, obs_unit, device=0, flow=None):
         self.cals = cals
+        # set_calibrate = 1: the closure tables of these basins in this order (``flow``, or those of the Calibrates)
+        self.flow = None
+        if obs_unit == 'm3_per_sec':
+            self.flow = flow if flow is not None else FlowTables.join([c.flow for c in cals])
+            if self.flow.basins != [c.basin_num for c in cals]:
+                raise ValueError('the flow tables hold basins {}, not {}'.format(self.flow.basins,
+                                                                                  [c.basin_num for c in cals]))
         self.objs = [c.objective() for c in cals]
         self.ctx = self.objs[0].ctx
         self.nosnow, self.npar = self.objs[0].nosnow, self.objs[0].npar
@@ -79,16 +97,20 @@ class BasinSet:
                 None if self.nosnow else [x.d_tmin for x in o],
                 None if o[0].d_area is None else [x.d_area for x in o])
 
-    def evaluate(self, pars):
-        """ED for parameter sets pars [nbasins, nmembers, npar] in ONE launch."""
+    def evaluate(self, pars, want_series=False):
+        """ED for parameter sets pars [nbasins, nmembers, npar] in ONE launch (and the modelled series)."""
         nc, pet, pr, tn, ar = self.args()
-        return self.ctx.calib_objective_multi(nc, self.n_months, self.spinup, np.asarray(pars)[:, :, :self.npar], pet,
-                                              pr, tn, ar, self.obs)
+        pars = np.asarray(pars)[:, :, :self.npar]
+        if self.flow is not None:
+            return self.ctx.calib_flow_objective_multi(nc, self.n_months, self.spinup, pars, pet, pr, tn, self.flow,
+                                                       self.obs, want_series=want_series)
+        return self.ctx.calib_objective_multi(nc, self.n_months, self.spinup, pars, pet, pr, tn, ar, self.obs,
+                                              want_series=want_series)
 
     def solver(self, nmembers, seed=0):
         nc, pet, pr, tn, ar = self.args()
         return _hip.CalibDE(self.ctx, nc, self.n_months, self.spinup, nmembers, self.bounds, pet, pr, tn, ar, self.obs,
-                            seed=seed, keys=[c.basin_num for c in self.cals])
+                            seed=seed, keys=[c.basin_num for c in self.cals], flow=self.flow)
 
     def close(self):
         for o in self.objs:
@@ -126,9 +148,22 @@ class Calibrate:
     """Calibrate the ABCD runoff module for one basin; constructor as calibrate_abcd.Calibrate (:20-88)."""
 
     def __init__(self, basin_num, basin_ids, basin_areas, precip, pet, obs, tmin, n_months, runoff_spinup,
-                 set_calibrate, obs_unit, out_dir, router_func=None, device=0, seed=None):
-        if set_calibrate != 0:
-            raise NotImplementedError('set_calibrate = 1 (stream flow) is not supported; see the module docstring')
+                 set_calibrate, obs_unit, out_dir, router_func=None, device=0, seed=None, um=None, flow_dist=None,
+                 velocity=None, chs_prev=None, ndays=None, routing_spinup=0, dt=10800, flow=None):
+        """set_calibrate = 1 also needs the routing inputs: ``um`` (routing.mrtm.upstream_genmatrix), ``flow_dist``,
+        ``velocity``, ``chs_prev`` (None = zeros), ``ndays`` [nmonths] and ``routing_spinup`` -- or ``flow``, this
+        basin's FlowTables.  ``router_func`` is kept for the reference's signature and not called."""
+        if set_calibrate not in (0, 1):
+            raise ValueError('set_calibrate must be 0 or 1')
+        self.flow = None
+        if set_calibrate == 1:
+            if flow is None:
+                if um is None or flow_dist is None or velocity is None or ndays is None:
+                    raise ValueError('set_calibrate = 1 needs um, flow_dist, velocity and ndays (or flow)')
+                check_forcing([basin_num], basin_ids, pet, precip, n_months)
+                flow = FlowTables(um, basin_ids, [basin_num], flow_dist, velocity, basin_areas, chs_prev, ndays, n_months,
+                                  routing_spinup, dt=dt)
+            self.flow = flow
         self.basin_num, self.n_months, self.runoff_spinup = basin_num, n_months, runoff_spinup
         self.set_calibrate, self.obs_unit, self.out_dir, self.seed = set_calibrate, obs_unit, out_dir, seed
         self.nosnow = tmin is None
@@ -149,7 +184,8 @@ class Calibrate:
 
     def objective(self):
         return BasinObjective(self.bsn_PET, self.bsn_P, self.bsn_TMIN, self.n_months, self.runoff_spinup,
-                              self.obs_unit, self.bsn_areas, self.bsn_Robs, device=self.device)
+                              self.obs_unit, self.bsn_areas, self.bsn_Robs, device=self.device,
+                              set_calibrate=self.set_calibrate)
 
     def calibrate_basin(self, popsize=15, polish=False):
         """Optimise (a, b, c, d[, m]) for maximum KGE and save the results (:90-131)."""
@@ -204,14 +240,28 @@ def expand_str_range(str_ranges):
     return out
 
 
-def process_basin(basin_num, settings, data, pet, router_function=None):
+def process_basin(basin_num, settings, data, pet, router_function=None, um=None, ndays=None, dt=10800):
+    flow = None
+    if settings.set_calibrate == 1:
+        flow = flow_tables(settings, data, pet, [basin_num], um, ndays, dt)
     cal = Calibrate(basin_num=basin_num, set_calibrate=settings.set_calibrate, obs_unit=settings.obs_unit,
                     basin_ids=data.basin_ids, basin_areas=data.area, precip=data.precip, pet=pet, obs=data.cal_obs,
                     tmin=data.tmin, n_months=settings.nmonths, runoff_spinup=settings.runoff_spinup,
                     router_func=router_function, out_dir=settings.calib_out_dir,
-                    device=getattr(settings, 'device', 0))
+                    device=getattr(settings, 'device', 0), flow=flow)
     cal.calibrate_basin()
     return cal
+
+
+def flow_tables(settings, data, pet, basins, um, ndays, dt=10800):
+    """set_calibrate = 1: check the forcing of ``basins`` and build their closure tables from the run's routing inputs
+    (``um`` = the topology routing uses, ``ndays`` [nmonths] the days of each month)."""
+    if um is None or ndays is None:
+        raise ValueError('set_calibrate = 1 needs the routing topology (um) and the day counts (ndays)')
+    check_forcing(basins, data.basin_ids, pet, data.precip, settings.nmonths)
+    return FlowTables(um, data.basin_ids, basins, data.flow_dist, data.str_velocity, data.area,
+                      getattr(data, 'chs_prev', None), ndays, settings.nmonths, getattr(settings, 'routing_spinup', 0),
+                      dt=dt)
 
 
 def assign_basins(sizes, n_ranks):
@@ -242,20 +292,23 @@ def gather_results(local, owner, group, root=0):
     return table
 
 
-def _make_calibrate(b, settings, data, pet):
-    return Calibrate(basin_num=b, set_calibrate=0, obs_unit=settings.obs_unit, basin_ids=data.basin_ids,
-                     basin_areas=data.area, precip=data.precip, pet=pet, obs=data.cal_obs, tmin=data.tmin,
-                     n_months=settings.nmonths, runoff_spinup=settings.runoff_spinup, out_dir=settings.calib_out_dir,
-                     device=getattr(settings, 'device', 0))
+def _make_calibrate(b, settings, data, pet, flow=None):
+    return Calibrate(basin_num=b, set_calibrate=settings.set_calibrate, obs_unit=settings.obs_unit,
+                     basin_ids=data.basin_ids, basin_areas=data.area, precip=data.precip, pet=pet, obs=data.cal_obs,
+                     tmin=data.tmin, n_months=settings.nmonths, runoff_spinup=settings.runoff_spinup,
+                     out_dir=settings.calib_out_dir, device=getattr(settings, 'device', 0),
+                     flow=None if flow is None else flow.subset([b]))
 
 
-def _calibrate_local(mine, settings, data, pet, seed, popsize, nmembers):
-    """This rank's share: rows [len(mine), npar + 3] = (parameters, ED, nfev, nit) and {basin: Calibrate}."""
+def _calibrate_local(mine, settings, data, pet, seed, popsize, nmembers, flow=None):
+    """This rank's share: rows [len(mine), npar + 3] = (parameters, ED, nfev, nit) and {basin: Calibrate}.
+    ``flow`` (set_calibrate = 1): the closure tables of at least these basins."""
     npar = 5 if data.tmin is not None else 4
     if not mine:
         return np.zeros((0, npar + 3)), {}
-    cals = [_make_calibrate(b, settings, data, pet) for b in mine]
-    bset = BasinSet(cals, settings.nmonths, settings.runoff_spinup, settings.obs_unit)
+    cals = [_make_calibrate(b, settings, data, pet, flow) for b in mine]
+    bset = BasinSet(cals, settings.nmonths, settings.runoff_spinup, settings.obs_unit,
+                    flow=None if flow is None else flow.subset(mine))
     try:
         x, ed, nfev, nit = differential_evolution_device(bset, popsize=popsize, seed=seed, nmembers=nmembers)
     finally:
@@ -263,16 +316,19 @@ def _calibrate_local(mine, settings, data, pet, seed, popsize, nmembers):
     return np.column_stack([x, ed, nfev, nit]), dict(zip(mine, cals))
 
 
-def calibrate_all(settings, data, pet, router_function=None, seed=None, popsize=15, nmembers=None, group=None):
+def calibrate_all(settings, data, pet, router_function=None, seed=None, popsize=15, nmembers=None, group=None, um=None,
+                  ndays=None, dt=10800):
     """Calibrate every requested basin (:256-262).
 
     All basins search in lock-step on the device (differential_evolution_device).  ``group`` = the job's process group
     (``launch.current_group()``; None = one rank): the basins are dealt to the ranks by size (every rank needs the same
     ``seed``), each rank calibrates its share on its own GPU, and rank 0 receives all results in one collective.  Writes the
     reference's two files per basin (:130-131; on rank 0) and returns {basin: (parameters, kge)} (rank 0; {} elsewhere).
+    set_calibrate = 1 also needs ``um`` (the routing topology), ``ndays`` [nmonths] and ``dt``; ``data`` then carries
+    flow_dist, str_velocity and chs_prev, and the basins are dealt by closure cells x (nmonths + routing_spinup).
     """
-    if settings.set_calibrate != 0:
-        raise NotImplementedError('set_calibrate = 1 (stream flow) is not supported; see the module docstring')
+    if settings.set_calibrate not in (0, 1):
+        raise ValueError('set_calibrate must be 0 or 1')
     basins = expand_str_range(settings.cal_basins)
     basin_ids = np.asarray(data.basin_ids)
     sizes = np.array([(basin_ids == b).sum() for b in basins])
@@ -283,11 +339,18 @@ def calibrate_all(settings, data, pet, router_function=None, seed=None, popsize=
     rank, n_ranks = (group.rank, group.size) if group is not None else (0, 1)
     if n_ranks > 1 and seed is None:
         raise ValueError('a multi-rank calibration needs the same explicit seed on every rank')
-    owner = assign_basins(sizes * settings.nmonths, n_ranks)
-    mine = [b for b, r in zip(basins, owner) if r == rank]
     st = time.time()
     npar = 5 if data.tmin is not None else 4
-    local, cals = _calibrate_local(mine, settings, data, pet, seed, popsize, nmembers)
+    if settings.set_calibrate == 1:
+        flow = flow_tables(settings, data, pet, basins, um, ndays, dt)
+        owner = assign_basins(flow.weights, n_ranks)
+        mine = [b for b, r in zip(basins, owner) if r == rank]
+        local, cals = _calibrate_local(mine, settings, data, pet, seed, popsize, nmembers, flow=flow)
+    else:
+        flow = None
+        owner = assign_basins(sizes * settings.nmonths, n_ranks)
+        mine = [b for b, r in zip(basins, owner) if r == rank]
+        local, cals = _calibrate_local(mine, settings, data, pet, seed, popsize, nmembers)
     table = gather_results(local, owner, group) if n_ranks > 1 else local
     if rank != 0:
         return {}
@@ -295,7 +358,7 @@ def calibrate_all(settings, data, pet, router_function=None, seed=None, popsize=
         len(basins), n_ranks, time.time() - st, int(table[:, npar + 1].sum())))
     results = {}
     for b, row in zip(basins, table):
-        c = cals[b] if b in cals else _make_calibrate(b, settings, data, pet)
+        c = cals[b] if b in cals else _make_calibrate(b, settings, data, pet, flow)
         c._store(row[:npar], row[npar], int(row[npar + 1]))
         results[b] = (row[:npar].copy(), 1 - row[npar])
     return results

@@ -337,8 +337,11 @@ class Components:
         pet_out = self.calculate_pet()
         multi = self.group is not None and self.group.size > 1
         # (several ranks: the basins are dealt over them; the search needs the same explicit seed on every rank)
+        flow = {}
+        if self.s.set_calibrate == 1:       # streamflow: each basin is routed on its own closure of the run's topology
+            flow = dict(um=self.topology(), ndays=self.yr_imth_dys[:, 2], dt=self.routing_timestep_hours)
         calib_mod.calibrate_all(settings=self.s, data=self.data, pet=pet_out, router_function=self.calculate_routing,
-                                group=self.group if multi else None, seed=20240807 if multi else None)
+                                group=self.group if multi else None, seed=20240807 if multi else None, **flow)
 
     def drought(self):
         """Drought statistics of runoff or soil moisture (components.py:391-399)."""

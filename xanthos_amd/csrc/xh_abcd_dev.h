@@ -37,6 +37,20 @@ __device__ __forceinline__ double quot(double x, double d, double inv_d) {
     return __builtin_fma(__builtin_fma(-d, q, x), inv_d, q);
 }
 
+// Parameters of one calibration member: row `row` of pars [*, npar] = (a, b, c, d[, m]), b in the reference's units
+// (x 1000, abcd.py:48).  The runoff and the streamflow objectives both map a member this way.
+__device__ __forceinline__ AbcdPar calib_par(const double *__restrict__ pars, int npar, int64_t row) {
+    const double *p = pars + row * npar;
+    AbcdPar P;
+    const double a = p[0];
+    P.b = p[1] * 1000.0;
+    P.c = p[2];
+    P.d = p[3];
+    P.m = npar > 4 ? p[4] : 0.0;
+    finish_par(P, a);
+    return P;
+}
+
 struct AbcdState {
     double snowpack, sm, gw;
 };

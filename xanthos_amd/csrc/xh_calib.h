@@ -31,6 +31,9 @@ struct xh_calib_problem {
     double *d_part = nullptr;                 // [nchunks, nmembers, nmonths]
     double *d_series = nullptr;               // [nbasins, nmembers, nmonths]
     double *d_series_m = nullptr;             // member-lane layout: [nbasins, nmonths, nmembers]
+    // streamflow objective (set_calibrate = 1; xh_calib_flow.hip): closures, routing tables and launch lists of the
+    // basins, owned by whoever made the problem; NULL = the runoff objective
+    struct xh_calib_flow *flow = nullptr;
 };
 
 // Validates the arguments, fills the host tables and returns the bytes xh_calib_problem_place needs.
@@ -49,3 +52,16 @@ int xh_calib_series_out(xh_ctx *ctx, const xh_calib_problem &P);
 // d_ed [nbasins, nmembers] (ED = 1 - KGE).  d_active [nbasins] (may be NULL): basins with 0 are skipped and their
 // d_ed entries left untouched.  No host synchronisation.
 int xh_calib_enqueue(xh_ctx *ctx, const xh_calib_problem &P, const double *d_pars, const int *d_active, double *d_ed);
+
+// The pieces of xh_calib_enqueue the streamflow objective shares: the spin-up march + basin-mean initial state
+// (P.d_sm0, P.d_gw0) in the problem's layout, and ED of series [nbasins, nmembers, nmonths] against P.d_obs.
+int xh_calib_spinup_enqueue(xh_ctx *ctx, const xh_calib_problem &P, const double *d_pars, const int *d_active);
+int xh_calib_kge_enqueue(xh_ctx *ctx, const xh_calib_problem &P, const int *d_active, const double *d_series, double *d_ed);
+
+// Streamflow objective (xh_calib_flow.hip).  create: validates and uploads the closure tables of `desc` for a problem of
+// nbasins basins (h_ncell basin cells each) and nmembers members; enqueue: spin-up, the fused ABCD + routing march and
+// ED into d_ed (d_active as for xh_calib_enqueue).
+int xh_calib_flow_create(xh_ctx *ctx, int32_t nbasins, const int64_t *h_ncell, int32_t nmonths, int32_t nmembers,
+                         const xh_calib_flow_desc *desc, xh_calib_flow **out);
+void xh_calib_flow_destroy(xh_calib_flow *f);
+int xh_calib_flow_enqueue(xh_ctx *ctx, const xh_calib_problem &P, const double *d_pars, const int *d_active, double *d_ed);

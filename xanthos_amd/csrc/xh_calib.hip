@@ -53,18 +53,6 @@ __device__ __forceinline__ double wave_sum(double v) {
     return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
 }
 
-__device__ __forceinline__ AbcdPar member_par(const double *__restrict__ pars, int npar, int member) {
-    const double *p = pars + (int64_t)member * npar;
-    AbcdPar P;
-    const double a = p[0];
-    P.b = p[1] * 1000.0;
-    P.c = p[2];
-    P.d = p[3];
-    P.m = npar > 4 ? p[4] : 0.0;
-    xh_abcd_dev::finish_par(P, a);
-    return P;
-}
-
 using CalibBasin = xh_calib_basin;
 
 // grid.x = 64-cell chunks of ALL basins of the call, grid.y = member blocks of MB; block = 64 threads (one wave).
@@ -99,7 +87,7 @@ __global__ void __launch_bounds__(64) k_calib_march(const CalibBasin *__restrict
 #pragma unroll
     for (int j = 0; j < MB; ++j) {
         const int mem = min(mb0 + j, nmembers - 1);
-        P[j] = member_par(pars, npar, b * nmembers + mem);
+        P[j] = calib_par(pars, npar, b * nmembers + mem);
         s[j].snowpack = 0.0;
         s[j].sm = SPINUP ? 100.0 : sm0[b * nmembers + mem];
         s[j].gw = SPINUP ? 500.0 : gw0[b * nmembers + mem];
@@ -283,7 +271,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3)))
     const bool ok = mem_raw < nmembers;
     const int mem = ok ? mem_raw : nmembers - 1;
     const bool snow_on = B.tn != nullptr;
-    const AbcdPar P = member_par(pars, npar, b * nmembers + mem);
+    const AbcdPar P = calib_par(pars, npar, b * nmembers + mem);
     const XhExpConsts K = xh_exp_consts();
     AbcdState s[CM];
 #pragma unroll
@@ -565,24 +553,56 @@ int xh_calib_problem_place(xh_ctx *ctx, xh_calib_problem &P, int32_t nmonths, in
     return XH_OK;
 }
 
+// spin-up march + basin mean of the Decembers -> P.d_sm0, P.d_gw0 (member-lane layout)
+static int spinup_m(xh_ctx *ctx, const xh_calib_problem &P, const double *d_pars, const int *d_active) {
+    const size_t nbm = (size_t)P.nbasins * P.nmembers;
+    const dim3 grid((unsigned)P.nchunks, (unsigned)((P.nmembers + 63) / 64)), block(64);
+    hipStream_t st = ctx->stream;
+    if (!P.split_done) {
+        const int rc = xh_launch(ctx, nullptr, st, k_calib_split, dim3(256, (unsigned)P.nbasins), 256, 0, P.d_basins,
+                                 P.nmonths);
+        if (rc) return rc;
+        P.split_done = true;
+    }
+    int rc = xh_launch(ctx, nullptr, st, k_calib_march_m<true>, grid, block, 0, P.d_basins, P.d_chunk_basin, d_active,
+                       P.spinup, P.nmembers, P.npar, d_pars, (const double *)nullptr, (const double *)nullptr, P.d_dec,
+                       P.d_cnt, (double *)nullptr);
+    if (!rc)
+        rc = xh_launch(ctx, nullptr, st, k_calib_init_m, xh_grid(ctx, nbm, 64), 64, 0, P.d_basins, d_active, P.nbasins,
+                       P.nmembers, P.d_dec, P.d_cnt, P.d_sm0, P.d_gw0);
+    return rc;
+}
+
+// the same for the cell-lane layout
+static int spinup_c(xh_ctx *ctx, const xh_calib_problem &P, const double *d_pars, const int *d_active) {
+    const size_t nbm = (size_t)P.nbasins * P.nmembers;
+    const dim3 grid((unsigned)P.nchunks, (unsigned)((P.nmembers + MB - 1) / MB)), block(64);
+    hipStream_t st = ctx->stream;
+    int rc = xh_launch(ctx, nullptr, st, k_calib_march<true>, grid, block, 0, P.d_basins, P.d_chunk_basin, d_active,
+                       P.spinup, P.nmembers, P.npar, d_pars, (const double *)nullptr, (const double *)nullptr, P.d_dec,
+                       P.d_cnt, (double *)nullptr);
+    if (!rc)
+        rc = xh_launch(ctx, nullptr, st, k_calib_init, xh_grid(ctx, nbm, 64), 64, 0, P.d_basins, d_active, P.nbasins,
+                       P.nmembers, P.d_dec, P.d_cnt, P.d_sm0, P.d_gw0);
+    return rc;
+}
+
+int xh_calib_spinup_enqueue(xh_ctx *ctx, const xh_calib_problem &P, const double *d_pars, const int *d_active) {
+    return P.member_lanes ? spinup_m(ctx, P, d_pars, d_active) : spinup_c(ctx, P, d_pars, d_active);
+}
+
+int xh_calib_kge_enqueue(xh_ctx *ctx, const xh_calib_problem &P, const int *d_active, const double *d_series, double *d_ed) {
+    return xh_launch(ctx, nullptr, ctx->stream, k_calib_kge, dim3((unsigned)((size_t)P.nbasins * P.nmembers)), 256, 0,
+                     d_active, P.nmonths, P.nmembers, d_series, P.d_obs, d_ed);
+}
+
 static int calib_enqueue_m(xh_ctx *ctx, const xh_calib_problem &P, const double *d_pars, const int *d_active,
                            double *d_ed) {
     const size_t nbm = (size_t)P.nbasins * P.nmembers;
     const dim3 grid((unsigned)P.nchunks, (unsigned)((P.nmembers + 63) / 64)), block(64);
     hipStream_t st = ctx->stream;
     const int rc = xh_timed(ctx, "calib_abcd", st, [&] {
-        if (!P.split_done) {
-            const int rc = xh_launch(ctx, nullptr, st, k_calib_split, dim3(256, (unsigned)P.nbasins), 256, 0, P.d_basins,
-                                     P.nmonths);
-            if (rc) return rc;
-            P.split_done = true;
-        }
-        int rc = xh_launch(ctx, nullptr, st, k_calib_march_m<true>, grid, block, 0, P.d_basins, P.d_chunk_basin, d_active,
-                           P.spinup, P.nmembers, P.npar, d_pars, (const double *)nullptr, (const double *)nullptr, P.d_dec,
-                           P.d_cnt, (double *)nullptr);
-        if (!rc)
-            rc = xh_launch(ctx, nullptr, st, k_calib_init_m, xh_grid(ctx, nbm, 64), 64, 0, P.d_basins, d_active, P.nbasins,
-                           P.nmembers, P.d_dec, P.d_cnt, P.d_sm0, P.d_gw0);
+        int rc = spinup_m(ctx, P, d_pars, d_active);
         if (!rc)
             rc = xh_launch(ctx, nullptr, st, k_calib_march_m<false>, grid, block, 0, P.d_basins, P.d_chunk_basin, d_active,
                            P.nmonths, P.nmembers, P.npar, d_pars, P.d_sm0, P.d_gw0, (double *)nullptr, (int *)nullptr,
@@ -600,25 +620,21 @@ static int calib_enqueue_m(xh_ctx *ctx, const xh_calib_problem &P, const double 
 }
 
 int xh_calib_series_out(xh_ctx *ctx, const xh_calib_problem &P) {
-    if (!P.member_lanes) return XH_OK;
+    if (!P.member_lanes || P.flow) return XH_OK;                 // (the streamflow march writes d_series itself)
     const int64_t n = (int64_t)P.nbasins * P.nmembers * P.nmonths;
     return xh_launch(ctx, nullptr, ctx->stream, k_calib_series_out, xh_grid(ctx, n, 256), 256, 0, P.nbasins, P.nmembers,
                      P.nmonths, P.d_series_m, P.d_series);
 }
 
 int xh_calib_enqueue(xh_ctx *ctx, const xh_calib_problem &P, const double *d_pars, const int *d_active, double *d_ed) {
+    if (P.flow) return xh_calib_flow_enqueue(ctx, P, d_pars, d_active, d_ed);
     if (P.member_lanes) return calib_enqueue_m(ctx, P, d_pars, d_active, d_ed);
     const int nmblocks = (P.nmembers + MB - 1) / MB;
     const size_t nbm = (size_t)P.nbasins * P.nmembers;
     const dim3 grid((unsigned)P.nchunks, (unsigned)nmblocks), block(64);
     hipStream_t st = ctx->stream;
     const int rc = xh_timed(ctx, "calib_abcd", st, [&] {
-        int rc = xh_launch(ctx, nullptr, st, k_calib_march<true>, grid, block, 0, P.d_basins, P.d_chunk_basin, d_active,
-                           P.spinup, P.nmembers, P.npar, d_pars, (const double *)nullptr, (const double *)nullptr, P.d_dec,
-                           P.d_cnt, (double *)nullptr);
-        if (!rc)
-            rc = xh_launch(ctx, nullptr, st, k_calib_init, xh_grid(ctx, nbm, 64), 64, 0, P.d_basins, d_active, P.nbasins,
-                           P.nmembers, P.d_dec, P.d_cnt, P.d_sm0, P.d_gw0);
+        int rc = spinup_c(ctx, P, d_pars, d_active);
         if (!rc)
             rc = xh_launch(ctx, nullptr, st, k_calib_march<false>, grid, block, 0, P.d_basins, P.d_chunk_basin, d_active,
                            P.nmonths, P.nmembers, P.npar, d_pars, P.d_sm0, P.d_gw0, (double *)nullptr, (int *)nullptr,

@@ -9,7 +9,8 @@
 //   k_de_trial    one workgroup per basin: arg-min of the energies (first minimum, like np.argmin), the generation's
 //                 dither, then per member the best1 mutant (two distinct members other than the candidate), binomial
 //                 crossover with one forced gene, re-draw of out-of-bounds genes, scaling to parameter space
-//   objective     xh_calib_enqueue (xh_calib.hip) on the trial parameters, skipping converged basins
+//   objective     xh_calib_enqueue (xh_calib.hip) on the trial parameters, skipping converged basins (the runoff
+//                 objective, or the streamflow one of xh_calib_flow.hip for a session made by xh_calib_de_create_flow)
 //   k_de_select   per basin: keep the trial where its energy is <= the member's (SciPy's `updating='deferred'`
 //                 semantics, the mode SciPy itself uses for vectorised / parallel objectives), then SciPy's
 //                 convergence test std(E) <= atol + tol |mean(E)| (never with an infinite energy in the population)
@@ -255,16 +256,18 @@ void xh_calib_de_destroy(xh_calib_de *de) {
         (void)hipStreamSynchronize(de->ctx->stream);
     }
     if (de->d_problem) (void)hipFree(de->d_problem);
+    xh_calib_flow_destroy(de->P.flow);
     if (de->d_key) (void)hipFree(de->d_key);          // one allocation holds every DE array
     if (de->h_n_active) (void)hipHostFree(de->h_n_active);
     delete de;
 }
 
-int xh_calib_de_create(xh_ctx *ctx, int32_t nbasins, const int64_t *h_ncell, const uint64_t *h_basin_key,
-                       int32_t nmonths, int32_t spinup, int32_t nmembers, int32_t npar,
-                       const double *const *h_pet_t, const double *const *h_precip_t, const double *const *h_tmin_t,
-                       const double *const *h_area, const double *h_obs, const double *h_lo, const double *h_hi,
-                       uint64_t seed, xh_calib_de **out) {
+// flow != NULL: the streamflow objective (xh_calib_flow.hip) on the same basins
+static int de_create(xh_ctx *ctx, int32_t nbasins, const int64_t *h_ncell, const uint64_t *h_basin_key, int32_t nmonths,
+                     int32_t spinup, int32_t nmembers, int32_t npar, const double *const *h_pet_t,
+                     const double *const *h_precip_t, const double *const *h_tmin_t, const double *const *h_area,
+                     const xh_calib_flow_desc *flow, const double *h_obs, const double *h_lo, const double *h_hi,
+                     uint64_t seed, xh_calib_de **out) {
     if (!ctx) return XH_ERR_ARG;
     XH_REQUIRE(ctx, out && h_obs && h_lo && h_hi, "xh_calib_de_create: NULL argument");
     *out = nullptr;
@@ -294,6 +297,7 @@ int xh_calib_de_create(xh_ctx *ctx, int32_t nbasins, const int64_t *h_ncell, con
     } while (0)
     DE_TRY(hipMalloc(&de->d_problem, bytes));
     rc = xh_calib_problem_place(ctx, de->P, nmonths, spinup, nmembers, npar, basins, chunk_basin, h_obs, de->d_problem, ml);
+    if (!rc && flow) rc = xh_calib_flow_create(ctx, nbasins, h_ncell, nmonths, nmembers, flow, &de->P.flow);
     if (rc) {
         xh_calib_de_destroy(de);
         return rc;
@@ -328,6 +332,26 @@ int xh_calib_de_create(xh_ctx *ctx, int32_t nbasins, const int64_t *h_ncell, con
 #undef DE_TRY
     *out = de;
     return XH_OK;
+}
+
+int xh_calib_de_create(xh_ctx *ctx, int32_t nbasins, const int64_t *h_ncell, const uint64_t *h_basin_key,
+                       int32_t nmonths, int32_t spinup, int32_t nmembers, int32_t npar,
+                       const double *const *h_pet_t, const double *const *h_precip_t, const double *const *h_tmin_t,
+                       const double *const *h_area, const double *h_obs, const double *h_lo, const double *h_hi,
+                       uint64_t seed, xh_calib_de **out) {
+    return de_create(ctx, nbasins, h_ncell, h_basin_key, nmonths, spinup, nmembers, npar, h_pet_t, h_precip_t, h_tmin_t,
+                     h_area, nullptr, h_obs, h_lo, h_hi, seed, out);
+}
+
+int xh_calib_de_create_flow(xh_ctx *ctx, int32_t nbasins, const int64_t *h_ncell, const uint64_t *h_basin_key,
+                            int32_t nmonths, int32_t spinup, int32_t nmembers, int32_t npar,
+                            const double *const *h_pet_t, const double *const *h_precip_t,
+                            const double *const *h_tmin_t, const xh_calib_flow_desc *flow, const double *h_obs,
+                            const double *h_lo, const double *h_hi, uint64_t seed, xh_calib_de **out) {
+    if (!ctx) return XH_ERR_ARG;
+    XH_REQUIRE(ctx, flow != nullptr, "xh_calib_de_create_flow: NULL flow tables");
+    return de_create(ctx, nbasins, h_ncell, h_basin_key, nmonths, spinup, nmembers, npar, h_pet_t, h_precip_t, h_tmin_t,
+                     nullptr, flow, h_obs, h_lo, h_hi, seed, out);
 }
 
 static int de_fill_active(xh_calib_de *de, int value) {

@@ -1,0 +1,495 @@
+// Streamflow calibration objective on gfx950 (set_calibrate = 1).
+//
+// The objective of a parameter vector p for basin B: ABCD on B's cells as the runoff objective runs it,
+// the runoff scattered onto B's upstream closure through UM (cells of the closure outside B carry zero runoff), MRTM
+// over the closure -- routing_spinup months, then all months with the carried storage -- and the sum of Avg_ChFlow
+// over B's outlets, scored with ED = 1 - KGE.  Only the closure can reach the outlets, so every (basin, member) routes
+// its own closure and never the world, and every such routing is independent of every other: a population of every
+// basin fills the chip, where the one-world routing kernel is latency-bound.
+//
+//   spin-up      xh_calib_spinup_enqueue (xh_calib.hip, the runoff objective's kernels unchanged): sm0, gw0 per
+//                (basin, member)
+//   k_calib_flow one workgroup per (closure, block of members); lanes <-> (member, closure cell), CPL cells per lane.
+//                Each month: the ABCD step of the lane's basin cells (state in registers, nothing stored), then the
+//                month's 8 nday routing sub-steps with F double-buffered in LDS.  A sub-step gathers UM F from one
+//                buffer, computes the trial storage and writes the NEXT sub-step's F = S tau^-1 into the other buffer
+//                before its one barrier; a cell that fires (dSdt dt < -S, mrtm.py:54) raises a flag, and only when the
+//                flag is up after the barrier does the workgroup take the reference's second pass (fired cells'
+//                F = dSdt + F + S / dt, S = 0, a second gather for the others, mrtm.py:56-69) and rewrite the next F.
+//                A cell none of whose terms changed gathers the same bits twice, so the flag's reach (the workgroup
+//                instead of the reference's world) does not change a bit.  At the month's end the outlets' Avg_ChFlow
+//                go to LDS and one lane per member sums them in ascending cell order into series[basin][member][month].
+//                The launch classes (closure sizes) run concurrently: class 0 on the context's stream, the others on
+//                streams of their own, forked after the spin-up and joined before the KGE.
+//   k_calib_kge  (xh_calib.hip) ED per (basin, member)
+//
+// Everything is fp64 in the reference's operation order (-ffp-contract=off), summation orders are fixed, outputs are
+// written once: results are bit-identical run to run.
+#include <algorithm>
+#include <cmath>
+#include <vector>
+
+#include "xh_abcd_dev.h"
+#include "xh_calib.h"
+#include "xh_launch.h"
+
+namespace {
+
+using namespace xh_abcd_dev;
+
+constexpr int MAX_CLOSURE = 3072;            // cells of one closure (the largest class: 1024 threads x 3 cells)
+constexpr size_t LDS_LIMIT = 160 * 1024;     // per workgroup on gfx950
+
+struct FlowBasin {
+    int nc, cell0, nout, tpm, mpw, klass;    // closure cells, first row, outlets, threads per member, members per group
+    int64_t e0;                              // first entry of the closure's rows
+    int nnz, pad;
+};
+
+// launch classes: threads per workgroup x cells per lane
+struct Klass {
+    int bt, cpl, lo, hi;                     // closures of (lo, hi] cells
+};
+constexpr Klass KLASSES[] = {{64, 1, 0, 64}, {256, 1, 64, 256}, {256, 2, 256, 512}, {256, 4, 512, 1024},
+                             {1024, 3, 1024, MAX_CLOSURE}};
+constexpr int NKLASS = 5;
+
+// UM F of one row from LDS: 0 + sum of +-F[col] in stored order (scipy's csr_matvec; the entry holds col or ~col)
+__device__ __forceinline__ double gather(const int *__restrict__ ent, int e_lo, int e_hi, const double *__restrict__ F) {
+    double g = 0.0;
+    for (int e = e_lo; e < e_hi; ++e) {
+        const int v = ent[e];
+        g = v >= 0 ? g + F[v] : g - F[~v];
+    }
+    return g;
+}
+
+template <int BT, int CPL>
+__global__ void __launch_bounds__(BT) k_calib_flow(const xh_calib_basin *__restrict__ basins,
+                                                   const FlowBasin *__restrict__ fbs, const int2 *__restrict__ work,
+                                                   const int *__restrict__ active, int nmonths, int rspin, double dt,
+                                                   const int *__restrict__ ndays, const int *__restrict__ nts,
+                                                   int nmembers, int npar, const double *__restrict__ pars,
+                                                   const double *__restrict__ sm0, const double *__restrict__ gw0,
+                                                   const int64_t *__restrict__ row_ptr, const int *__restrict__ g_ent,
+                                                   const double *__restrict__ g_tau, const double *__restrict__ g_area,
+                                                   const double *__restrict__ g_s0, const int *__restrict__ g_bcol,
+                                                   const int *__restrict__ g_orank, double *__restrict__ series) {
+    extern __shared__ double lds[];
+    const int2 wk = work[blockIdx.x];
+    const int b = wk.x;
+    if (active && !active[b]) return;                                // workgroup-uniform
+    const FlowBasin FB = fbs[b];
+    const xh_calib_basin B = basins[b];
+    const int nc = FB.nc, tpm = FB.tpm, mpw = FB.mpw, nout = FB.nout;
+    const int t = threadIdx.x;
+    const int mloc = t / tpm, lane = t - mloc * tpm;
+    const int mem = wk.y + mloc;
+    const bool mem_ok = mem < nmembers;
+    const int row = b * nmembers + min(mem, nmembers - 1);
+
+    double *Fbuf = lds;                                              // [2][mpw][nc]
+    double *outv = lds + 2 * mpw * nc;                               // [mpw][nout]
+    int *ent = reinterpret_cast<int *>(outv + mpw * nout);           // [nnz]
+    int *flag = ent + FB.nnz;                                        // [3]
+    for (int e = t; e < FB.nnz; e += BT) ent[e] = g_ent[FB.e0 + e];
+    if (t < 3) flag[t] = 0;
+
+    const bool snow_on = B.tn != nullptr;
+    const AbcdPar P = calib_par(pars, npar, row);
+    const XhExpConsts K = xh_exp_consts();
+    const double sm_init = sm0[row], gw_init = gw0[row];
+    const double dtinv = 1.0 / dt;
+
+    bool own[CPL];
+    int ci[CPL], e_lo[CPL], e_hi[CPL], bcol[CPL];
+    double S[CPL], F[CPL], tau[CPL], erl[CPL], favg[CPL];
+    AbcdState st[CPL];
+#pragma unroll
+    for (int k = 0; k < CPL; ++k) {
+        const int i = lane + k * tpm;
+        own[k] = i < nc;
+        ci[k] = own[k] ? i : 0;
+        const int c = FB.cell0 + ci[k];
+        e_lo[k] = own[k] ? (int)(row_ptr[c] - FB.e0) : 0;
+        e_hi[k] = own[k] ? (int)(row_ptr[c + 1] - FB.e0) : 0;
+        bcol[k] = own[k] ? g_bcol[c] : -1;
+        tau[k] = own[k] ? g_tau[c] : 0.0;
+        S[k] = own[k] ? g_s0[c] : 0.0;
+        F[k] = S[k] * tau[k];
+        erl[k] = favg[k] = 0.0;
+    }
+    // F of this member in buffer p: Fbuf + (p mpw + mloc) nc
+    const int fstride = mpw * nc;
+    double *Fmine = Fbuf + mloc * nc;
+    int par = 0;
+#pragma unroll
+    for (int k = 0; k < CPL; ++k)
+        if (own[k]) Fmine[ci[k]] = F[k];
+    __syncthreads();
+
+    unsigned gs = 0;                                                 // sub-steps so far: the flag slot is gs % 3
+    for (int pass = 0; pass < 2; ++pass) {
+        const int nmon = pass ? nmonths : rspin;
+#pragma unroll
+        for (int k = 0; k < CPL; ++k) {                              // every pass starts ABCD from the month-0 state
+            st[k].snowpack = 0.0;
+            st[k].sm = sm_init;
+            st[k].gw = gw_init;
+        }
+        for (int m = 0; m < nmon; ++m) {
+            const int nday = ndays[m], nt = nts[m];
+            const double secs = (double)((int64_t)nday * 86400);     // nday * 24 * 3600 (mrtm.py:38)
+#pragma unroll
+            for (int k = 0; k < CPL; ++k) {
+                double q = 0.0;                                      // rsim = 0 outside the basin
+                if (bcol[k] >= 0) {
+                    const int64_t o = (int64_t)m * B.ncell + bcol[k];
+                    const AbcdPre pre = abcd_pre(P, K, snow_on, B.pet[o], B.pr[o], snow_on ? B.tn[o] : 0.0);
+                    double aet;
+                    abcd_step(P, st[k], snow_on, m == 0, pre, aet, q);
+                }
+                erl[k] = own[k] ? ((q * g_area[FB.cell0 + ci[k]]) * 1000.0) / secs : 0.0;   // (q area) (1e6 / 1e3) / s
+                favg[k] = 0.0;
+            }
+            for (int s = 0; s < nt; ++s, ++gs) {
+                double *Fc = Fmine + par * fstride;
+                double *Fn = Fmine + (par ^ 1) * fstride;
+                bool fire[CPL];
+                double dsdt[CPL], Sn[CPL];
+                bool any = false;
+#pragma unroll
+                for (int k = 0; k < CPL; ++k) {
+                    fire[k] = false;
+                    dsdt[k] = 0.0;
+                    Sn[k] = S[k];
+                    if (own[k]) {
+                        dsdt[k] = gather(ent, e_lo[k], e_hi[k], Fc) + erl[k];     // UM.dot(F) + erlateral (:52)
+                        const double d = dsdt[k] * dt;
+                        fire[k] = d < -S[k];                                      // :54
+                        Sn[k] = S[k] + d;                                         // :76
+                        any = any || fire[k];
+                        Fn[ci[k]] = Sn[k] * tau[k];                               // next sub-step's F (:50), if none fires
+                    }
+                }
+                if (any) flag[gs % 3] = 1;
+                if (t == 0) flag[(gs + 1) % 3] = 0;                  // read two sub-steps ago, written next sub-step
+                __syncthreads();
+                if (flag[gs % 3]) {                                  // workgroup-uniform
+#pragma unroll
+                    for (int k = 0; k < CPL; ++k)
+                        if (fire[k]) {
+                            F[k] = (dsdt[k] + F[k]) + S[k] * dtinv;                // :60
+                            Fc[ci[k]] = F[k];
+                            Sn[k] = 0.0;                                          // :63
+                        }
+                    __syncthreads();
+#pragma unroll
+                    for (int k = 0; k < CPL; ++k)
+                        if (own[k] && !fire[k]) {
+                            const double d2 = gather(ent, e_lo[k], e_hi[k], Fc) + erl[k];   // :66-67
+                            Sn[k] = S[k] + d2 * dt;                               // :69
+                        }
+#pragma unroll
+                    for (int k = 0; k < CPL; ++k)
+                        if (own[k]) Fn[ci[k]] = Sn[k] * tau[k];
+                    __syncthreads();
+                }
+#pragma unroll
+                for (int k = 0; k < CPL; ++k) {
+                    favg[k] += F[k];                                 // :78
+                    S[k] = Sn[k];
+                    F[k] = S[k] * tau[k];
+                }
+                par ^= 1;
+            }
+#pragma unroll
+            for (int k = 0; k < CPL; ++k)
+                if (own[k]) {
+                    const int r = g_orank[FB.cell0 + ci[k]];
+                    if (r >= 0) outv[mloc * nout + r] = favg[k] / (double)nt;       // Avg_ChFlow (:80)
+                }
+            __syncthreads();
+            if (pass == 1 && lane == 0 && mem_ok) {
+                double sum = 0.0;
+                for (int r = 0; r < nout; ++r) sum += outv[mloc * nout + r];
+                series[((int64_t)b * nmembers + mem) * nmonths + m] = sum;
+            }
+            __syncthreads();                                         // outv is rewritten next month
+        }
+    }
+}
+
+template <int BT, int CPL>
+int launch_klass(xh_ctx *ctx, const xh_calib_problem &P, const xh_calib_flow &f, int kl, const double *d_pars,
+                 const int *d_active);
+
+}  // namespace
+
+struct xh_calib_flow {
+    int nbasins = 0, nmonths = 0, nmembers = 0, rspin = 0;
+    double dt = 0.0;
+    void *d_buf = nullptr;
+    FlowBasin *d_fb = nullptr;
+    int64_t *d_row_ptr = nullptr;
+    int *d_ent = nullptr, *d_bcol = nullptr, *d_orank = nullptr, *d_ndays = nullptr, *d_nt = nullptr;
+    double *d_tau = nullptr, *d_area = nullptr, *d_s0 = nullptr;
+    int2 *d_work = nullptr;
+    int work0[NKLASS] = {0}, nwork[NKLASS] = {0};
+    size_t lds[NKLASS] = {0};
+    // classes 1..4 run on streams of their own beside class 0 on the context's stream: every class is a chain of all
+    // the sub-steps, and one after another the classes would take (classes in use) x chain
+    hipStream_t side[NKLASS] = {nullptr};
+    hipEvent_t fork = nullptr, join[NKLASS] = {nullptr};
+};
+
+namespace {
+
+template <int BT, int CPL>
+int launch_klass(xh_ctx *ctx, const xh_calib_problem &P, const xh_calib_flow &f, int kl, const double *d_pars,
+                 const int *d_active) {
+    return xh_launch(ctx, nullptr, kl ? f.side[kl] : ctx->stream, k_calib_flow<BT, CPL>, dim3((unsigned)f.nwork[kl]), dim3(BT), f.lds[kl],
+                     P.d_basins, f.d_fb, f.d_work + f.work0[kl], d_active, f.nmonths, f.rspin, f.dt, f.d_ndays, f.d_nt,
+                     P.nmembers, P.npar, d_pars, P.d_sm0, P.d_gw0, f.d_row_ptr, f.d_ent, f.d_tau, f.d_area, f.d_s0,
+                     f.d_bcol, f.d_orank, P.d_series);
+}
+
+}  // namespace
+
+void xh_calib_flow_destroy(xh_calib_flow *f) {
+    if (!f) return;
+    for (int kl = 0; kl < NKLASS; ++kl) {
+        if (f->side[kl]) {
+            (void)hipStreamSynchronize(f->side[kl]);
+            (void)hipStreamDestroy(f->side[kl]);
+        }
+        if (f->join[kl]) (void)hipEventDestroy(f->join[kl]);
+    }
+    if (f->fork) (void)hipEventDestroy(f->fork);
+    if (f->d_buf) (void)hipFree(f->d_buf);
+    delete f;
+}
+
+int xh_calib_flow_create(xh_ctx *ctx, int32_t nbasins, const int64_t *h_ncell, int32_t nmonths, int32_t nmembers,
+                         const xh_calib_flow_desc *d, xh_calib_flow **out) {
+    XH_REQUIRE(ctx, d && out && h_ncell, "xh_calib_flow: NULL argument");
+    *out = nullptr;
+    XH_REQUIRE(ctx, d->h_ndays && d->h_closure_ptr && d->h_row_ptr && d->h_cols && d->h_sign && d->h_basin_col &&
+                        d->h_outlet_rank && d->h_tauinv && d->h_area && d->h_s0,
+               "xh_calib_flow: NULL table");
+    XH_REQUIRE(ctx, d->routing_spinup >= 0 && d->routing_spinup <= nmonths,
+               "xh_calib_flow: routing_spinup = %d must lie in [0, nmonths = %d]", d->routing_spinup, nmonths);
+    XH_REQUIRE(ctx, d->dt > 0.0, "xh_calib_flow: dt must be positive");
+    const int64_t *cp = d->h_closure_ptr;
+    XH_REQUIRE(ctx, cp[0] == 0, "xh_calib_flow: closure_ptr[0] must be 0");
+    const int64_t ncl = cp[nbasins];
+    const int64_t nnz = d->h_row_ptr[ncl];
+    XH_REQUIRE(ctx, ncl > 0 && ncl < ((int64_t)1 << 30) && d->h_row_ptr[0] == 0 && nnz >= 0 && nnz < ((int64_t)1 << 30),
+               "xh_calib_flow: bad table sizes");
+    std::vector<int> nt(nmonths);
+    for (int m = 0; m < nmonths; ++m) {
+        XH_REQUIRE(ctx, d->h_ndays[m] > 0 && d->h_ndays[m] <= 31, "xh_calib_flow: month %d has %d days", m, d->h_ndays[m]);
+        nt[m] = (int)((double)((int64_t)d->h_ndays[m] * 86400) / d->dt);      // int(nday * 24 * 3600 / dt) (mrtm.py:35)
+        XH_REQUIRE(ctx, nt[m] >= 1, "xh_calib_flow: dt = %g leaves month %d without a sub-step", d->dt, m);
+    }
+    std::vector<FlowBasin> fb(nbasins);
+    std::vector<int> ent(nnz > 0 ? nnz : 1);
+    std::vector<std::vector<int2>> work(NKLASS);
+    std::vector<size_t> lds(NKLASS, 0);
+    for (int b = 0; b < nbasins; ++b) {
+        const int64_t c0 = cp[b], c1 = cp[b + 1];
+        XH_REQUIRE(ctx, c1 > c0, "xh_calib_flow: basin %d has an empty closure", b);
+        const int64_t nc = c1 - c0;
+        XH_REQUIRE(ctx, nc <= MAX_CLOSURE, "xh_calib_flow: the closure of basin %d has %lld cells, more than %d", b,
+                   (long long)nc, MAX_CLOSURE);
+        FlowBasin &B = fb[b];
+        B.nc = (int)nc;
+        B.cell0 = (int)c0;
+        B.e0 = d->h_row_ptr[c0];
+        B.nnz = (int)(d->h_row_ptr[c1] - B.e0);
+        B.pad = 0;
+        int nout = 0, nbc = 0;
+        for (int64_t c = c0; c < c1; ++c) {
+            XH_REQUIRE(ctx, d->h_row_ptr[c + 1] >= d->h_row_ptr[c], "xh_calib_flow: row_ptr decreases");
+            for (int64_t e = d->h_row_ptr[c]; e < d->h_row_ptr[c + 1]; ++e) {
+                const int col = d->h_cols[e];
+                XH_REQUIRE(ctx, col >= 0 && col < nc && (d->h_sign[e] == 1 || d->h_sign[e] == -1),
+                           "xh_calib_flow: basin %d: bad entry %lld", b, (long long)e);
+                ent[e] = d->h_sign[e] > 0 ? col : ~col;
+            }
+            const int bc = d->h_basin_col[c];
+            XH_REQUIRE(ctx, bc >= -1 && bc < h_ncell[b], "xh_calib_flow: basin %d: bad basin column %d", b, bc);
+            nbc += bc >= 0;
+            const int r = d->h_outlet_rank[c];
+            XH_REQUIRE(ctx, r == -1 || r == nout, "xh_calib_flow: basin %d: outlet ranks must count up in row order", b);
+            nout += r >= 0;
+        }
+        XH_REQUIRE(ctx, nbc == h_ncell[b], "xh_calib_flow: basin %d: %d closure rows carry forcing, the basin has %lld cells",
+                   b, nbc, (long long)h_ncell[b]);
+        XH_REQUIRE(ctx, nout > 0, "xh_calib_flow: basin %d has no outlet", b);
+        B.nout = nout;
+        int kl = 0;
+        while (nc > KLASSES[kl].hi) ++kl;
+        const Klass &K = KLASSES[kl];
+        int tpm = K.bt;
+        if (K.cpl == 1) {                                            // smallest power of two that holds the closure
+            tpm = 1;
+            while (tpm < nc) tpm <<= 1;
+        }
+        B.tpm = tpm;
+        B.mpw = K.bt / tpm;
+        B.klass = kl;
+        const size_t bytes = sizeof(double) * (2 * (size_t)B.mpw * nc + (size_t)B.mpw * nout) + sizeof(int) * (B.nnz + 4);
+        XH_REQUIRE(ctx, bytes <= LDS_LIMIT, "xh_calib_flow: basin %d needs %zu bytes of LDS, more than %zu", b, bytes,
+                   LDS_LIMIT);
+        lds[kl] = std::max(lds[kl], bytes);
+        for (int m0 = 0; m0 < nmembers; m0 += B.mpw) work[kl].push_back(make_int2(b, m0));
+    }
+    xh_calib_flow *f = new xh_calib_flow();
+    f->nbasins = nbasins;
+    f->nmonths = nmonths;
+    f->nmembers = nmembers;
+    f->rspin = d->routing_spinup;
+    f->dt = d->dt;
+    std::vector<int2> all;
+    for (int kl = NKLASS - 1; kl >= 0; --kl) {                       // (the largest closures first: the longest chains)
+        std::stable_sort(work[kl].begin(), work[kl].end(),
+                         [&](const int2 &x, const int2 &y) { return fb[x.x].nc > fb[y.x].nc; });
+        f->work0[kl] = (int)all.size();
+        f->nwork[kl] = (int)work[kl].size();
+        f->lds[kl] = lds[kl];
+        all.insert(all.end(), work[kl].begin(), work[kl].end());
+    }
+    auto al = [](size_t x) { return (x + 255) & ~size_t(255); };
+    const size_t o_fb = 0, o_rp = al(o_fb + sizeof(FlowBasin) * nbasins), o_ent = al(o_rp + 8 * (size_t)(ncl + 1)),
+                 o_bcol = al(o_ent + 4 * ent.size()), o_or = al(o_bcol + 4 * (size_t)ncl),
+                 o_nd = al(o_or + 4 * (size_t)ncl), o_nt = al(o_nd + 4 * (size_t)nmonths),
+                 o_tau = al(o_nt + 4 * (size_t)nmonths), o_area = al(o_tau + 8 * (size_t)ncl),
+                 o_s0 = al(o_area + 8 * (size_t)ncl), o_work = al(o_s0 + 8 * (size_t)ncl),
+                 total = al(o_work + sizeof(int2) * std::max<size_t>(all.size(), 1));
+    hipError_t e = hipMalloc(&f->d_buf, total);
+    if (e != hipSuccess) {
+        xh_calib_flow_destroy(f);
+        return xh_fail(ctx, XH_ERR_HIP, "xh_calib_flow: hipMalloc(%zu) failed: %s", total, hipGetErrorString(e));
+    }
+    char *base = static_cast<char *>(f->d_buf);
+    f->d_fb = reinterpret_cast<FlowBasin *>(base + o_fb);
+    f->d_row_ptr = reinterpret_cast<int64_t *>(base + o_rp);
+    f->d_ent = reinterpret_cast<int *>(base + o_ent);
+    f->d_bcol = reinterpret_cast<int *>(base + o_bcol);
+    f->d_orank = reinterpret_cast<int *>(base + o_or);
+    f->d_ndays = reinterpret_cast<int *>(base + o_nd);
+    f->d_nt = reinterpret_cast<int *>(base + o_nt);
+    f->d_tau = reinterpret_cast<double *>(base + o_tau);
+    f->d_area = reinterpret_cast<double *>(base + o_area);
+    f->d_s0 = reinterpret_cast<double *>(base + o_s0);
+    f->d_work = reinterpret_cast<int2 *>(base + o_work);
+    const struct {
+        void *dst;
+        const void *src;
+        size_t n;
+    } up[] = {{f->d_fb, fb.data(), sizeof(FlowBasin) * nbasins}, {f->d_row_ptr, d->h_row_ptr, 8 * (size_t)(ncl + 1)},
+              {f->d_ent, ent.data(), 4 * ent.size()},            {f->d_bcol, d->h_basin_col, 4 * (size_t)ncl},
+              {f->d_orank, d->h_outlet_rank, 4 * (size_t)ncl},   {f->d_ndays, d->h_ndays, 4 * (size_t)nmonths},
+              {f->d_nt, nt.data(), 4 * (size_t)nmonths},         {f->d_tau, d->h_tauinv, 8 * (size_t)ncl},
+              {f->d_area, d->h_area, 8 * (size_t)ncl},           {f->d_s0, d->h_s0, 8 * (size_t)ncl},
+              {f->d_work, all.data(), sizeof(int2) * all.size()}};
+    for (const auto &u : up) {
+        if (!u.n) continue;
+        e = hipMemcpyAsync(u.dst, u.src, u.n, hipMemcpyHostToDevice, ctx->stream);
+        if (e != hipSuccess) {
+            xh_calib_flow_destroy(f);
+            return xh_fail(ctx, XH_ERR_HIP, "xh_calib_flow: upload failed: %s", hipGetErrorString(e));
+        }
+    }
+    e = hipStreamSynchronize(ctx->stream);                           // the host tables are locals
+    if (e != hipSuccess) {
+        xh_calib_flow_destroy(f);
+        return xh_fail(ctx, XH_ERR_HIP, "xh_calib_flow: upload failed: %s", hipGetErrorString(e));
+    }
+    e = hipEventCreateWithFlags(&f->fork, hipEventDisableTiming);
+    for (int kl = 1; kl < NKLASS && e == hipSuccess; ++kl) {
+        if (!f->nwork[kl]) continue;
+        e = hipStreamCreateWithFlags(&f->side[kl], hipStreamNonBlocking);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&f->join[kl], hipEventDisableTiming);
+    }
+    if (e != hipSuccess) {
+        xh_calib_flow_destroy(f);
+        return xh_fail(ctx, XH_ERR_HIP, "xh_calib_flow: stream / event creation failed: %s", hipGetErrorString(e));
+    }
+    *out = f;
+    return XH_OK;
+}
+
+int xh_calib_flow_enqueue(xh_ctx *ctx, const xh_calib_problem &P, const double *d_pars, const int *d_active, double *d_ed) {
+    const xh_calib_flow &f = *P.flow;
+    hipStream_t st = ctx->stream;
+    int rc = xh_timed(ctx, "calib_abcd", st, [&] { return xh_calib_spinup_enqueue(ctx, P, d_pars, d_active); });
+    if (rc) return rc;
+    rc = xh_timed(ctx, "calib_flow", st, [&] {
+        // fork: the side streams start after the spin-up; join: the context's stream waits for every class
+        XH_HIP(ctx, hipEventRecord(f.fork, st));
+        for (int kl = 1; kl < NKLASS; ++kl)
+            if (f.nwork[kl]) XH_HIP(ctx, hipStreamWaitEvent(f.side[kl], f.fork, 0));
+        int r = XH_OK;
+        if (!r && f.nwork[4]) r = launch_klass<1024, 3>(ctx, P, f, 4, d_pars, d_active);
+        if (!r && f.nwork[3]) r = launch_klass<256, 4>(ctx, P, f, 3, d_pars, d_active);
+        if (!r && f.nwork[2]) r = launch_klass<256, 2>(ctx, P, f, 2, d_pars, d_active);
+        if (!r && f.nwork[1]) r = launch_klass<256, 1>(ctx, P, f, 1, d_pars, d_active);
+        if (!r && f.nwork[0]) r = launch_klass<64, 1>(ctx, P, f, 0, d_pars, d_active);
+        for (int kl = 1; kl < NKLASS; ++kl)
+            if (f.nwork[kl]) {
+                XH_HIP(ctx, hipEventRecord(f.join[kl], f.side[kl]));
+                XH_HIP(ctx, hipStreamWaitEvent(st, f.join[kl], 0));
+            }
+        return r;
+    });
+    if (rc) return rc;
+    return xh_timed(ctx, "calib_kge", st, [&] { return xh_calib_kge_enqueue(ctx, P, d_active, P.d_series, d_ed); });
+}
+
+extern "C" int xh_calib_flow_objective_multi(xh_ctx *ctx, int32_t nbasins, const int64_t *h_ncell, int32_t nmonths,
+                                             int32_t spinup, int32_t nmembers, int32_t npar, const double *h_pars,
+                                             const double *const *h_pet_t, const double *const *h_precip_t,
+                                             const double *const *h_tmin_t, const xh_calib_flow_desc *flow,
+                                             const double *h_obs, double *h_ed, double *h_series) {
+    if (!ctx) return XH_ERR_ARG;
+    XH_REQUIRE(ctx, h_pars && h_obs && h_ed && flow, "xh_calib_flow_objective_multi: NULL argument");
+    std::vector<xh_calib_basin> basins;
+    std::vector<int> chunk_basin;
+    size_t bytes = 0;
+    int ml = 0;
+    int rc = xh_calib_problem_plan(ctx, nbasins, h_ncell, nmonths, spinup, nmembers, npar, h_pet_t, h_precip_t, h_tmin_t,
+                                   nullptr, basins, chunk_basin, &bytes, &ml);
+    if (rc) return rc;
+    xh_calib_flow *f = nullptr;
+    rc = xh_calib_flow_create(ctx, nbasins, h_ncell, nmonths, nmembers, flow, &f);
+    if (rc) return rc;
+    const size_t nbm = (size_t)nbasins * nmembers;
+    const size_t io_bytes = ((nbm * npar + nbm) * sizeof(double) + 255) & ~size_t(255);
+    void *buf = nullptr;
+    rc = xh_scratch(ctx, 1, io_bytes + bytes, &buf);
+    xh_calib_problem P;
+    if (!rc) {
+        double *d_pars = static_cast<double *>(buf);
+        double *d_ed = d_pars + nbm * npar;
+        const hipError_t e = hipMemcpyAsync(d_pars, h_pars, sizeof(double) * nbm * npar, hipMemcpyHostToDevice, ctx->stream);
+        rc = e == hipSuccess ? XH_OK : xh_fail(ctx, XH_ERR_HIP, "xh_calib_flow_objective_multi: %s", hipGetErrorString(e));
+        if (!rc)
+            rc = xh_calib_problem_place(ctx, P, nmonths, spinup, nmembers, npar, basins, chunk_basin, h_obs,
+                                        static_cast<char *>(buf) + io_bytes, ml);
+        P.flow = f;
+        if (!rc) rc = xh_calib_enqueue(ctx, P, d_pars, nullptr, d_ed);
+        if (!rc) {
+            hipError_t e2 = hipMemcpyAsync(h_ed, d_ed, sizeof(double) * nbm, hipMemcpyDeviceToHost, ctx->stream);
+            if (e2 == hipSuccess && h_series)
+                e2 = hipMemcpyAsync(h_series, P.d_series, sizeof(double) * nbm * nmonths, hipMemcpyDeviceToHost,
+                                    ctx->stream);
+            if (e2 == hipSuccess) e2 = hipStreamSynchronize(ctx->stream);
+            if (e2 != hipSuccess) rc = xh_fail(ctx, XH_ERR_HIP, "xh_calib_flow_objective_multi: %s", hipGetErrorString(e2));
+        }
+    }
+    (void)hipStreamSynchronize(ctx->stream);                         // nothing of the call may still run on f
+    xh_calib_flow_destroy(f);
+    return rc;
+}

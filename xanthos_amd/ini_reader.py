@@ -77,6 +77,14 @@ def check_modules(s):
                                   "GWAM driver reads the temperature only Hargreaves loads (components.py:144-160).".format(pet))
     if runoff == 'gwam' and getattr(s, 'calibrate', 0):
         raise ValidationException('Calibrate = 1 calibrates the ABCD parameters; there is no calibration of GWAM.')
+    check_calibration(s)
+
+
+def check_calibration(s):
+    """[Calibrate] against the modules: set_calibrate = 1 routes the basin's runoff, so it needs MRTM."""
+    if getattr(s, 'calibrate', 0) and getattr(s, 'set_calibrate', 0) == 1 and getattr(s, 'routing_module', None) != 'mrtm':
+        raise ValidationException("[Calibrate] set_calibrate = 1 calibrates against routed streamflow and needs "
+                                  "routing_module = mrtm, not '{}'.".format(getattr(s, 'routing_module', None)))
 
 
 def _subsection(cfg, name, section):
@@ -169,6 +177,7 @@ class ConfigReader:
             if 'Calibrate' not in c:
                 raise ValidationException('Calibrate = 1 but no [Calibrate] section.')
             self.configure_calibration(c['Calibrate'])
+            check_calibration(self)
 
     # ------------------------------------------------------------------ modules
     def configure_pet(self, cfg):

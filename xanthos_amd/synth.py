@@ -216,7 +216,8 @@ def data_bag(world, forcing):
 
 def write_example(root, world, forcing, start_year, end_year, project='pm_abcd_mrtm_synth', runoff_spinup=36,
                   routing_spinup=None, output_vars=('q', 'avgchflow'), obs=None, post=False, aggregates=False,
-                  hist_flag=True, ch_storage=None, output_format=1, output_in_year=0):
+                  hist_flag=True, ch_storage=None, output_format=1, output_in_year=0, set_calibrate=0,
+                  calibration_basins='1-2'):
     """Write ``world`` + ``forcing`` as a Xanthos-style input tree under ``root`` and return the .ini path.
 
     Layout and file names follow the reference's example (ini_reader.py:254-279, 353-381, 399-416, 425-437):
@@ -228,6 +229,9 @@ def write_example(root, world, forcing, start_year, end_year, project='pm_abcd_m
     name of each without cells; countries numbered from 0) and switches the three runoff aggregations on.
     ``hist_flag=False`` + ``ch_storage`` (array [ncell]): future mode starting from a saved channel storage file
     (ini_reader.py HistFlag / ChStorageFile, data_load.py:427-438).
+    ``obs`` (rows [basin, 0, 0, value]) switches calibration on: ``set_calibrate = 0`` against runoff in km3_per_mth,
+    ``set_calibrate = 1`` against the basins' outlet streamflow in m3_per_sec (the values then made by the caller, e.g.
+    from known parameters), for ``calibration_basins``.
     """
     import os
     inp = os.path.join(root, 'input')
@@ -260,8 +264,10 @@ def write_example(root, world, forcing, start_year, end_year, project='pm_abcd_m
     if obs is not None:
         obs_file = os.path.join(inp, 'obs.csv')
         np.savetxt(obs_file, obs, delimiter=',', fmt='%.17g')
-        calib = ('\n[Calibrate]\nset_calibrate = 0\nobserved = {}\nobs_unit = km3_per_mth\ncalib_out_dir = {}\n'
-                 'calibration_basins = 1-2\n').format(obs_file, os.path.join(root, 'calib_out'))
+        calib = ('\n[Calibrate]\nset_calibrate = {}\nobserved = {}\nobs_unit = {}\ncalib_out_dir = {}\n'
+                 'calibration_basins = {}\n').format(int(set_calibrate), obs_file,
+                                                     'm3_per_sec' if set_calibrate else 'km3_per_mth',
+                                                     os.path.join(root, 'calib_out'), calibration_basins)
     post_project = post_sections = ''
     if post:
         acc = os.path.join(inp, 'accessible')
