@@ -37,17 +37,23 @@ def _split_rain_snow(p, tmin):
     return rain, snow
 
 
-def _march(a, b, c, d, m, pet, precip, tmin, sm0, gw0, steps, keep=None):
+def _march(a, b, c, d, m, pet, precip, tmin, sm0, gw0, steps, keep=None, decay=None, gw_reciprocal=False):
     """Run ``steps`` months of abcd_dist (:171-228) from soil moisture ``sm0`` / groundwater ``gw0``.
 
     pet/precip/tmin: [months, cells].  Returns (aet, q, sav, sm_keep, gw_keep) where the first three are
     [steps, cells] and the *_keep lists hold soil-moisture / groundwater rows for the month indices in ``keep``.
+
+    ``decay`` [>= steps, cells], if given, replaces ``numpy.exp(-pet / b)`` month by month: exp is the one operation of
+    the update that is not an IEEE operation, so with another implementation's values handed in, that implementation's
+    march must reproduce this one bit for bit.  ``gw_reciprocal`` restates the groundwater line as
+    ``(gw + c awet) * (1 / (d + 1))``, the form of the calibration marches (one rounding more than the quotient).
     """
     ncell = pet.shape[1]
     rain, snow = _split_rain_snow(precip[:steps], None if tmin is None else tmin[:steps])
     a2 = a * 2
     b_over_a = b / a
     d1 = d + 1
+    inv_d1 = 1 / d1
 
     aet = np.empty((steps, ncell))
     q = np.empty((steps, ncell))
@@ -73,10 +79,10 @@ def _march(a, b, c, d, m, pet, precip, tmin, sm0, gw0, steps, keep=None):
                 w = rain[i] + sm_prev + snm
             rpt = (w + b) / a2
             y = rpt - np.sqrt(np.square(rpt) - (w * b_over_a))
-            sm = y * np.exp(-pet[i] / b)
+            sm = y * (np.exp(-pet[i] / b) if decay is None else decay[i])
             awet = w - y
             c_awet = c * awet
-            gw = (gw_prev + c_awet) / d1
+            gw = (gw_prev + c_awet) * inv_d1 if gw_reciprocal else (gw_prev + c_awet) / d1
             e = np.minimum(pet[i], np.maximum(0, y - sm))
             sm = y - e
             aet[i] = e
@@ -109,8 +115,14 @@ def basin_initial_state(sm_dec, gw_dec, basin_ids):
 class ABCD:
     """Same constructor, ``emulate()`` and result attributes as abcd.ABCD (:18-311)."""
 
-    def __init__(self, pars, pet, precip, tmin, basin_ids, process_steps, spinup_steps, method='dist'):
+    def __init__(self, pars, pet, precip, tmin, basin_ids, process_steps, spinup_steps, method='dist', decay=None,
+                 state0=None, gw_reciprocal=False):
+        """``decay`` [cells, months]: values to use for exp(-pet / b) (see _march); ``state0`` = (sm0, gw0) per cell: the
+        post-spin-up state taken from outside instead of from this class's own spin-up."""
         self.nosnow = tmin is None
+        self.decay = None if decay is None else np.asarray(decay).T
+        self.state0 = state0
+        self.gw_reciprocal = gw_reciprocal
         self.a = pars[:, 0]
         self.b = pars[:, 1] * 1000
         self.c = pars[:, 2]
@@ -132,12 +144,16 @@ class ABCD:
         n = self.pet.shape[1]
         s = self.spinup_steps
         keep = [s - 1, s - 13, s - 25]
-        _, _, _, sm_dec, gw_dec = _march(self.a, self.b, self.c, self.d, self.m, self.pet, self.precip,
-                                         self.tmin, np.full(n, SM_INIT), np.full(n, GW_INIT), s, keep=keep)
-        self.sm0, self.gw0 = basin_initial_state(sm_dec, gw_dec, self.basin_ids)
+        form = dict(decay=self.decay, gw_reciprocal=self.gw_reciprocal)
+        if self.state0 is None:
+            _, _, _, sm_dec, gw_dec = _march(self.a, self.b, self.c, self.d, self.m, self.pet, self.precip,
+                                             self.tmin, np.full(n, SM_INIT), np.full(n, GW_INIT), s, keep=keep, **form)
+            self.sm0, self.gw0 = basin_initial_state(sm_dec, gw_dec, self.basin_ids)
+        else:
+            self.sm0, self.gw0 = (np.asarray(v, dtype=np.float64) for v in self.state0)
         self.actual_et, self.rsim, self.soil_water_storage = _march(
             self.a, self.b, self.c, self.d, self.m, self.pet, self.precip, self.tmin,
-            self.sm0, self.gw0, self.steps)
+            self.sm0, self.gw0, self.steps, **form)
 
 
 def _run_basins(basin_nums, pars_abcdm, basin_ids, pet, precip, tmin, n_months, spinup_steps):

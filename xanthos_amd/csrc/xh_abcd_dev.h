@@ -23,6 +23,14 @@ struct AbcdPar {
 // instructions, which gives the correctly rounded quotient (the last step of the IEEE sequence, without its scaling
 // for extreme exponents).  A bare x * (1/d) is not good enough here: y = rpt - sqrt(rpt^2 - w b / a) cancels, and one
 // ulp in rpt showed up as 1e-11 in soil moisture against numpy.
+// Domain (tests/test_gpu_math.py::test_quot_is_the_ieee_quotient pins all of it): equal to x / d in bits for x = +0 and
+// 2^-960 <= |x| <= 2^1000 at the divisors the march has (1.9, 2a, 1000 b, d + 1 over the calibration box).  Outside it:
+//   * quot(-0.0, d) is +0.0 where IEEE gives -0.0 -- and -pet IS -0.0 whenever pet = 0: harmless, exp(+-0) = 1;
+//   * quot(+-inf, d) is NaN where IEEE gives +-inf (the residual is inf - inf): infinite precipitation turns the snowpack
+//     NaN where numpy carries an infinite one; the month's outputs are NaN on both sides all the same (rain = inf - inf);
+//   * for |x| below about 2^-1000 the residual loses bits to underflow and the result can be one step in the last place
+//     off x / d (never more).  (Subnormal numerators proper are benign again -- residual and quotient are exact multiples
+//     of 2^-1074: the march test's subnormal precipitation, below 2^-1054, gives numpy's bits.)
 __device__ __forceinline__ void finish_par(AbcdPar &P, double a) {
     P.a2 = a * 2.0;                                                   // :54-56
     P.b_over_a = P.b / a;
@@ -32,7 +40,7 @@ __device__ __forceinline__ void finish_par(AbcdPar &P, double a) {
     P.inv_d1 = 1.0 / P.d1;
 }
 
-__device__ __forceinline__ double quot(double x, double d, double inv_d) {
+__host__ __device__ __forceinline__ double quot(double x, double d, double inv_d) {
     const double q = x * inv_d;
     return __builtin_fma(__builtin_fma(-d, q, x), inv_d, q);
 }

@@ -13,7 +13,8 @@
 // host-computed reciprocals, 1/cc is formed as gsum / numerator, rc / (lai fwet) as rc (1/lai) (1/fwet) with 1/lai from a
 // table and 1/fwet shared by the classes, and the three quotients that make up a class's ET (:306-327) are put over one
 // common denominator (one reciprocal per class instead of three).  Differences from numpy therefore come from the
-// exp/log/sqrt implementations, from fdiv() below and from those regroupings -- a few ulp each, 5e-13 in PET overall.
+// exp/log/sqrt implementations, from fdiv() (xh_math.h: up to 19 ulp per quotient) and from those regroupings -- 5e-13 in
+// PET overall.
 #include <algorithm>
 
 #include "xh_launch.h"
@@ -60,23 +61,7 @@ __device__ __forceinline__ int days_in_month(int year, int moy) {
     return d + ((moy == 1 && leap) ? 1 : 0);
 }
 
-// a / b as a * (1 / b), the reciprocal from v_rcp_f64 refined by Newton steps (see frcp): within a few ulp of the IEEE quotient
-// for the magnitudes that occur here (no scaling for operands near the exponent limits; b == 0 gives NaN, not an
-// infinity -- every denominator below is guarded or strictly positive) in 6 instructions instead of the ~13 of the
-// correctly rounded sequence.  The kernel is bound by its divisions (~145 per cell-month as written in the reference,
-// ~50 after the regroupings above): 4.9 ms -> 3.7 ms -> 3.1 ms per 67,420 x 600 launch.  PET still agrees with numpy to 5e-13 relative (exp / log dominate; tolerance 1e-6).
-// Round 4: ONE Newton step (two until then).  v_rcp_f64 delivers ~26 bits, one step squares the error: ~1e-15 relative per
-// quotient, PET 8.6e-12 against numpy on the bench world (7.9e-12 with two steps) and every PM test and fuzz case unchanged
-// in outcome, for 3.2 % of the kernel's time (1.95 -> 1.89 ms).
-__device__ __forceinline__ double frcp(double b) {
-    double r = __builtin_amdgcn_rcp(b);
-    r = __builtin_fma(r, __builtin_fma(-b, r, 1.0), r);
-#ifdef XH_PM_RCP2      // the second step (round 1 - 3)
-    r = __builtin_fma(r, __builtin_fma(-b, r, 1.0), r);
-#endif
-    return r;
-}
-__device__ __forceinline__ double fdiv(double a, double b) { return a * frcp(b); }
+// fdiv() / frcp(): a / b as a * (1 / b) from v_rcp_f64 and one Newton step -- xh_math.h (accuracy measured there).
 
 struct PmCell {          // per-cell quantities shared by the months a thread handles
     double p;            // air pressure (calc_p :185-188)
