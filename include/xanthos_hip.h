@@ -478,6 +478,49 @@ int xh_calib_flow_objective_multi(xh_ctx *ctx, int32_t nbasins, const int64_t *h
                                   const double *const *h_precip_t, const double *const *h_tmin_t,
                                   const xh_calib_flow_desc *flow, const double *h_obs, double *h_ed, double *h_series);
 
+/* ------------------------------------------------------------------ streamflow objective at stream gauges
+ * The same objective scored at gauges on cells inside the network instead of at the basin's outlets; records may have
+ * gaps.  A gauge is (id, cell, weight) and belongs to the basin of its cell.  Runoff of basin B, spin-up and initial
+ * state are those of the outlet form (the basin-mean December state over ALL of B's cells); rsim = 0 outside B.  B is
+ * routed ONCE per member on the union of its gauges' upstream closures through UM (a subset of the outlet closure;
+ * basin cells outside the union take no part in the routing pass, closure cells outside B carry zero runoff from their
+ * own initial storage): routing_spinup months, then all nmonths, dt seconds per sub-step.  The series of gauge g is
+ * Avg_ChFlow[cell_g] [m3/s] for every month, nothing summed: the bits of routing the world.
+ * ED_g = 1 - KGE of series_g against obs_g over the months V_g whose observation is finite (n = |V_g| >= 2; population
+ * std, corrcoef via cov with n - 1, clipped to [-1, 1]); a complete record gives the bits of the outlet form's score.
+ * ED_B = (sum w_g ED_g) / (sum w_g), the basin's gauges taken in ascending (cell, gauge id) order and summed left to
+ * right; one gauge of weight 1 gives ED_B == ED_g.
+ * Tables as xh_calib_flow_desc without outlet ranks, the closure being the union closure, plus
+ *   h_gauge_ptr [nbasins + 1]  first gauge of each basin (every basin has at least one); ngauge = h_gauge_ptr[nbasins]
+ *   h_gauge_row [ngauge]       closure-local row of the gauge's cell (a basin cell), ascending within a basin
+ *   h_gauge_weight [ngauge]    w_g > 0, finite
+ * h_basin_col addresses the basin's forcing ([nmonths, ncell_b], all of B's cells) as in the outlet form; only the
+ * basin cells present in the closure run ABCD in the routing pass.  A union closure holds at most 3072 cells.     */
+typedef struct {
+    int32_t routing_spinup;
+    double dt;
+    const int32_t *h_ndays;
+    const int64_t *h_closure_ptr;
+    const int64_t *h_row_ptr;
+    const int32_t *h_cols;
+    const int8_t *h_sign;
+    const int32_t *h_basin_col;
+    const double *h_tauinv;
+    const double *h_area;
+    const double *h_s0;
+    const int64_t *h_gauge_ptr;
+    const int32_t *h_gauge_row;
+    const double *h_gauge_weight;
+} xh_calib_gauge_desc;
+
+/* As xh_calib_flow_objective_multi with h_obs [ngauge, nmonths] (NaN = missing) and h_ed [nbasins, nmembers] = ED_B.
+ * Optional outs: h_ed_gauge [ngauge, nmembers] = ED_g, h_series [ngauge, nmembers, nmonths] = the gauge series.  */
+int xh_calib_gauge_objective_multi(xh_ctx *ctx, int32_t nbasins, const int64_t *h_ncell, int32_t nmonths, int32_t spinup,
+                                   int32_t nmembers, int32_t npar, const double *h_pars, const double *const *h_pet_t,
+                                   const double *const *h_precip_t, const double *const *h_tmin_t,
+                                   const xh_calib_gauge_desc *gauge, const double *h_obs, double *h_ed,
+                                   double *h_ed_gauge, double *h_series);
+
 /* ------------------------------------------------------------------ differential evolution on the device
  * Replaces the scipy.optimize.differential_evolution call of calibrate/calibrate_abcd.py:calibrate_basin (:103-112,
  * SciPy defaults: best1bin, Latin-hypercube start, dither (0.5, 1), recombination 0.7, tol 0.01, polish off) AND the
@@ -509,6 +552,14 @@ int xh_calib_de_create_flow(xh_ctx *ctx, int32_t nbasins, const int64_t *h_ncell
                             const double *const *h_pet_t, const double *const *h_precip_t,
                             const double *const *h_tmin_t, const xh_calib_flow_desc *flow, const double *h_obs,
                             const double *h_lo, const double *h_hi, uint64_t seed, xh_calib_de **out);
+/* The same search on the gauge form of the streamflow objective (the contract of xh_calib_gauge_objective_multi:
+ * union closures routed once per member, masked ED per gauge, weighted mean per basin); h_obs [ngauge, nmonths],
+ * NaN = missing.  The energies of the search are ED_B.                                                          */
+int xh_calib_de_create_gauge(xh_ctx *ctx, int32_t nbasins, const int64_t *h_ncell, const uint64_t *h_basin_key,
+                             int32_t nmonths, int32_t spinup, int32_t nmembers, int32_t npar,
+                             const double *const *h_pet_t, const double *const *h_precip_t,
+                             const double *const *h_tmin_t, const xh_calib_gauge_desc *gauge, const double *h_obs,
+                             const double *h_lo, const double *h_hi, uint64_t seed, xh_calib_de **out);
 void xh_calib_de_destroy(xh_calib_de *de);
 int xh_calib_de_init(xh_calib_de *de);
 int xh_calib_de_step(xh_calib_de *de, int32_t ngen, double tol, double atol, double mut_lo, double mut_hi,

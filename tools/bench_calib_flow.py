@@ -5,7 +5,11 @@ and the fraction of the fp64 issue rate the sub-steps reach (one wave-instructio
 SIMDs, at the clock given; INSTR fp64 lane-instructions per member-cell-sub-step, counted from the kernel's no-fire
 path: F = S tau, the gather's adds (about two entries per row), + erl, x dt, the compare, S + d, the next F, favg += F).
 
-    python tools/bench_calib_flow.py [--members 75] [--gens 2] [--clock-ghz 2.4] [--instr 9]
+    python tools/bench_calib_flow.py [--members 75] [--gens 2] [--clock-ghz 2.4] [--instr 9] [--gauges]
+
+--gauges times the gauge form of the objective on the same world: one gauge per basin, on the basin's outlet with the
+largest upstream closure, complete records.  Each basin then routes that outlet's closure -- a subset of its outlet
+closure -- and is scored by the masked KGE and the weighted combine.
 """
 import argparse
 import json
@@ -18,7 +22,8 @@ import numpy as np
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
 from xanthos_amd import _hip, synth  # noqa: E402
-from xanthos_amd.calibrate.flow_tables import FlowTables  # noqa: E402
+from xanthos_amd.calibrate.flow_tables import FlowTables, outlets_and_closure, um_arrays  # noqa: E402
+from xanthos_amd.calibrate.gauge_tables import Gauges, GaugeTables  # noqa: E402
 from xanthos_amd.routing import mrtm  # noqa: E402
 from xanthos_amd.utils import set_month_arrays  # noqa: E402
 
@@ -32,6 +37,7 @@ def main():
     ap.add_argument('--routing-spinup', type=int, default=120)
     ap.add_argument('--clock-ghz', type=float, default=2.4)
     ap.add_argument('--instr', type=float, default=9.0)
+    ap.add_argument('--gauges', action='store_true', help='the gauge form: one gauge per basin on its largest-closure outlet')
     a = ap.parse_args()
     nm, spin, rspin, members = a.months, a.spinup, a.routing_spinup, a.members
     ctx = _hip.get_context(0)
@@ -45,6 +51,13 @@ def main():
     basins = list(range(1, w.n_basins + 1))
     rng = np.random.default_rng(0)
     ft = FlowTables(um, w.basin_ids, basins, w.flow_dist, w.velocity, w.area, None, ndays, nm, rspin)
+    obs = rng.uniform(50, 500, (len(basins), nm))
+    if a.gauges:
+        ip, ix, sg = um_arrays(um)
+        cells = [int(max(out, key=lambda o: outlets_and_closure(ip, ix, sg, np.array([o]))[1].size)) for out in ft.outlets]
+        ft = GaugeTables(um, w.basin_ids, basins, Gauges(np.arange(len(basins)) + 1, cells, None, obs), w.flow_dist,
+                         w.velocity, w.area, None, ndays, nm, rspin)
+        obs = ft.obs
     # per basin: forcing rows gathered and transposed to [month, cell] ('rsds', 30..330, stands in for PET)
     pet_t, pr_t, tn_t = [], [], []
     for cells in ft.basin_cells:
@@ -59,7 +72,6 @@ def main():
             lst.append(t)
         rows.free()
     ctx.sync()
-    obs = rng.uniform(50, 500, (len(basins), nm))
     bounds = [(1e-4, 1 - 1e-4), (1e-4, 8 - 1e-4), (1e-4, 1 - 1e-4), (1e-4, 1 - 1e-4), (1e-4, 1 - 1e-4)]
     setup = time.perf_counter() - t0
     de = _hip.CalibDE(ctx, [c.size for c in ft.basin_cells], nm, spin, members, bounds, pet_t, pr_t, tn_t, None, obs,
@@ -83,7 +95,7 @@ def main():
     sec = min(gens)
     rate = mcs / sec
     peak = 256 * 4 * 64 * a.clock_ghz * 1e9 / 4             # fp64 lane-instructions per second at full issue
-    res = dict(world_cells=int(w.ncell), basins=len(basins), closure_cells=cells, largest_closure=int(max(c.size for c in ft.closures)),
+    res = dict(form='gauges' if a.gauges else 'outlets', world_cells=int(w.ncell), basins=len(basins), closure_cells=cells, largest_closure=int(max(c.size for c in ft.closures)),
                members=members, months=nm, routing_spinup=rspin, substeps=subs, member_cell_substeps=mcs,
                setup_s=round(setup, 2), init_s=round(t_init, 3), generation_s=[round(g, 3) for g in gens],
                kernels_last_generation_ms=dict(calib_flow=round(ms_flow, 1), calib_abcd=round(ms_spin, 1)),

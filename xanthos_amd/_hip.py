@@ -64,6 +64,21 @@ def flow_desc(tables):
         t.ndays, t.closure_ptr, t.row_ptr, t.cols, t.sign, t.basin_col, t.outlet_rank, t.tauinv, t.area, t.s0)])
 
 
+class CalibGaugeDesc(Structure):
+    """xh_calib_gauge_desc (include/xanthos_hip.h): union-closure tables and gauges of the gauge form."""
+    _fields_ = [('routing_spinup', c_int32), ('dt', c_double)] + [(n, c_void_p) for n in (
+        'h_ndays', 'h_closure_ptr', 'h_row_ptr', 'h_cols', 'h_sign', 'h_basin_col', 'h_tauinv', 'h_area', 'h_s0',
+        'h_gauge_ptr', 'h_gauge_row', 'h_gauge_weight')]
+
+
+def gauge_desc(tables):
+    """CalibGaugeDesc over the arrays of ``tables`` (calibrate.gauge_tables.GaugeTables); keep ``tables`` alive."""
+    t = tables
+    return CalibGaugeDesc(int(t.routing_spinup), float(t.dt), *[_host_ptr(a) for a in (
+        t.ndays, t.closure_ptr, t.row_ptr, t.cols, t.sign, t.basin_col, t.tauinv, t.area, t.s0, t.gauge_ptr, t.gauge_row,
+        t.gauge_weight)])
+
+
 _P = c_void_p
 # name -> (restype, argtypes); mirrors include/xanthos_hip.h one to one
 SIGNATURES = {
@@ -119,6 +134,10 @@ SIGNATURES = {
                                               POINTER(CalibFlowDesc), _P, _P, _P]),
     'xh_calib_de_create_flow': (c_int, [_P, c_int32, _P, _P, c_int32, c_int32, c_int32, c_int32, _P, _P, _P,
                                         POINTER(CalibFlowDesc), _P, _P, _P, c_uint64, POINTER(c_void_p)]),
+    'xh_calib_gauge_objective_multi': (c_int, [_P, c_int32, _P, c_int32, c_int32, c_int32, c_int32, _P, _P, _P, _P,
+                                               POINTER(CalibGaugeDesc), _P, _P, _P, _P]),
+    'xh_calib_de_create_gauge': (c_int, [_P, c_int32, _P, _P, c_int32, c_int32, c_int32, c_int32, _P, _P, _P,
+                                         POINTER(CalibGaugeDesc), _P, _P, _P, c_uint64, POINTER(c_void_p)]),
     'xh_calib_de_destroy': (None, [_P]),
     'xh_calib_de_init': (c_int, [_P]),
     'xh_calib_de_step': (c_int, [_P, c_int32, c_double, c_double, c_double, c_double, c_double, POINTER(c_int32)]),
@@ -551,6 +570,32 @@ class Context:
                                                         _host_ptr(series) if want_series else None))
         return (ed, series) if want_series else ed
 
+    def calib_gauge_objective_multi(self, ncells, nmonths, spinup, pars, pet_t, precip_t, tmin_t, tables, want_series=False,
+                                    want_gauges=False):
+        """Gauge form of the streamflow objective: ``tables`` = calibrate.gauge_tables.GaugeTables (union closures, gauges
+        and their observations [ngauge, nmonths], NaN = missing).  Returns ed [nb, nmem] -- then, as asked, series
+        [ngauge, nmem, nmonths] (the gauge flows, m3/s) and ed_gauge [ngauge, nmem]."""
+        pars = as_f64(pars)
+        nb, nmem, npar = pars.shape
+        obs = as_f64(tables.obs)
+        ng = int(tables.gauge_ptr[-1])
+        if obs.shape != (ng, nmonths) or len(tables.basins) != nb:
+            raise ValueError('the gauge tables hold {} basins and observations {}, not {} basins and {}'.format(
+                len(tables.basins), obs.shape, nb, (ng, nmonths)))
+        nc = np.ascontiguousarray(ncells, dtype=np.int64)
+        ptrs = lambda lst: None if lst is None else (c_void_p * nb)(*[_dptr(x) for x in lst])
+        desc = gauge_desc(tables)
+        ed = np.empty((nb, nmem))
+        series = np.empty((ng, nmem, nmonths)) if want_series else None
+        edg = np.empty((ng, nmem)) if want_gauges else None
+        self._check(lib().xh_calib_gauge_objective_multi(self.handle, nb, _host_ptr(nc), nmonths, spinup, nmem, npar,
+                                                         _host_ptr(pars), ptrs(pet_t), ptrs(precip_t), ptrs(tmin_t),
+                                                         byref(desc), _host_ptr(obs), _host_ptr(ed),
+                                                         _host_ptr(edg) if want_gauges else None,
+                                                         _host_ptr(series) if want_series else None))
+        out = (ed,) + ((series,) if want_series else ()) + ((edg,) if want_gauges else ())
+        return out if len(out) > 1 else ed
+
     # ---- output aggregation
     def agg_time(self, ncell, ncols, group, mode, scale, src, dst):
         self._check(lib().xh_agg_time(self.handle, ncell, ncols, group, mode, _dptr(scale), _dptr(src), _dptr(dst)))
@@ -742,7 +787,9 @@ class CalibDE:
 
     ncells [nb]; pet_t / precip_t / tmin_t / area: lists of DeviceArrays ([nmonths, ncell_b]; tmin_t / area may be
     None) that must stay alive as long as the session; obs [nb, nmonths]; bounds [(lo, hi)] * npar; keys [nb] RNG
-    stream of each basin (e.g. the basin number) so that a basin's search does not depend on its companions."""
+    stream of each basin (e.g. the basin number) so that a basin's search does not depend on its companions.
+    flow: calibrate.flow_tables.FlowTables (the streamflow objective at the outlets) or calibrate.gauge_tables.GaugeTables
+    (at stream gauges; obs is then [ngauge, nmonths], NaN = missing)."""
 
     def __init__(self, ctx, ncells, nmonths, spinup, nmembers, bounds, pet_t, precip_t, tmin_t, area, obs, seed=0,
                  keys=None, flow=None):
@@ -750,13 +797,22 @@ class CalibDE:
         nc = np.ascontiguousarray(ncells, dtype=np.int64)
         self.nb, self.n, self.d = int(nc.size), int(nmembers), len(bounds)
         obs = as_f64(obs)
-        if obs.shape != (self.nb, nmonths):
-            raise ValueError('obs must be [nbasins, nmonths]')
+        gauge_form = flow is not None and hasattr(flow, 'gauge_ptr')
+        if obs.shape != ((int(flow.gauge_ptr[-1]) if gauge_form else self.nb), nmonths):
+            raise ValueError('obs must be [ngauge, nmonths]' if gauge_form else 'obs must be [nbasins, nmonths]')
         lo, hi = as_f64([b[0] for b in bounds]), as_f64([b[1] for b in bounds])
         kk = None if keys is None else np.ascontiguousarray(keys, dtype=np.uint64)
         ptrs = lambda lst: None if lst is None else (c_void_p * self.nb)(*[_dptr(x) for x in lst])
         self._keep = (pet_t, precip_t, tmin_t, area)
         h = c_void_p()
+        if gauge_form:              # the streamflow objective at gauges: flow = calibrate.gauge_tables.GaugeTables
+            ctx._check(lib().xh_calib_de_create_gauge(ctx.handle, self.nb, _host_ptr(nc),
+                                                      None if kk is None else _host_ptr(kk), nmonths, spinup, self.n, self.d,
+                                                      ptrs(pet_t), ptrs(precip_t), ptrs(tmin_t), byref(gauge_desc(flow)),
+                                                      _host_ptr(obs), _host_ptr(lo), _host_ptr(hi),
+                                                      int(seed) & 0xFFFFFFFFFFFFFFFF, byref(h)))
+            self.handle = h.value
+            return
         if flow is not None:        # the streamflow objective: flow = calibrate.flow_tables.FlowTables (copied at creation)
             ctx._check(lib().xh_calib_de_create_flow(ctx.handle, self.nb, _host_ptr(nc),
                                                      None if kk is None else _host_ptr(kk), nmonths, spinup, self.n, self.d,

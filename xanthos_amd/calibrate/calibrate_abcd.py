@@ -18,6 +18,11 @@ summed over the basin's outlets.  The reference's branch cannot run (a flat ``np
 whole ``[ncell, nmonths]`` Avg_ChFlow handed to ``np.corrcoef``, :173, :196-213); this is its evident intent.  Each
 basin routes its own closure on the device (flow_tables.py, csrc/xh_calib_flow.hip); ``router_func`` is accepted for
 signature compatibility and not called.
+
+With ``gauges`` (gauge_tables.Gauges: stream gauges on cells inside the network, records with gaps) the same objective is
+scored at the gauges instead of the outlets: each basin is routed once per member on the union of its gauges' upstream
+closures, every gauge is scored over its finite months, and the basin's energy is the weighted mean of its gauges' ED
+(gauge_tables.py).  ``calibrate_all`` then also writes ``gauge_kge.csv``.
 """
 import logging
 import os
@@ -27,6 +32,7 @@ import numpy as np
 
 from .. import _hip
 from .flow_tables import FlowTables, check_forcing
+from .gauge_tables import GaugeTables
 
 LB = 1e-4
 UB = 1 - LB
@@ -54,7 +60,8 @@ class BasinObjective:
         # the loader's np.nan_to_num of TempMinFile (data_load.py:194-195); precipitation keeps its NaNs (:186)
         self.d_tmin = None if self.nosnow else self.ctx.nan_to_num(tr(tmin))
         self.d_area = self.ctx.upload(bsn_areas) if obs_unit == 'km3_per_mth' else None   # (m3_per_sec: in the routing tables)
-        self.obs = np.ascontiguousarray(np.asarray(bsn_robs, dtype=np.float64)[:n_months])
+        # (gauge form: the records live in the gauge tables)
+        self.obs = None if bsn_robs is None else np.ascontiguousarray(np.asarray(bsn_robs, dtype=np.float64)[:n_months])
         self.obs_unit = obs_unit
         self.nfev = 0
 
@@ -80,7 +87,7 @@ class BasinSet:
         # set_calibrate = 1: the closure tables of these basins in this order (``flow``, or those of the Calibrates)
         self.flow = None
         if obs_unit == 'm3_per_sec':
-            self.flow = flow if flow is not None else FlowTables.join([c.flow for c in cals])
+            self.flow = flow if flow is not None else type(cals[0].flow).join([c.flow for c in cals])
             if self.flow.basins != [c.basin_num for c in cals]:
                 raise ValueError('the flow tables hold basins {}, not {}'.format(self.flow.basins,
                                                                                   [c.basin_num for c in cals]))
@@ -88,7 +95,9 @@ class BasinSet:
         self.ctx = self.objs[0].ctx
         self.nosnow, self.npar = self.objs[0].nosnow, self.objs[0].npar
         self.n_months, self.spinup = int(n_months), int(runoff_spinup)
-        self.obs = np.stack([o.obs for o in self.objs])
+        self.gauge_form = getattr(self.flow, 'gauge_form', False)
+        # gauge form: one record per gauge [ngauge, nmonths], NaN = missing
+        self.obs = self.flow.obs if self.gauge_form else np.stack([o.obs for o in self.objs])
         self.bounds = cals[0].bounds
 
     def args(self):
@@ -97,10 +106,16 @@ class BasinSet:
                 None if self.nosnow else [x.d_tmin for x in o],
                 None if o[0].d_area is None else [x.d_area for x in o])
 
-    def evaluate(self, pars, want_series=False):
-        """ED for parameter sets pars [nbasins, nmembers, npar] in ONE launch (and the modelled series)."""
+    def evaluate(self, pars, want_series=False, want_gauges=False):
+        """ED for parameter sets pars [nbasins, nmembers, npar] in ONE launch (and the modelled series).  Gauge form: the
+        series is [ngauge, nmembers, nmonths], and ``want_gauges`` adds ED of every gauge [ngauge, nmembers]."""
         nc, pet, pr, tn, ar = self.args()
         pars = np.asarray(pars)[:, :, :self.npar]
+        if self.gauge_form:
+            return self.ctx.calib_gauge_objective_multi(nc, self.n_months, self.spinup, pars, pet, pr, tn, self.flow,
+                                                        want_series=want_series, want_gauges=want_gauges)
+        if want_gauges:
+            raise ValueError('want_gauges needs gauge tables')
         if self.flow is not None:
             return self.ctx.calib_flow_objective_multi(nc, self.n_months, self.spinup, pars, pet, pr, tn, self.flow,
                                                        self.obs, want_series=want_series)
@@ -149,10 +164,14 @@ class Calibrate:
 
     def __init__(self, basin_num, basin_ids, basin_areas, precip, pet, obs, tmin, n_months, runoff_spinup,
                  set_calibrate, obs_unit, out_dir, router_func=None, device=0, seed=None, um=None, flow_dist=None,
-                 velocity=None, chs_prev=None, ndays=None, routing_spinup=0, dt=10800, flow=None):
+                 velocity=None, chs_prev=None, ndays=None, routing_spinup=0, dt=10800, flow=None, gauges=None):
         """set_calibrate = 1 also needs the routing inputs: ``um`` (routing.mrtm.upstream_genmatrix), ``flow_dist``,
         ``velocity``, ``chs_prev`` (None = zeros), ``ndays`` [nmonths] and ``routing_spinup`` -- or ``flow``, this
-        basin's FlowTables.  ``router_func`` is kept for the reference's signature and not called."""
+        basin's FlowTables.  ``router_func`` is kept for the reference's signature and not called.
+        ``gauges`` (gauge_tables.Gauges; or ``flow`` = this basin's GaugeTables): score the basin at its stream gauges
+        instead of its outlets; ``obs`` may then be None."""
+        if gauges is not None and set_calibrate != 1:
+            raise ValueError('gauges need set_calibrate = 1')
         if set_calibrate not in (0, 1):
             raise ValueError('set_calibrate must be 0 or 1')
         self.flow = None
@@ -161,8 +180,12 @@ class Calibrate:
                 if um is None or flow_dist is None or velocity is None or ndays is None:
                     raise ValueError('set_calibrate = 1 needs um, flow_dist, velocity and ndays (or flow)')
                 check_forcing([basin_num], basin_ids, pet, precip, n_months)
-                flow = FlowTables(um, basin_ids, [basin_num], flow_dist, velocity, basin_areas, chs_prev, ndays, n_months,
-                                  routing_spinup, dt=dt)
+                if gauges is not None:
+                    flow = GaugeTables(um, basin_ids, [basin_num], gauges, flow_dist, velocity, basin_areas, chs_prev,
+                                       ndays, n_months, routing_spinup, dt=dt)
+                else:
+                    flow = FlowTables(um, basin_ids, [basin_num], flow_dist, velocity, basin_areas, chs_prev, ndays,
+                                      n_months, routing_spinup, dt=dt)
             self.flow = flow
         self.basin_num, self.n_months, self.runoff_spinup = basin_num, n_months, runoff_spinup
         self.set_calibrate, self.obs_unit, self.out_dir, self.seed = set_calibrate, obs_unit, out_dir, seed
@@ -177,8 +200,11 @@ class Calibrate:
         self.bsn_PET = np.asarray(pet)[self.basin_idx]
         self.bsn_P = np.asarray(precip)[self.basin_idx]
         self.bsn_TMIN = None if self.nosnow else np.asarray(tmin)[self.basin_idx]
-        obs = np.asarray(obs)
-        self.bsn_Robs = obs[np.where(obs[:, 0] == basin_num)][:n_months, 1]           # :88
+        if getattr(self.flow, 'gauge_form', False):
+            self.bsn_Robs = None                                                      # the records are in the gauge tables
+        else:
+            obs = np.asarray(obs)
+            self.bsn_Robs = obs[np.where(obs[:, 0] == basin_num)][:n_months, 1]       # :88
         self.device = device
         self.nfev = 0
 
@@ -245,9 +271,9 @@ def process_basin(basin_num, settings, data, pet, router_function=None, um=None,
     if settings.set_calibrate == 1:
         flow = flow_tables(settings, data, pet, [basin_num], um, ndays, dt)
     cal = Calibrate(basin_num=basin_num, set_calibrate=settings.set_calibrate, obs_unit=settings.obs_unit,
-                    basin_ids=data.basin_ids, basin_areas=data.area, precip=data.precip, pet=pet, obs=data.cal_obs,
-                    tmin=data.tmin, n_months=settings.nmonths, runoff_spinup=settings.runoff_spinup,
-                    router_func=router_function, out_dir=settings.calib_out_dir,
+                    basin_ids=data.basin_ids, basin_areas=data.area, precip=data.precip, pet=pet,
+                    obs=getattr(data, 'cal_obs', None), tmin=data.tmin, n_months=settings.nmonths,
+                    runoff_spinup=settings.runoff_spinup, router_func=router_function, out_dir=settings.calib_out_dir,
                     device=getattr(settings, 'device', 0), flow=flow)
     cal.calibrate_basin()
     return cal
@@ -259,6 +285,11 @@ def flow_tables(settings, data, pet, basins, um, ndays, dt=10800):
     if um is None or ndays is None:
         raise ValueError('set_calibrate = 1 needs the routing topology (um) and the day counts (ndays)')
     check_forcing(basins, data.basin_ids, pet, data.precip, settings.nmonths)
+    gauges = getattr(data, 'gauges', None)
+    if gauges is not None:      # scored at stream gauges: union closures of each basin's gauges
+        return GaugeTables(um, data.basin_ids, basins, gauges, data.flow_dist, data.str_velocity, data.area,
+                           getattr(data, 'chs_prev', None), ndays, settings.nmonths,
+                           getattr(settings, 'routing_spinup', 0), dt=dt)
     return FlowTables(um, data.basin_ids, basins, data.flow_dist, data.str_velocity, data.area,
                       getattr(data, 'chs_prev', None), ndays, settings.nmonths, getattr(settings, 'routing_spinup', 0),
                       dt=dt)
@@ -294,9 +325,9 @@ def gather_results(local, owner, group, root=0):
 
 def _make_calibrate(b, settings, data, pet, flow=None):
     return Calibrate(basin_num=b, set_calibrate=settings.set_calibrate, obs_unit=settings.obs_unit,
-                     basin_ids=data.basin_ids, basin_areas=data.area, precip=data.precip, pet=pet, obs=data.cal_obs,
-                     tmin=data.tmin, n_months=settings.nmonths, runoff_spinup=settings.runoff_spinup,
-                     out_dir=settings.calib_out_dir, device=getattr(settings, 'device', 0),
+                     basin_ids=data.basin_ids, basin_areas=data.area, precip=data.precip, pet=pet,
+                     obs=getattr(data, 'cal_obs', None), tmin=data.tmin, n_months=settings.nmonths,
+                     runoff_spinup=settings.runoff_spinup, out_dir=settings.calib_out_dir, device=getattr(settings, 'device', 0),
                      flow=None if flow is None else flow.subset([b]))
 
 
@@ -326,6 +357,9 @@ def calibrate_all(settings, data, pet, router_function=None, seed=None, popsize=
     reference's two files per basin (:130-131; on rank 0) and returns {basin: (parameters, kge)} (rank 0; {} elsewhere).
     set_calibrate = 1 also needs ``um`` (the routing topology), ``ndays`` [nmonths] and ``dt``; ``data`` then carries
     flow_dist, str_velocity and chs_prev, and the basins are dealt by closure cells x (nmonths + routing_spinup).
+    With ``data.gauges`` (gauge_tables.Gauges) the basins are scored at their stream gauges (union closures; dealt by
+    union-closure cells x (nmonths + routing_spinup)) and rank 0 also writes ``gauge_kge.csv`` to ``calib_out_dir``: per
+    gauge its id, basin, cell (1-based), months used and KGE at the basin's best parameters.
     """
     if settings.set_calibrate not in (0, 1):
         raise ValueError('set_calibrate must be 0 or 1')
@@ -361,4 +395,28 @@ def calibrate_all(settings, data, pet, router_function=None, seed=None, popsize=
         c = cals[b] if b in cals else _make_calibrate(b, settings, data, pet, flow)
         c._store(row[:npar], row[npar], int(row[npar + 1]))
         results[b] = (row[:npar].copy(), 1 - row[npar])
+    if getattr(flow, 'gauge_form', False) and settings.calib_out_dir is not None:
+        write_gauge_kge(os.path.join(settings.calib_out_dir, 'gauge_kge.csv'), flow,
+                        gauge_kge(basins, table[:, :npar], settings, data, pet, flow))
     return results
+
+
+def gauge_kge(basins, best, settings, data, pet, flow):
+    """KGE of every gauge of ``flow`` (GaugeTables of ``basins``) at its basin's parameters ``best`` [nbasins, npar]:
+    one evaluation of one member per basin."""
+    cals = [_make_calibrate(b, settings, data, pet, flow) for b in basins]
+    bset = BasinSet(cals, settings.nmonths, settings.runoff_spinup, settings.obs_unit, flow=flow.subset(basins))
+    try:
+        _, edg = bset.evaluate(np.asarray(best)[:, None, :], want_gauges=True)
+    finally:
+        bset.close()
+    return 1 - edg[:, 0]
+
+
+def write_gauge_kge(path, flow, kge):
+    """gauge_kge.csv: gauge_id, basin, cell_id (1-based, as the coordinates' first column), months_used, kge."""
+    os.makedirs(os.path.dirname(path) or '.', exist_ok=True)
+    with open(path, 'w') as fh:
+        fh.write('gauge_id,basin,cell_id,months_used,kge\n')
+        for gid, b, c, n, k in zip(flow.gauge_id, flow.gauge_basin, flow.gauge_cell, flow.months_used, kge):
+            fh.write('{},{},{},{},{!r}\n'.format(int(gid), int(b), int(c) + 1, int(n), float(k)))

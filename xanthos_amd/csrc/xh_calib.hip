@@ -224,7 +224,70 @@ __global__ void __launch_bounds__(256) k_calib_kge(const int *__restrict__ activ
         ed[mem] = sqrt((r - 1.0) * (r - 1.0) + (relvar - 1.0) * (relvar - 1.0) + (bias - 1.0) * (bias - 1.0));
     }
 }
+// Gauge form of the streamflow objective: one workgroup per (gauge, member), ED over the months V whose observation is
+// finite, n = |V|.  The sums are those of k_calib_kge -- the same strided partial sums and the same tree -- and a skipped
+// month adds nothing, so a complete record gives k_calib_kge's bits.
+__global__ void __launch_bounds__(256) k_calib_kge_masked(const int *__restrict__ active,
+                                                          const int *__restrict__ gauge_basin, int nmonths, int nmembers,
+                                                          const double *__restrict__ series,
+                                                          const double *__restrict__ obs_all, double *__restrict__ ed) {
+    __shared__ double sh[256];
+    const int gm = blockIdx.x;                           // gauge * nmembers + member
+    const int g = gm / nmembers;
+    if (active && !active[gauge_basin[g]]) return;       // block-uniform
+    const double *x = series + (int64_t)gm * nmonths;
+    const double *obs = obs_all + (int64_t)g * nmonths;
+    double sx = 0.0, so = 0.0, cnt = 0.0;
+    for (int m = threadIdx.x; m < nmonths; m += blockDim.x) {
+        const double o = obs[m];
+        if (o - o == 0.0) {                              // finite
+            sx += x[m];
+            so += o;
+            cnt += 1.0;
+        }
+    }
+    const double n = block_sum(cnt, sh);                 // (whole numbers: exact)
+    const double mx = block_sum(sx, sh) / n, mo = block_sum(so, sh) / n;
+    double vxx = 0.0, voo = 0.0, vxo = 0.0;
+    for (int m = threadIdx.x; m < nmonths; m += blockDim.x) {
+        const double o = obs[m];
+        if (o - o == 0.0) {
+            const double dx = x[m] - mx, d_o = o - mo;
+            vxx += dx * dx;
+            voo += d_o * d_o;
+            vxo += dx * d_o;
+        }
+    }
+    vxx = block_sum(vxx, sh);
+    voo = block_sum(voo, sh);
+    vxo = block_sum(vxo, sh);
+    if (threadIdx.x == 0) {
+        const double relvar = sqrt(vxx / n) / sqrt(voo / n);     // np.std, population
+        const double bias = mx / mo;
+        const double c00 = voo / (n - 1.0), c11 = vxx / (n - 1.0), c01 = vxo / (n - 1.0);   // np.corrcoef via np.cov
+        double r = c01 / sqrt(c11) / sqrt(c00);
+        r = r > 1.0 ? 1.0 : (r < -1.0 ? -1.0 : r);               // corrcoef clips to [-1, 1]
+        ed[gm] = sqrt((r - 1.0) * (r - 1.0) + (relvar - 1.0) * (relvar - 1.0) + (bias - 1.0) * (bias - 1.0));
+    }
+}
 
+// one thread per (basin, member): ED_B = (sum w_g ED_g) / (sum w_g) over the basin's gauges in their stored order
+// (ascending (cell, gauge id)), left to right.  One gauge of weight 1: (1 ED_g) / 1 = ED_g to the bit.
+__global__ void __launch_bounds__(64) k_calib_gauge_combine(const int *__restrict__ active, int nbasins, int nmembers,
+                                                            const int *__restrict__ gauge_ptr,
+                                                            const double *__restrict__ weight,
+                                                            const double *__restrict__ ed_gauge, double *__restrict__ ed) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nbasins * nmembers) return;
+    const int b = i / nmembers, mem = i - b * nmembers;
+    if (active && !active[b]) return;
+    double num = 0.0, den = 0.0;
+    for (int g = gauge_ptr[b]; g < gauge_ptr[b + 1]; ++g) {
+        num += weight[g] * ed_gauge[(int64_t)g * nmembers + mem];
+        den += weight[g];
+    }
+    ed[i] = num / den;
+}
 
 // =============================================================================== member-lane layout
 // lanes <-> members, CM cells per wave.  Everything that does not depend on the member -- PET, the rain / snow split,
@@ -457,7 +520,7 @@ int xh_calib_problem_plan(xh_ctx *ctx, int32_t nbasins, const int64_t *h_ncell, 
                           int32_t nmembers, int32_t npar, const double *const *h_pet_t,
                           const double *const *h_precip_t, const double *const *h_tmin_t,
                           const double *const *h_area, std::vector<xh_calib_basin> &basins,
-                          std::vector<int> &chunk_basin, size_t *bytes, int *member_lanes) {
+                          std::vector<int> &chunk_basin, size_t *bytes, int *member_lanes, int32_t ngauge) {
     XH_REQUIRE(ctx, nbasins > 0 && h_ncell && h_pet_t && h_precip_t, "xh_calib_objective: NULL argument");
     XH_REQUIRE(ctx, nmonths > 1 && nmembers > 0, "xh_calib_objective: bad size");
     XH_REQUIRE(ctx, npar == 4 || npar == 5, "xh_calib_objective: npar must be 4 (no snow) or 5");
@@ -491,8 +554,11 @@ int xh_calib_problem_plan(xh_ctx *ctx, int32_t nbasins, const int64_t *h_ncell, 
     const size_t nchunks = chunk_basin.size(), nbm = (size_t)nbasins * nmembers;
     size_t cells = 0;
     for (int b = 0; b < nbasins; ++b) cells += (size_t)h_ncell[b];
-    const size_t dbl = (size_t)nbasins * nmonths + 2 * nbm + nchunks * nmembers * 6 + nchunks * nmembers * (size_t)nmonths +
-                       nbm * nmonths * (ml ? 2 : 1) + (ml ? 3 * cells * (size_t)nmonths : 0);
+    XH_REQUIRE(ctx, ngauge >= 0, "xh_calib_objective: bad gauge count");
+    const size_t nser = ngauge ? (size_t)ngauge : (size_t)nbasins;   // rows of obs and series: gauges or basins
+    const size_t dbl = nser * nmonths + 2 * nbm + nchunks * nmembers * 6 + nchunks * nmembers * (size_t)nmonths +
+                       nser * nmembers * nmonths + (ml ? nbm * nmonths : 0) + (size_t)ngauge * nmembers +
+                       (ml ? 3 * cells * (size_t)nmonths : 0);
     const size_t tab_bytes = ((sizeof(xh_calib_basin) * nbasins + sizeof(int) * nchunks) + 255) & ~size_t(255);
     *bytes = dbl * sizeof(double) + nchunks * nmembers * 6 * sizeof(int) + (ml ? cells * (size_t)nmonths * sizeof(int) : 0) +
              tab_bytes + 512;
@@ -501,7 +567,7 @@ int xh_calib_problem_plan(xh_ctx *ctx, int32_t nbasins, const int64_t *h_ncell, 
 
 int xh_calib_problem_place(xh_ctx *ctx, xh_calib_problem &P, int32_t nmonths, int32_t spinup, int32_t nmembers,
                            int32_t npar, std::vector<xh_calib_basin> &basins, const std::vector<int> &chunk_basin,
-                           const double *h_obs, void *buf, int member_lanes) {
+                           const double *h_obs, void *buf, int member_lanes, int32_t ngauge) {
     XH_REQUIRE(ctx, h_obs != nullptr, "xh_calib_objective: obs is NULL");
     const int nbasins = (int)basins.size();
     const size_t nchunks = chunk_basin.size(), nbm = (size_t)nbasins * nmembers;
@@ -515,13 +581,17 @@ int xh_calib_problem_place(xh_ctx *ctx, xh_calib_problem &P, int32_t nmonths, in
     P.nchunks = nchunks;
     P.member_lanes = member_lanes;
     P.split_done = false;
+    P.ngauge = ngauge;
+    const size_t nser = ngauge ? (size_t)ngauge : (size_t)nbasins;
     P.d_obs = static_cast<double *>(buf);
-    P.d_sm0 = P.d_obs + (size_t)nbasins * nmonths;
+    P.d_sm0 = P.d_obs + nser * nmonths;
     P.d_gw0 = P.d_sm0 + nbm;
     P.d_dec = P.d_gw0 + nbm;
     P.d_part = P.d_dec + n_dec;
     P.d_series = P.d_part + n_part;
-    double *next = P.d_series + nbm * nmonths;
+    double *next = P.d_series + nser * nmembers * nmonths;
+    P.d_ed_gauge = ngauge ? next : nullptr;
+    next += (size_t)ngauge * nmembers;
     P.d_series_m = nullptr;
     if (member_lanes) {
         P.d_series_m = next;
@@ -544,7 +614,7 @@ int xh_calib_problem_place(xh_ctx *ctx, xh_calib_problem &P, int32_t nmonths, in
             kind += (size_t)B.ncell * nmonths;
         }
     }
-    XH_HIP(ctx, hipMemcpyAsync(P.d_obs, h_obs, sizeof(double) * nbasins * nmonths, hipMemcpyHostToDevice, ctx->stream));
+    XH_HIP(ctx, hipMemcpyAsync(P.d_obs, h_obs, sizeof(double) * nser * nmonths, hipMemcpyHostToDevice, ctx->stream));
     XH_HIP(ctx, hipMemcpyAsync(P.d_basins, basins.data(), sizeof(xh_calib_basin) * nbasins, hipMemcpyHostToDevice,
                                ctx->stream));
     XH_HIP(ctx, hipMemcpyAsync(P.d_chunk_basin, chunk_basin.data(), sizeof(int) * nchunks, hipMemcpyHostToDevice,
@@ -594,6 +664,18 @@ int xh_calib_spinup_enqueue(xh_ctx *ctx, const xh_calib_problem &P, const double
 int xh_calib_kge_enqueue(xh_ctx *ctx, const xh_calib_problem &P, const int *d_active, const double *d_series, double *d_ed) {
     return xh_launch(ctx, nullptr, ctx->stream, k_calib_kge, dim3((unsigned)((size_t)P.nbasins * P.nmembers)), 256, 0,
                      d_active, P.nmonths, P.nmembers, d_series, P.d_obs, d_ed);
+}
+
+int xh_calib_gauge_score_enqueue(xh_ctx *ctx, const xh_calib_problem &P, const int *d_active, int ngauge,
+                                 const int *d_gauge_basin, const int *d_gauge_ptr, const double *d_weight,
+                                 const double *d_series, double *d_ed) {
+    XH_REQUIRE(ctx, ngauge > 0 && ngauge == P.ngauge && P.d_ed_gauge, "xh_calib_gauge: the problem was not laid out for %d gauges",
+               ngauge);
+    const int rc = xh_launch(ctx, nullptr, ctx->stream, k_calib_kge_masked, dim3((unsigned)((size_t)ngauge * P.nmembers)), 256,
+                             0, d_active, d_gauge_basin, P.nmonths, P.nmembers, d_series, P.d_obs, P.d_ed_gauge);
+    if (rc) return rc;
+    return xh_launch(ctx, nullptr, ctx->stream, k_calib_gauge_combine, xh_grid(ctx, (int64_t)P.nbasins * P.nmembers, 64), 64, 0,
+                     d_active, P.nbasins, P.nmembers, d_gauge_ptr, d_weight, P.d_ed_gauge, d_ed);
 }
 
 static int calib_enqueue_m(xh_ctx *ctx, const xh_calib_problem &P, const double *d_pars, const int *d_active,

@@ -10,7 +10,8 @@
 //                 dither, then per member the best1 mutant (two distinct members other than the candidate), binomial
 //                 crossover with one forced gene, re-draw of out-of-bounds genes, scaling to parameter space
 //   objective     xh_calib_enqueue (xh_calib.hip) on the trial parameters, skipping converged basins (the runoff
-//                 objective, or the streamflow one of xh_calib_flow.hip for a session made by xh_calib_de_create_flow)
+//                 objective, or the streamflow one of xh_calib_flow.hip for a session made by xh_calib_de_create_flow
+//                 or, in its gauge form, xh_calib_de_create_gauge)
 //   k_de_select   per basin: keep the trial where its energy is <= the member's (SciPy's `updating='deferred'`
 //                 semantics, the mode SciPy itself uses for vectorised / parallel objectives), then SciPy's
 //                 convergence test std(E) <= atol + tol |mean(E)| (never with an infinite energy in the population)
@@ -262,12 +263,13 @@ void xh_calib_de_destroy(xh_calib_de *de) {
     delete de;
 }
 
-// flow != NULL: the streamflow objective (xh_calib_flow.hip) on the same basins
+// flow != NULL: the streamflow objective (xh_calib_flow.hip) on the same basins; gauge != NULL: its gauge form, with
+// h_obs [ngauge, nmonths]
 static int de_create(xh_ctx *ctx, int32_t nbasins, const int64_t *h_ncell, const uint64_t *h_basin_key, int32_t nmonths,
                      int32_t spinup, int32_t nmembers, int32_t npar, const double *const *h_pet_t,
                      const double *const *h_precip_t, const double *const *h_tmin_t, const double *const *h_area,
-                     const xh_calib_flow_desc *flow, const double *h_obs, const double *h_lo, const double *h_hi,
-                     uint64_t seed, xh_calib_de **out) {
+                     const xh_calib_flow_desc *flow, const xh_calib_gauge_desc *gauge, const double *h_obs,
+                     const double *h_lo, const double *h_hi, uint64_t seed, xh_calib_de **out) {
     if (!ctx) return XH_ERR_ARG;
     XH_REQUIRE(ctx, out && h_obs && h_lo && h_hi, "xh_calib_de_create: NULL argument");
     *out = nullptr;
@@ -277,8 +279,12 @@ static int de_create(xh_ctx *ctx, int32_t nbasins, const int64_t *h_ncell, const
     std::vector<int> chunk_basin;
     size_t bytes = 0;
     int ml = 0;
+    XH_REQUIRE(ctx, !gauge || (gauge->h_gauge_ptr && nbasins > 0 && gauge->h_gauge_ptr[nbasins] > 0 &&
+                               gauge->h_gauge_ptr[nbasins] < ((int64_t)1 << 24)),
+               "xh_calib_de_create_gauge: bad gauge_ptr");
+    const int32_t ngauge = gauge ? (int32_t)gauge->h_gauge_ptr[nbasins] : 0;
     int rc = xh_calib_problem_plan(ctx, nbasins, h_ncell, nmonths, spinup, nmembers, npar, h_pet_t, h_precip_t, h_tmin_t,
-                                   h_area, basins, chunk_basin, &bytes, &ml);
+                                   h_area, basins, chunk_basin, &bytes, &ml, ngauge);
     if (rc) return rc;
     XH_HIP(ctx, hipSetDevice(ctx->device));
     xh_calib_de *de = new xh_calib_de();
@@ -296,8 +302,10 @@ static int de_create(xh_ctx *ctx, int32_t nbasins, const int64_t *h_ncell, const
         }                                                                                               \
     } while (0)
     DE_TRY(hipMalloc(&de->d_problem, bytes));
-    rc = xh_calib_problem_place(ctx, de->P, nmonths, spinup, nmembers, npar, basins, chunk_basin, h_obs, de->d_problem, ml);
+    rc = xh_calib_problem_place(ctx, de->P, nmonths, spinup, nmembers, npar, basins, chunk_basin, h_obs, de->d_problem, ml,
+                                ngauge);
     if (!rc && flow) rc = xh_calib_flow_create(ctx, nbasins, h_ncell, nmonths, nmembers, flow, &de->P.flow);
+    if (!rc && gauge) rc = xh_calib_gauge_create(ctx, nbasins, h_ncell, nmonths, nmembers, gauge, &de->P.flow);
     if (rc) {
         xh_calib_de_destroy(de);
         return rc;
@@ -340,7 +348,7 @@ int xh_calib_de_create(xh_ctx *ctx, int32_t nbasins, const int64_t *h_ncell, con
                        const double *const *h_area, const double *h_obs, const double *h_lo, const double *h_hi,
                        uint64_t seed, xh_calib_de **out) {
     return de_create(ctx, nbasins, h_ncell, h_basin_key, nmonths, spinup, nmembers, npar, h_pet_t, h_precip_t, h_tmin_t,
-                     h_area, nullptr, h_obs, h_lo, h_hi, seed, out);
+                     h_area, nullptr, nullptr, h_obs, h_lo, h_hi, seed, out);
 }
 
 int xh_calib_de_create_flow(xh_ctx *ctx, int32_t nbasins, const int64_t *h_ncell, const uint64_t *h_basin_key,
@@ -351,7 +359,18 @@ int xh_calib_de_create_flow(xh_ctx *ctx, int32_t nbasins, const int64_t *h_ncell
     if (!ctx) return XH_ERR_ARG;
     XH_REQUIRE(ctx, flow != nullptr, "xh_calib_de_create_flow: NULL flow tables");
     return de_create(ctx, nbasins, h_ncell, h_basin_key, nmonths, spinup, nmembers, npar, h_pet_t, h_precip_t, h_tmin_t,
-                     nullptr, flow, h_obs, h_lo, h_hi, seed, out);
+                     nullptr, flow, nullptr, h_obs, h_lo, h_hi, seed, out);
+}
+
+int xh_calib_de_create_gauge(xh_ctx *ctx, int32_t nbasins, const int64_t *h_ncell, const uint64_t *h_basin_key,
+                             int32_t nmonths, int32_t spinup, int32_t nmembers, int32_t npar,
+                             const double *const *h_pet_t, const double *const *h_precip_t,
+                             const double *const *h_tmin_t, const xh_calib_gauge_desc *gauge, const double *h_obs,
+                             const double *h_lo, const double *h_hi, uint64_t seed, xh_calib_de **out) {
+    if (!ctx) return XH_ERR_ARG;
+    XH_REQUIRE(ctx, gauge != nullptr, "xh_calib_de_create_gauge: NULL gauge tables");
+    return de_create(ctx, nbasins, h_ncell, h_basin_key, nmonths, spinup, nmembers, npar, h_pet_t, h_precip_t, h_tmin_t,
+                     nullptr, nullptr, gauge, h_obs, h_lo, h_hi, seed, out);
 }
 
 static int de_fill_active(xh_calib_de *de, int value) {

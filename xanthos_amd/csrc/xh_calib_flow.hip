@@ -23,6 +23,14 @@
 //                streams of their own, forked after the spin-up and joined before the KGE.
 //   k_calib_kge  (xh_calib.hip) ED per (basin, member)
 //
+// Gauge form (xh_calib_gauge_desc): the basin is scored at stream gauges on cells inside the network instead of at its
+// outlets.  The closure is the UNION of the gauges' upstream closures (a subset of the outlet closure), routed once per
+// member by the same kernel -- same launch classes, LDS double buffer, one-barrier sub-step and flag protocol; ABCD runs
+// on the basin cells the closure holds.  There is no outlet stage: the lane that owns a gauge cell writes its
+// Avg_ChFlow = favg / nt straight to series[gauge][member][month] in the simulation pass, so the outlet sums' LDS
+// share and the two barriers per month around it go.  k_calib_kge_masked then scores every (gauge, member) over the
+// months with a finite observation and k_calib_gauge_combine forms the basin's weighted mean (xh_calib.hip).
+//
 // Everything is fp64 in the reference's operation order (-ffp-contract=off), summation orders are fixed, outputs are
 // written once: results are bit-identical run to run.
 #include <algorithm>
@@ -43,7 +51,7 @@ constexpr size_t LDS_LIMIT = 160 * 1024;     // per workgroup on gfx950
 struct FlowBasin {
     int nc, cell0, nout, tpm, mpw, klass;    // closure cells, first row, outlets, threads per member, members per group
     int64_t e0;                              // first entry of the closure's rows
-    int nnz, pad;
+    int nnz, g1;                             // gauge form: nout = the basin's gauges, g1 = one past its last gauge
 };
 
 // launch classes: threads per workgroup x cells per lane
@@ -64,7 +72,9 @@ __device__ __forceinline__ double gather(const int *__restrict__ ent, int e_lo, 
     return g;
 }
 
-template <int BT, int CPL>
+// GAUGE: g_orank holds, per closure row, the first gauge on that cell (index into the problem's gauges, which are sorted
+// by cell within a basin) or -1, g_grow the closure-local row of every gauge, and series is [gauge][member][month].
+template <int BT, int CPL, bool GAUGE>
 __global__ void __launch_bounds__(BT) k_calib_flow(const xh_calib_basin *__restrict__ basins,
                                                    const FlowBasin *__restrict__ fbs, const int2 *__restrict__ work,
                                                    const int *__restrict__ active, int nmonths, int rspin, double dt,
@@ -74,7 +84,8 @@ __global__ void __launch_bounds__(BT) k_calib_flow(const xh_calib_basin *__restr
                                                    const int64_t *__restrict__ row_ptr, const int *__restrict__ g_ent,
                                                    const double *__restrict__ g_tau, const double *__restrict__ g_area,
                                                    const double *__restrict__ g_s0, const int *__restrict__ g_bcol,
-                                                   const int *__restrict__ g_orank, double *__restrict__ series) {
+                                                   const int *__restrict__ g_orank, const int *__restrict__ g_grow,
+                                                   double *__restrict__ series) {
     extern __shared__ double lds[];
     const int2 wk = work[blockIdx.x];
     const int b = wk.x;
@@ -89,8 +100,8 @@ __global__ void __launch_bounds__(BT) k_calib_flow(const xh_calib_basin *__restr
     const int row = b * nmembers + min(mem, nmembers - 1);
 
     double *Fbuf = lds;                                              // [2][mpw][nc]
-    double *outv = lds + 2 * mpw * nc;                               // [mpw][nout]
-    int *ent = reinterpret_cast<int *>(outv + mpw * nout);           // [nnz]
+    double *outv = lds + 2 * mpw * nc;                               // [mpw][nout] (outlet form only)
+    int *ent = reinterpret_cast<int *>(outv + (GAUGE ? 0 : mpw * nout));   // [nnz]
     int *flag = ent + FB.nnz;                                        // [3]
     for (int e = t; e < FB.nnz; e += BT) ent[e] = g_ent[FB.e0 + e];
     if (t < 3) flag[t] = 0;
@@ -102,7 +113,7 @@ __global__ void __launch_bounds__(BT) k_calib_flow(const xh_calib_basin *__restr
     const double dtinv = 1.0 / dt;
 
     bool own[CPL];
-    int ci[CPL], e_lo[CPL], e_hi[CPL], bcol[CPL];
+    int ci[CPL], e_lo[CPL], e_hi[CPL], bcol[CPL], gfirst[CPL];
     double S[CPL], F[CPL], tau[CPL], erl[CPL], favg[CPL];
     AbcdState st[CPL];
 #pragma unroll
@@ -114,6 +125,7 @@ __global__ void __launch_bounds__(BT) k_calib_flow(const xh_calib_basin *__restr
         e_lo[k] = own[k] ? (int)(row_ptr[c] - FB.e0) : 0;
         e_hi[k] = own[k] ? (int)(row_ptr[c + 1] - FB.e0) : 0;
         bcol[k] = own[k] ? g_bcol[c] : -1;
+        gfirst[k] = (GAUGE && own[k]) ? g_orank[c] : -1;
         tau[k] = own[k] ? g_tau[c] : 0.0;
         S[k] = own[k] ? g_s0[c] : 0.0;
         F[k] = S[k] * tau[k];
@@ -203,26 +215,34 @@ __global__ void __launch_bounds__(BT) k_calib_flow(const xh_calib_basin *__restr
                 }
                 par ^= 1;
             }
+            if constexpr (GAUGE) {
+                if (pass == 1 && mem_ok) {
 #pragma unroll
-            for (int k = 0; k < CPL; ++k)
-                if (own[k]) {
-                    const int r = g_orank[FB.cell0 + ci[k]];
-                    if (r >= 0) outv[mloc * nout + r] = favg[k] / (double)nt;       // Avg_ChFlow (:80)
+                    for (int k = 0; k < CPL; ++k)
+                        if (gfirst[k] >= 0) {                        // every gauge on this cell: Avg_ChFlow (:80), nothing summed
+                            const double v = favg[k] / (double)nt;
+                            for (int g = gfirst[k]; g < FB.g1 && g_grow[g] == ci[k]; ++g)
+                                series[((int64_t)g * nmembers + mem) * nmonths + m] = v;
+                        }
                 }
-            __syncthreads();
-            if (pass == 1 && lane == 0 && mem_ok) {
-                double sum = 0.0;
-                for (int r = 0; r < nout; ++r) sum += outv[mloc * nout + r];
-                series[((int64_t)b * nmembers + mem) * nmonths + m] = sum;
+            } else {
+#pragma unroll
+                for (int k = 0; k < CPL; ++k)
+                    if (own[k]) {
+                        const int r = g_orank[FB.cell0 + ci[k]];
+                        if (r >= 0) outv[mloc * nout + r] = favg[k] / (double)nt;       // Avg_ChFlow (:80)
+                    }
+                __syncthreads();
+                if (pass == 1 && lane == 0 && mem_ok) {
+                    double sum = 0.0;
+                    for (int r = 0; r < nout; ++r) sum += outv[mloc * nout + r];
+                    series[((int64_t)b * nmembers + mem) * nmonths + m] = sum;
+                }
+                __syncthreads();                                     // outv is rewritten next month
             }
-            __syncthreads();                                         // outv is rewritten next month
         }
     }
 }
-
-template <int BT, int CPL>
-int launch_klass(xh_ctx *ctx, const xh_calib_problem &P, const xh_calib_flow &f, int kl, const double *d_pars,
-                 const int *d_active);
 
 }  // namespace
 
@@ -234,6 +254,11 @@ struct xh_calib_flow {
     int64_t *d_row_ptr = nullptr;
     int *d_ent = nullptr, *d_bcol = nullptr, *d_orank = nullptr, *d_ndays = nullptr, *d_nt = nullptr;
     double *d_tau = nullptr, *d_area = nullptr, *d_s0 = nullptr;
+    // gauge form: d_orank holds the first gauge of each closure row; per gauge its closure-local row, basin and weight,
+    // per basin its first gauge
+    int ngauge = 0;                          // 0 = the outlet form
+    int *d_grow = nullptr, *d_gbasin = nullptr, *d_gptr = nullptr;
+    double *d_gw = nullptr;
     int2 *d_work = nullptr;
     int work0[NKLASS] = {0}, nwork[NKLASS] = {0};
     size_t lds[NKLASS] = {0};
@@ -245,13 +270,20 @@ struct xh_calib_flow {
 
 namespace {
 
+template <int BT, int CPL, bool GAUGE>
+int launch_form(xh_ctx *ctx, const xh_calib_problem &P, const xh_calib_flow &f, int kl, const double *d_pars,
+                const int *d_active) {
+    return xh_launch(ctx, nullptr, kl ? f.side[kl] : ctx->stream, k_calib_flow<BT, CPL, GAUGE>, dim3((unsigned)f.nwork[kl]), dim3(BT), f.lds[kl],
+                     P.d_basins, f.d_fb, f.d_work + f.work0[kl], d_active, f.nmonths, f.rspin, f.dt, f.d_ndays, f.d_nt,
+                     P.nmembers, P.npar, d_pars, P.d_sm0, P.d_gw0, f.d_row_ptr, f.d_ent, f.d_tau, f.d_area, f.d_s0,
+                     f.d_bcol, f.d_orank, f.d_grow, P.d_series);
+}
+
 template <int BT, int CPL>
 int launch_klass(xh_ctx *ctx, const xh_calib_problem &P, const xh_calib_flow &f, int kl, const double *d_pars,
                  const int *d_active) {
-    return xh_launch(ctx, nullptr, kl ? f.side[kl] : ctx->stream, k_calib_flow<BT, CPL>, dim3((unsigned)f.nwork[kl]), dim3(BT), f.lds[kl],
-                     P.d_basins, f.d_fb, f.d_work + f.work0[kl], d_active, f.nmonths, f.rspin, f.dt, f.d_ndays, f.d_nt,
-                     P.nmembers, P.npar, d_pars, P.d_sm0, P.d_gw0, f.d_row_ptr, f.d_ent, f.d_tau, f.d_area, f.d_s0,
-                     f.d_bcol, f.d_orank, P.d_series);
+    return f.ngauge ? launch_form<BT, CPL, true>(ctx, P, f, kl, d_pars, d_active)
+                    : launch_form<BT, CPL, false>(ctx, P, f, kl, d_pars, d_active);
 }
 
 }  // namespace
@@ -270,13 +302,25 @@ void xh_calib_flow_destroy(xh_calib_flow *f) {
     delete f;
 }
 
-int xh_calib_flow_create(xh_ctx *ctx, int32_t nbasins, const int64_t *h_ncell, int32_t nmonths, int32_t nmembers,
-                         const xh_calib_flow_desc *d, xh_calib_flow **out) {
+namespace {
+
+// the gauge part of an xh_calib_gauge_desc (NULL = the outlet form, whose desc carries h_outlet_rank)
+struct GaugePart {
+    const int64_t *ptr;
+    const int32_t *row;
+    const double *weight;
+};
+
+int flow_create(xh_ctx *ctx, int32_t nbasins, const int64_t *h_ncell, int32_t nmonths, int32_t nmembers,
+                const xh_calib_flow_desc *d, const GaugePart *gp, xh_calib_flow **out) {
     XH_REQUIRE(ctx, d && out && h_ncell, "xh_calib_flow: NULL argument");
     *out = nullptr;
     XH_REQUIRE(ctx, d->h_ndays && d->h_closure_ptr && d->h_row_ptr && d->h_cols && d->h_sign && d->h_basin_col &&
-                        d->h_outlet_rank && d->h_tauinv && d->h_area && d->h_s0,
+                        (gp || d->h_outlet_rank) && d->h_tauinv && d->h_area && d->h_s0,
                "xh_calib_flow: NULL table");
+    XH_REQUIRE(ctx, !gp || (gp->ptr && gp->row && gp->weight), "xh_calib_flow: NULL gauge table");
+    const int64_t ngauge = gp ? gp->ptr[nbasins] : 0;
+    XH_REQUIRE(ctx, !gp || (gp->ptr[0] == 0 && ngauge > 0 && ngauge < ((int64_t)1 << 24)), "xh_calib_flow: bad gauge_ptr");
     XH_REQUIRE(ctx, d->routing_spinup >= 0 && d->routing_spinup <= nmonths,
                "xh_calib_flow: routing_spinup = %d must lie in [0, nmonths = %d]", d->routing_spinup, nmonths);
     XH_REQUIRE(ctx, d->dt > 0.0, "xh_calib_flow: dt must be positive");
@@ -294,6 +338,7 @@ int xh_calib_flow_create(xh_ctx *ctx, int32_t nbasins, const int64_t *h_ncell, i
     }
     std::vector<FlowBasin> fb(nbasins);
     std::vector<int> ent(nnz > 0 ? nnz : 1);
+    std::vector<int> gfirst(gp ? ncl : 0, -1), gbasin(ngauge), gptr(gp ? nbasins + 1 : 0);
     std::vector<std::vector<int2>> work(NKLASS);
     std::vector<size_t> lds(NKLASS, 0);
     for (int b = 0; b < nbasins; ++b) {
@@ -307,7 +352,7 @@ int xh_calib_flow_create(xh_ctx *ctx, int32_t nbasins, const int64_t *h_ncell, i
         B.cell0 = (int)c0;
         B.e0 = d->h_row_ptr[c0];
         B.nnz = (int)(d->h_row_ptr[c1] - B.e0);
-        B.pad = 0;
+        B.g1 = 0;
         int nout = 0, nbc = 0;
         for (int64_t c = c0; c < c1; ++c) {
             XH_REQUIRE(ctx, d->h_row_ptr[c + 1] >= d->h_row_ptr[c], "xh_calib_flow: row_ptr decreases");
@@ -320,13 +365,35 @@ int xh_calib_flow_create(xh_ctx *ctx, int32_t nbasins, const int64_t *h_ncell, i
             const int bc = d->h_basin_col[c];
             XH_REQUIRE(ctx, bc >= -1 && bc < h_ncell[b], "xh_calib_flow: basin %d: bad basin column %d", b, bc);
             nbc += bc >= 0;
+            if (gp) continue;
             const int r = d->h_outlet_rank[c];
             XH_REQUIRE(ctx, r == -1 || r == nout, "xh_calib_flow: basin %d: outlet ranks must count up in row order", b);
             nout += r >= 0;
         }
-        XH_REQUIRE(ctx, nbc == h_ncell[b], "xh_calib_flow: basin %d: %d closure rows carry forcing, the basin has %lld cells",
-                   b, nbc, (long long)h_ncell[b]);
-        XH_REQUIRE(ctx, nout > 0, "xh_calib_flow: basin %d has no outlet", b);
+        if (gp) {                                                    // the basin's gauges, sorted by closure row
+            const int64_t g0 = gp->ptr[b], g1 = gp->ptr[b + 1];
+            XH_REQUIRE(ctx, g1 > g0 && g1 <= ngauge, "xh_calib_flow: basin %d has no gauge", b);
+            for (int64_t g = g0; g < g1; ++g) {
+                const int r = gp->row[g];
+                XH_REQUIRE(ctx, r >= 0 && r < nc && (g == g0 || r >= gp->row[g - 1]),
+                           "xh_calib_flow: basin %d: gauge rows must lie in the closure and ascend", b);
+                XH_REQUIRE(ctx, d->h_basin_col[c0 + r] >= 0, "xh_calib_flow: gauge %lld is not on a cell of basin %d",
+                           (long long)g, b);
+                XH_REQUIRE(ctx, gp->weight[g] > 0.0 && std::isfinite(gp->weight[g]),
+                           "xh_calib_flow: gauge %lld: the weight must be positive and finite", (long long)g);
+                if (gfirst[c0 + r] < 0) gfirst[c0 + r] = (int)g;
+                gbasin[g] = b;
+            }
+            gptr[b] = (int)g0;
+            gptr[b + 1] = (int)g1;
+            nout = (int)(g1 - g0);
+            B.g1 = (int)g1;
+        } else {
+            // (the outlet form only: every basin cell is in the outlet closure; a union of gauge closures may leave some out)
+            XH_REQUIRE(ctx, nbc == h_ncell[b], "xh_calib_flow: basin %d: %d closure rows carry forcing, the basin has %lld cells",
+                       b, nbc, (long long)h_ncell[b]);
+            XH_REQUIRE(ctx, nout > 0, "xh_calib_flow: basin %d has no outlet", b);
+        }
         B.nout = nout;
         int kl = 0;
         while (nc > KLASSES[kl].hi) ++kl;
@@ -339,7 +406,7 @@ int xh_calib_flow_create(xh_ctx *ctx, int32_t nbasins, const int64_t *h_ncell, i
         B.tpm = tpm;
         B.mpw = K.bt / tpm;
         B.klass = kl;
-        const size_t bytes = sizeof(double) * (2 * (size_t)B.mpw * nc + (size_t)B.mpw * nout) + sizeof(int) * (B.nnz + 4);
+        const size_t bytes = sizeof(double) * (2 * (size_t)B.mpw * nc + (gp ? 0 : (size_t)B.mpw * nout)) + sizeof(int) * (B.nnz + 4);
         XH_REQUIRE(ctx, bytes <= LDS_LIMIT, "xh_calib_flow: basin %d needs %zu bytes of LDS, more than %zu", b, bytes,
                    LDS_LIMIT);
         lds[kl] = std::max(lds[kl], bytes);
@@ -351,6 +418,7 @@ int xh_calib_flow_create(xh_ctx *ctx, int32_t nbasins, const int64_t *h_ncell, i
     f->nmembers = nmembers;
     f->rspin = d->routing_spinup;
     f->dt = d->dt;
+    f->ngauge = (int)ngauge;
     std::vector<int2> all;
     for (int kl = NKLASS - 1; kl >= 0; --kl) {                       // (the largest closures first: the longest chains)
         std::stable_sort(work[kl].begin(), work[kl].end(),
@@ -366,7 +434,9 @@ int xh_calib_flow_create(xh_ctx *ctx, int32_t nbasins, const int64_t *h_ncell, i
                  o_nd = al(o_or + 4 * (size_t)ncl), o_nt = al(o_nd + 4 * (size_t)nmonths),
                  o_tau = al(o_nt + 4 * (size_t)nmonths), o_area = al(o_tau + 8 * (size_t)ncl),
                  o_s0 = al(o_area + 8 * (size_t)ncl), o_work = al(o_s0 + 8 * (size_t)ncl),
-                 total = al(o_work + sizeof(int2) * std::max<size_t>(all.size(), 1));
+                 o_grow = al(o_work + sizeof(int2) * std::max<size_t>(all.size(), 1)), o_gb = al(o_grow + 4 * (size_t)ngauge),
+                 o_gp = al(o_gb + 4 * (size_t)ngauge), o_gw = al(o_gp + 4 * gptr.size()),
+                 total = al(o_gw + 8 * (size_t)ngauge);
     hipError_t e = hipMalloc(&f->d_buf, total);
     if (e != hipSuccess) {
         xh_calib_flow_destroy(f);
@@ -384,16 +454,22 @@ int xh_calib_flow_create(xh_ctx *ctx, int32_t nbasins, const int64_t *h_ncell, i
     f->d_area = reinterpret_cast<double *>(base + o_area);
     f->d_s0 = reinterpret_cast<double *>(base + o_s0);
     f->d_work = reinterpret_cast<int2 *>(base + o_work);
+    f->d_grow = reinterpret_cast<int *>(base + o_grow);
+    f->d_gbasin = reinterpret_cast<int *>(base + o_gb);
+    f->d_gptr = reinterpret_cast<int *>(base + o_gp);
+    f->d_gw = reinterpret_cast<double *>(base + o_gw);
     const struct {
         void *dst;
         const void *src;
         size_t n;
     } up[] = {{f->d_fb, fb.data(), sizeof(FlowBasin) * nbasins}, {f->d_row_ptr, d->h_row_ptr, 8 * (size_t)(ncl + 1)},
               {f->d_ent, ent.data(), 4 * ent.size()},            {f->d_bcol, d->h_basin_col, 4 * (size_t)ncl},
-              {f->d_orank, d->h_outlet_rank, 4 * (size_t)ncl},   {f->d_ndays, d->h_ndays, 4 * (size_t)nmonths},
+              {f->d_orank, gp ? gfirst.data() : d->h_outlet_rank, 4 * (size_t)ncl},   {f->d_ndays, d->h_ndays, 4 * (size_t)nmonths},
               {f->d_nt, nt.data(), 4 * (size_t)nmonths},         {f->d_tau, d->h_tauinv, 8 * (size_t)ncl},
               {f->d_area, d->h_area, 8 * (size_t)ncl},           {f->d_s0, d->h_s0, 8 * (size_t)ncl},
-              {f->d_work, all.data(), sizeof(int2) * all.size()}};
+              {f->d_work, all.data(), sizeof(int2) * all.size()},
+              {f->d_grow, gp ? gp->row : nullptr, 4 * (size_t)ngauge},   {f->d_gbasin, gbasin.data(), 4 * (size_t)ngauge},
+              {f->d_gptr, gptr.data(), 4 * gptr.size()},         {f->d_gw, gp ? gp->weight : nullptr, 8 * (size_t)ngauge}};
     for (const auto &u : up) {
         if (!u.n) continue;
         e = hipMemcpyAsync(u.dst, u.src, u.n, hipMemcpyHostToDevice, ctx->stream);
@@ -421,6 +497,22 @@ int xh_calib_flow_create(xh_ctx *ctx, int32_t nbasins, const int64_t *h_ncell, i
     return XH_OK;
 }
 
+}  // namespace
+
+int xh_calib_flow_create(xh_ctx *ctx, int32_t nbasins, const int64_t *h_ncell, int32_t nmonths, int32_t nmembers,
+                         const xh_calib_flow_desc *d, xh_calib_flow **out) {
+    return flow_create(ctx, nbasins, h_ncell, nmonths, nmembers, d, nullptr, out);
+}
+
+int xh_calib_gauge_create(xh_ctx *ctx, int32_t nbasins, const int64_t *h_ncell, int32_t nmonths, int32_t nmembers,
+                          const xh_calib_gauge_desc *g, xh_calib_flow **out) {
+    XH_REQUIRE(ctx, g && out, "xh_calib_gauge: NULL argument");
+    const xh_calib_flow_desc d = {g->routing_spinup, g->dt,        g->h_ndays, g->h_closure_ptr, g->h_row_ptr, g->h_cols,
+                                  g->h_sign,         g->h_basin_col, nullptr,    g->h_tauinv,      g->h_area,    g->h_s0};
+    const GaugePart gp = {g->h_gauge_ptr, g->h_gauge_row, g->h_gauge_weight};
+    return flow_create(ctx, nbasins, h_ncell, nmonths, nmembers, &d, &gp, out);
+}
+
 int xh_calib_flow_enqueue(xh_ctx *ctx, const xh_calib_problem &P, const double *d_pars, const int *d_active, double *d_ed) {
     const xh_calib_flow &f = *P.flow;
     hipStream_t st = ctx->stream;
@@ -445,27 +537,37 @@ int xh_calib_flow_enqueue(xh_ctx *ctx, const xh_calib_problem &P, const double *
         return r;
     });
     if (rc) return rc;
+    if (f.ngauge)
+        return xh_timed(ctx, "calib_kge", st, [&] {
+            return xh_calib_gauge_score_enqueue(ctx, P, d_active, f.ngauge, f.d_gbasin, f.d_gptr, f.d_gw, P.d_series, d_ed);
+        });
     return xh_timed(ctx, "calib_kge", st, [&] { return xh_calib_kge_enqueue(ctx, P, d_active, P.d_series, d_ed); });
 }
 
-extern "C" int xh_calib_flow_objective_multi(xh_ctx *ctx, int32_t nbasins, const int64_t *h_ncell, int32_t nmonths,
-                                             int32_t spinup, int32_t nmembers, int32_t npar, const double *h_pars,
-                                             const double *const *h_pet_t, const double *const *h_precip_t,
-                                             const double *const *h_tmin_t, const xh_calib_flow_desc *flow,
-                                             const double *h_obs, double *h_ed, double *h_series) {
+// one evaluation of either form: `flow` (outlets) or `gauge`
+static int objective_multi(xh_ctx *ctx, const char *who, int32_t nbasins, const int64_t *h_ncell, int32_t nmonths,
+                           int32_t spinup, int32_t nmembers, int32_t npar, const double *h_pars,
+                           const double *const *h_pet_t, const double *const *h_precip_t, const double *const *h_tmin_t,
+                           const xh_calib_flow_desc *flow, const xh_calib_gauge_desc *gauge, const double *h_obs,
+                           double *h_ed, double *h_ed_gauge, double *h_series) {
     if (!ctx) return XH_ERR_ARG;
-    XH_REQUIRE(ctx, h_pars && h_obs && h_ed && flow, "xh_calib_flow_objective_multi: NULL argument");
+    XH_REQUIRE(ctx, h_pars && h_obs && h_ed && (flow || gauge), "%s: NULL argument", who);
+    XH_REQUIRE(ctx, !gauge || (gauge->h_gauge_ptr && nbasins > 0), "%s: NULL gauge table", who);
+    const int64_t ng64 = gauge ? gauge->h_gauge_ptr[nbasins] : 0;
+    XH_REQUIRE(ctx, !gauge || (ng64 > 0 && ng64 < ((int64_t)1 << 24)), "%s: bad gauge_ptr", who);
+    const int32_t ngauge = (int32_t)ng64;
     std::vector<xh_calib_basin> basins;
     std::vector<int> chunk_basin;
     size_t bytes = 0;
     int ml = 0;
     int rc = xh_calib_problem_plan(ctx, nbasins, h_ncell, nmonths, spinup, nmembers, npar, h_pet_t, h_precip_t, h_tmin_t,
-                                   nullptr, basins, chunk_basin, &bytes, &ml);
+                                   nullptr, basins, chunk_basin, &bytes, &ml, ngauge);
     if (rc) return rc;
     xh_calib_flow *f = nullptr;
-    rc = xh_calib_flow_create(ctx, nbasins, h_ncell, nmonths, nmembers, flow, &f);
+    rc = gauge ? xh_calib_gauge_create(ctx, nbasins, h_ncell, nmonths, nmembers, gauge, &f)
+               : xh_calib_flow_create(ctx, nbasins, h_ncell, nmonths, nmembers, flow, &f);
     if (rc) return rc;
-    const size_t nbm = (size_t)nbasins * nmembers;
+    const size_t nbm = (size_t)nbasins * nmembers, nsm = (size_t)(gauge ? ngauge : nbasins) * nmembers;
     const size_t io_bytes = ((nbm * npar + nbm) * sizeof(double) + 255) & ~size_t(255);
     void *buf = nullptr;
     rc = xh_scratch(ctx, 1, io_bytes + bytes, &buf);
@@ -474,22 +576,42 @@ extern "C" int xh_calib_flow_objective_multi(xh_ctx *ctx, int32_t nbasins, const
         double *d_pars = static_cast<double *>(buf);
         double *d_ed = d_pars + nbm * npar;
         const hipError_t e = hipMemcpyAsync(d_pars, h_pars, sizeof(double) * nbm * npar, hipMemcpyHostToDevice, ctx->stream);
-        rc = e == hipSuccess ? XH_OK : xh_fail(ctx, XH_ERR_HIP, "xh_calib_flow_objective_multi: %s", hipGetErrorString(e));
+        rc = e == hipSuccess ? XH_OK : xh_fail(ctx, XH_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
         if (!rc)
             rc = xh_calib_problem_place(ctx, P, nmonths, spinup, nmembers, npar, basins, chunk_basin, h_obs,
-                                        static_cast<char *>(buf) + io_bytes, ml);
+                                        static_cast<char *>(buf) + io_bytes, ml, ngauge);
         P.flow = f;
         if (!rc) rc = xh_calib_enqueue(ctx, P, d_pars, nullptr, d_ed);
         if (!rc) {
             hipError_t e2 = hipMemcpyAsync(h_ed, d_ed, sizeof(double) * nbm, hipMemcpyDeviceToHost, ctx->stream);
+            if (e2 == hipSuccess && h_ed_gauge && gauge)
+                e2 = hipMemcpyAsync(h_ed_gauge, P.d_ed_gauge, sizeof(double) * nsm, hipMemcpyDeviceToHost, ctx->stream);
             if (e2 == hipSuccess && h_series)
-                e2 = hipMemcpyAsync(h_series, P.d_series, sizeof(double) * nbm * nmonths, hipMemcpyDeviceToHost,
+                e2 = hipMemcpyAsync(h_series, P.d_series, sizeof(double) * nsm * nmonths, hipMemcpyDeviceToHost,
                                     ctx->stream);
             if (e2 == hipSuccess) e2 = hipStreamSynchronize(ctx->stream);
-            if (e2 != hipSuccess) rc = xh_fail(ctx, XH_ERR_HIP, "xh_calib_flow_objective_multi: %s", hipGetErrorString(e2));
+            if (e2 != hipSuccess) rc = xh_fail(ctx, XH_ERR_HIP, "%s: %s", who, hipGetErrorString(e2));
         }
     }
     (void)hipStreamSynchronize(ctx->stream);                         // nothing of the call may still run on f
     xh_calib_flow_destroy(f);
     return rc;
+}
+
+extern "C" int xh_calib_flow_objective_multi(xh_ctx *ctx, int32_t nbasins, const int64_t *h_ncell, int32_t nmonths,
+                                             int32_t spinup, int32_t nmembers, int32_t npar, const double *h_pars,
+                                             const double *const *h_pet_t, const double *const *h_precip_t,
+                                             const double *const *h_tmin_t, const xh_calib_flow_desc *flow,
+                                             const double *h_obs, double *h_ed, double *h_series) {
+    return objective_multi(ctx, "xh_calib_flow_objective_multi", nbasins, h_ncell, nmonths, spinup, nmembers, npar, h_pars,
+                           h_pet_t, h_precip_t, h_tmin_t, flow, nullptr, h_obs, h_ed, nullptr, h_series);
+}
+
+extern "C" int xh_calib_gauge_objective_multi(xh_ctx *ctx, int32_t nbasins, const int64_t *h_ncell, int32_t nmonths,
+                                              int32_t spinup, int32_t nmembers, int32_t npar, const double *h_pars,
+                                              const double *const *h_pet_t, const double *const *h_precip_t,
+                                              const double *const *h_tmin_t, const xh_calib_gauge_desc *gauge,
+                                              const double *h_obs, double *h_ed, double *h_ed_gauge, double *h_series) {
+    return objective_multi(ctx, "xh_calib_gauge_objective_multi", nbasins, h_ncell, nmonths, spinup, nmembers, npar, h_pars,
+                           h_pet_t, h_precip_t, h_tmin_t, nullptr, gauge, h_obs, h_ed, h_ed_gauge, h_series);
 }

@@ -57,6 +57,36 @@ def load_file(fn, header_num=0, key=None, mmap=False):
     raise RuntimeError('File {} has unrecognized extension'.format(fn))
 
 
+def load_gauges(gauges_file, observed_file, nmonths, missing=None):
+    """Stream gauges of [Calibrate]: ``gauges_file`` rows gauge_id,cell_id[,weight] (cell_id 1-based; default weight 1),
+    ``observed_file`` rows [gauge_id, *, *, value], ``nmonths`` rows per gauge in month order, NaN (or ``missing``) =
+    no observation.  Returns calibrate.gauge_tables.Gauges (cells 0-based, obs [ngauge, nmonths])."""
+    from .calibrate.gauge_tables import Gauges
+    tab = np.atleast_2d(np.asarray(load_file(gauges_file, 0), dtype=float))
+    if tab.shape[1] < 2:
+        raise ValidationException('gauges: every row needs gauge_id,cell_id[,weight]')
+    ids = tab[:, 0].astype(np.int64)
+    weights = tab[:, 2] if tab.shape[1] > 2 else np.ones(ids.size)
+    if isinstance(observed_file, str) and observed_file.endswith(('.csv', '.txt')):
+        # (genfromtxt: an empty field is a missing observation too, not the 0 load_file fills in)
+        rec = np.genfromtxt(observed_file, delimiter=',' if observed_file.endswith('.csv') else ' ')
+    else:
+        rec = load_file(observed_file, 0)
+    rec = np.atleast_2d(np.asarray(rec, dtype=float))
+    if rec.shape[1] < 4:
+        raise ValidationException('gauge_observed: every row needs four columns, gauge id first and the value last')
+    obs = np.full((ids.size, nmonths), np.nan)
+    for i, g in enumerate(ids):
+        rows = rec[rec[:, 0] == g][:nmonths, 3]
+        if 0 < rows.size < nmonths:
+            raise ValidationException('gauge_observed: gauge {} has {} rows, the run has {} months'.format(
+                int(g), rows.size, nmonths))
+        obs[i, :rows.size] = rows
+    if missing is not None:
+        obs[obs == missing] = np.nan
+    return Gauges(ids, tab[:, 1].astype(np.int64) - 1, weights, obs)
+
+
 def _present(f):
     return isinstance(f, np.ndarray) or (isinstance(f, str) and os.path.isfile(f))
 
@@ -184,7 +214,11 @@ class DataLoader:
             self.chs_prev = self.load_chs_data()
 
         if s.calibrate:
-            self.cal_obs = np.asarray(load_file(s.cal_observed, 0))[:, [0, 3]]
+            self.cal_obs = None if s.cal_observed is None else np.asarray(load_file(s.cal_observed, 0))[:, [0, 3]]
+            self.gauges = None
+            if getattr(s, 'cal_gauges', None) is not None:
+                self.gauges = load_gauges(s.cal_gauges, s.cal_gauge_observed, s.nmonths,
+                                          getattr(s, 'cal_gauge_missing', None))
 
     @property
     def tairprev_load(self):

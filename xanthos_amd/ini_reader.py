@@ -486,7 +486,22 @@ class ConfigReader:
     def configure_calibration(self, cfg):
         """[Calibrate] (ini_reader.py:506-519)."""
         self.set_calibrate = int(cfg['set_calibrate'])
-        self.cal_observed = cfg['observed']
+        # stream gauges inside the network (set_calibrate = 1 only): `gauges` = csv gauge_id,cell_id[,weight] (cell_id
+        # 1-based, as the coordinates' first column), `gauge_observed` = the four-column layout of `observed` with the
+        # gauge id in column 0 (nmonths rows per gauge in month order, value in column 3, NaN = missing), `gauge_missing`
+        # = a sentinel value also read as missing.  `observed` is not required when they are given.
+        self.cal_gauges = cfg.get('gauges')
+        self.cal_gauge_observed = cfg.get('gauge_observed')
+        self.cal_gauge_missing = None if cfg.get('gauge_missing') is None else float(cfg['gauge_missing'])
+        given = [k for k in ('gauges', 'gauge_observed', 'gauge_missing') if cfg.get(k) is not None]
+        if given and self.set_calibrate != 1:
+            raise ValidationException('[Calibrate] {} is valid only with set_calibrate = 1 (calibration against routed '
+                                      'streamflow); set_calibrate = {}.'.format(', '.join(given), self.set_calibrate))
+        if (self.cal_gauges is None) != (self.cal_gauge_observed is None):
+            raise ValidationException('[Calibrate] gauges and gauge_observed go together: the stations and their records.')
+        if self.cal_gauges is None and 'observed' not in cfg:
+            raise ValidationException('[Calibrate] needs observed (or, with set_calibrate = 1, gauges and gauge_observed).')
+        self.cal_observed = cfg.get('observed')
         self.obs_unit = self.ck_obs_unit(self.set_calibrate, cfg['obs_unit'])
         self.calib_out_dir = cfg['calib_out_dir']
         basins = cfg.get('calibration_basins')

@@ -217,7 +217,7 @@ def data_bag(world, forcing):
 def write_example(root, world, forcing, start_year, end_year, project='pm_abcd_mrtm_synth', runoff_spinup=36,
                   routing_spinup=None, output_vars=('q', 'avgchflow'), obs=None, post=False, aggregates=False,
                   hist_flag=True, ch_storage=None, output_format=1, output_in_year=0, set_calibrate=0,
-                  calibration_basins='1-2'):
+                  calibration_basins='1-2', gauges=None, gauge_obs=None, gauge_missing=None):
     """Write ``world`` + ``forcing`` as a Xanthos-style input tree under ``root`` and return the .ini path.
 
     Layout and file names follow the reference's example (ini_reader.py:254-279, 353-381, 399-416, 425-437):
@@ -232,6 +232,9 @@ def write_example(root, world, forcing, start_year, end_year, project='pm_abcd_m
     ``obs`` (rows [basin, 0, 0, value]) switches calibration on: ``set_calibrate = 0`` against runoff in km3_per_mth,
     ``set_calibrate = 1`` against the basins' outlet streamflow in m3_per_sec (the values then made by the caller, e.g.
     from known parameters), for ``calibration_basins``.
+    ``gauges`` (rows [gauge_id, cell_id (1-based)[, weight]]) + ``gauge_obs`` (rows [gauge_id, 0, 0, value], NaN =
+    missing; ``gauge_missing``: a sentinel written to the ini) switch on ``set_calibrate = 1`` at stream gauges; ``obs``
+    is then optional.
     """
     import os
     inp = os.path.join(root, 'input')
@@ -261,7 +264,20 @@ def write_example(root, world, forcing, start_year, end_year, project='pm_abcd_m
     nmonths = (end_year - start_year + 1) * 12
     ini = os.path.join(root, project + '.ini')
     calib = ''
-    if obs is not None:
+    if gauges is not None:
+        lines = 'set_calibrate = 1\n'
+        if obs is not None:
+            np.savetxt(os.path.join(inp, 'obs.csv'), obs, delimiter=',', fmt='%.17g')
+            lines += 'observed = {}\n'.format(os.path.join(inp, 'obs.csv'))
+        np.savetxt(os.path.join(inp, 'gauges.csv'), np.atleast_2d(gauges), delimiter=',', fmt='%.17g')
+        np.savetxt(os.path.join(inp, 'gauge_obs.csv'), gauge_obs, delimiter=',', fmt='%.17g')
+        lines += 'gauges = {}\ngauge_observed = {}\n'.format(os.path.join(inp, 'gauges.csv'),
+                                                           os.path.join(inp, 'gauge_obs.csv'))
+        if gauge_missing is not None:
+            lines += 'gauge_missing = {!r}\n'.format(float(gauge_missing))
+        calib = '\n[Calibrate]\n{}obs_unit = m3_per_sec\ncalib_out_dir = {}\ncalibration_basins = {}\n'.format(
+            lines, os.path.join(root, 'calib_out'), calibration_basins)
+    elif obs is not None:
         obs_file = os.path.join(inp, 'obs.csv')
         np.savetxt(obs_file, obs, delimiter=',', fmt='%.17g')
         calib = ('\n[Calibrate]\nset_calibrate = {}\nobserved = {}\nobs_unit = {}\ncalib_out_dir = {}\n'
@@ -360,7 +376,7 @@ channel_velocity = velocity.npy
 flow_distance = flow_dist.npy
 flow_direction = flow_dir.npy
 {calib}{post_sections}'''.format(ofmt=int(output_format), oyear=int(output_in_year), chs=chs_lines, hist='True' if hist_flag else 'False', post_project=post_project, post_sections=post_sections, project=project, root=root, nb=world.n_basins, ncell=world.ncell, nrow=world.nrow, ncol=world.ncol,
-                  y0=start_year, y1=end_year, ov=', '.join(output_vars), cal=int(obs is not None), nlcs=world.nlcs,
+                  y0=start_year, y1=end_year, ov=', '.join(output_vars), cal=int(obs is not None or gauges is not None), nlcs=world.nlcs,
                   lcy=', '.join(str(y) for y in world.lc_years), rsp=runoff_spinup,
                   rtsp=nmonths if routing_spinup is None else routing_spinup,
                   pr=os.path.join(dirs['ro'], 'pr.npy'), tn=os.path.join(dirs['ro'], 'tmin.npy'), calib=calib))
