@@ -521,6 +521,36 @@ int xh_calib_gauge_objective_multi(xh_ctx *ctx, int32_t nbasins, const int64_t *
                                    const xh_calib_gauge_desc *gauge, const double *h_obs, double *h_ed,
                                    double *h_ed_gauge, double *h_series);
 
+/* ------------------------------------------------------------------ streamflow objective with a velocity scale
+ * One more calibration parameter per basin, the dimensionless velocity scale v > 0, in either form above.  Steps of the
+ * contract other than the routing are unchanged; the routing (mrtm.py:42 on a scaled channel velocity) uses
+ *   ChV_i' = v ChV_i for the closure's cells of basin B,  ChV_i' = ChV_i for its cells outside B (those belong to
+ *   another basin's calibration),  tau^-1 = (v ChV_i) / L_i: the product first, then the IEEE quotient.
+ * A member's row of parameters is [a, b, c, d, (m), v]: h_pars [nbasins, nmembers, npar + 1], npar = 4 or 5 still
+ * counting the ABCD genes.  v = 1.0 returns the bits of the form without the scale, and a member's result depends on its
+ * own row only.  Beside the desc of the form:
+ *   h_velocity, h_length [ncl]   ChV (m/s) and L (m) of every closure row; h_tauinv must equal h_velocity / h_length   */
+typedef struct {
+    const double *h_velocity;
+    const double *h_length;
+} xh_calib_velocity_desc;
+
+/* As xh_calib_flow_objective_multi (calibrate_abcd.py:134-213 with mrtm.py:42 on the scaled ChV), h_pars rows
+ * [npar + 1].                                                                                                    */
+int xh_calib_flow_velocity_objective_multi(xh_ctx *ctx, int32_t nbasins, const int64_t *h_ncell, int32_t nmonths,
+                                           int32_t spinup, int32_t nmembers, int32_t npar, const double *h_pars,
+                                           const double *const *h_pet_t, const double *const *h_precip_t,
+                                           const double *const *h_tmin_t, const xh_calib_flow_desc *flow,
+                                           const xh_calib_velocity_desc *velocity, const double *h_obs, double *h_ed,
+                                           double *h_series);
+/* As xh_calib_gauge_objective_multi (the same lines, scored at gauges), h_pars rows [npar + 1].                 */
+int xh_calib_gauge_velocity_objective_multi(xh_ctx *ctx, int32_t nbasins, const int64_t *h_ncell, int32_t nmonths,
+                                            int32_t spinup, int32_t nmembers, int32_t npar, const double *h_pars,
+                                            const double *const *h_pet_t, const double *const *h_precip_t,
+                                            const double *const *h_tmin_t, const xh_calib_gauge_desc *gauge,
+                                            const xh_calib_velocity_desc *velocity, const double *h_obs, double *h_ed,
+                                            double *h_ed_gauge, double *h_series);
+
 /* ------------------------------------------------------------------ differential evolution on the device
  * Replaces the scipy.optimize.differential_evolution call of calibrate/calibrate_abcd.py:calibrate_basin (:103-112,
  * SciPy defaults: best1bin, Latin-hypercube start, dither (0.5, 1), recombination 0.7, tol 0.01, polish off) AND the
@@ -560,6 +590,20 @@ int xh_calib_de_create_gauge(xh_ctx *ctx, int32_t nbasins, const int64_t *h_ncel
                              const double *const *h_pet_t, const double *const *h_precip_t,
                              const double *const *h_tmin_t, const xh_calib_gauge_desc *gauge, const double *h_obs,
                              const double *h_lo, const double *h_hi, uint64_t seed, xh_calib_de **out);
+/* The same searches (calibrate_abcd.py:103-112) on the velocity forms of the streamflow objective: npar = 4 or 5 ABCD
+ * genes, the search has npar + 1 genes with v last; h_lo / h_hi [npar + 1], results and states [.., npar + 1].     */
+int xh_calib_de_create_flow_velocity(xh_ctx *ctx, int32_t nbasins, const int64_t *h_ncell, const uint64_t *h_basin_key,
+                                     int32_t nmonths, int32_t spinup, int32_t nmembers, int32_t npar,
+                                     const double *const *h_pet_t, const double *const *h_precip_t,
+                                     const double *const *h_tmin_t, const xh_calib_flow_desc *flow,
+                                     const xh_calib_velocity_desc *velocity, const double *h_obs, const double *h_lo,
+                                     const double *h_hi, uint64_t seed, xh_calib_de **out);
+int xh_calib_de_create_gauge_velocity(xh_ctx *ctx, int32_t nbasins, const int64_t *h_ncell, const uint64_t *h_basin_key,
+                                      int32_t nmonths, int32_t spinup, int32_t nmembers, int32_t npar,
+                                      const double *const *h_pet_t, const double *const *h_precip_t,
+                                      const double *const *h_tmin_t, const xh_calib_gauge_desc *gauge,
+                                      const xh_calib_velocity_desc *velocity, const double *h_obs, const double *h_lo,
+                                      const double *h_hi, uint64_t seed, xh_calib_de **out);
 void xh_calib_de_destroy(xh_calib_de *de);
 int xh_calib_de_init(xh_calib_de *de);
 int xh_calib_de_step(xh_calib_de *de, int32_t ngen, double tol, double atol, double mut_lo, double mut_hi,

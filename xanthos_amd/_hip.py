@@ -79,6 +79,16 @@ def gauge_desc(tables):
         t.gauge_weight)])
 
 
+class CalibVelocityDesc(Structure):
+    """xh_calib_velocity_desc (include/xanthos_hip.h): ChV and L of every closure row, for the velocity forms."""
+    _fields_ = [('h_velocity', c_void_p), ('h_length', c_void_p)]
+
+
+def velocity_desc(tables):
+    """CalibVelocityDesc over ``tables.velocity`` and ``tables.length`` (FlowTables or GaugeTables); keep ``tables`` alive."""
+    return CalibVelocityDesc(_host_ptr(tables.velocity), _host_ptr(tables.length))
+
+
 _P = c_void_p
 # name -> (restype, argtypes); mirrors include/xanthos_hip.h one to one
 SIGNATURES = {
@@ -138,6 +148,17 @@ SIGNATURES = {
                                                POINTER(CalibGaugeDesc), _P, _P, _P, _P]),
     'xh_calib_de_create_gauge': (c_int, [_P, c_int32, _P, _P, c_int32, c_int32, c_int32, c_int32, _P, _P, _P,
                                          POINTER(CalibGaugeDesc), _P, _P, _P, c_uint64, POINTER(c_void_p)]),
+    'xh_calib_flow_velocity_objective_multi': (c_int, [_P, c_int32, _P, c_int32, c_int32, c_int32, c_int32, _P, _P, _P, _P,
+                                                       POINTER(CalibFlowDesc), POINTER(CalibVelocityDesc), _P, _P, _P]),
+    'xh_calib_gauge_velocity_objective_multi': (c_int, [_P, c_int32, _P, c_int32, c_int32, c_int32, c_int32, _P, _P, _P, _P,
+                                                        POINTER(CalibGaugeDesc), POINTER(CalibVelocityDesc), _P, _P, _P,
+                                                        _P]),
+    'xh_calib_de_create_flow_velocity': (c_int, [_P, c_int32, _P, _P, c_int32, c_int32, c_int32, c_int32, _P, _P, _P,
+                                                 POINTER(CalibFlowDesc), POINTER(CalibVelocityDesc), _P, _P, _P, c_uint64,
+                                                 POINTER(c_void_p)]),
+    'xh_calib_de_create_gauge_velocity': (c_int, [_P, c_int32, _P, _P, c_int32, c_int32, c_int32, c_int32, _P, _P, _P,
+                                                  POINTER(CalibGaugeDesc), POINTER(CalibVelocityDesc), _P, _P, _P, c_uint64,
+                                                  POINTER(c_void_p)]),
     'xh_calib_de_destroy': (None, [_P]),
     'xh_calib_de_init': (c_int, [_P]),
     'xh_calib_de_step': (c_int, [_P, c_int32, c_double, c_double, c_double, c_double, c_double, POINTER(c_int32)]),
@@ -551,11 +572,13 @@ class Context:
         return (ed, series) if want_series else ed
 
     def calib_flow_objective_multi(self, ncells, nmonths, spinup, pars, pet_t, precip_t, tmin_t, tables, obs,
-                                   want_series=False):
+                                   want_series=False, velocity=False):
         """Streamflow objective (set_calibrate = 1) of several basins at once: as calib_objective_multi, with the
-        closure tables ``tables`` (calibrate.flow_tables.FlowTables) instead of areas. series = outlet flow [m3/s]."""
+        closure tables ``tables`` (calibrate.flow_tables.FlowTables) instead of areas. series = outlet flow [m3/s].
+        velocity: the rows of pars end in the basin's velocity scale v, [a, b, c, d, (m), v]."""
         pars = as_f64(pars)
         nb, nmem, npar = pars.shape
+        npar -= 1 if velocity else 0            # the library counts the ABCD genes
         obs = as_f64(obs)
         if obs.shape != (nb, nmonths):
             raise ValueError('obs must be [nbasins, nmonths]')
@@ -564,6 +587,13 @@ class Context:
         desc = flow_desc(tables)
         ed = np.empty((nb, nmem))
         series = np.empty((nb, nmem, nmonths)) if want_series else None
+        if velocity:
+            vdesc = velocity_desc(tables)
+            self._check(lib().xh_calib_flow_velocity_objective_multi(
+                self.handle, nb, _host_ptr(nc), nmonths, spinup, nmem, npar, _host_ptr(pars), ptrs(pet_t), ptrs(precip_t),
+                ptrs(tmin_t), byref(desc), byref(vdesc), _host_ptr(obs), _host_ptr(ed),
+                _host_ptr(series) if want_series else None))
+            return (ed, series) if want_series else ed
         self._check(lib().xh_calib_flow_objective_multi(self.handle, nb, _host_ptr(nc), nmonths, spinup, nmem, npar,
                                                         _host_ptr(pars), ptrs(pet_t), ptrs(precip_t), ptrs(tmin_t),
                                                         byref(desc), _host_ptr(obs), _host_ptr(ed),
@@ -571,12 +601,14 @@ class Context:
         return (ed, series) if want_series else ed
 
     def calib_gauge_objective_multi(self, ncells, nmonths, spinup, pars, pet_t, precip_t, tmin_t, tables, want_series=False,
-                                    want_gauges=False):
+                                    want_gauges=False, velocity=False):
         """Gauge form of the streamflow objective: ``tables`` = calibrate.gauge_tables.GaugeTables (union closures, gauges
         and their observations [ngauge, nmonths], NaN = missing).  Returns ed [nb, nmem] -- then, as asked, series
-        [ngauge, nmem, nmonths] (the gauge flows, m3/s) and ed_gauge [ngauge, nmem]."""
+        [ngauge, nmem, nmonths] (the gauge flows, m3/s) and ed_gauge [ngauge, nmem].
+        velocity: the rows of pars end in the basin's velocity scale v, [a, b, c, d, (m), v]."""
         pars = as_f64(pars)
         nb, nmem, npar = pars.shape
+        npar -= 1 if velocity else 0
         obs = as_f64(tables.obs)
         ng = int(tables.gauge_ptr[-1])
         if obs.shape != (ng, nmonths) or len(tables.basins) != nb:
@@ -588,11 +620,18 @@ class Context:
         ed = np.empty((nb, nmem))
         series = np.empty((ng, nmem, nmonths)) if want_series else None
         edg = np.empty((ng, nmem)) if want_gauges else None
-        self._check(lib().xh_calib_gauge_objective_multi(self.handle, nb, _host_ptr(nc), nmonths, spinup, nmem, npar,
-                                                         _host_ptr(pars), ptrs(pet_t), ptrs(precip_t), ptrs(tmin_t),
-                                                         byref(desc), _host_ptr(obs), _host_ptr(ed),
-                                                         _host_ptr(edg) if want_gauges else None,
-                                                         _host_ptr(series) if want_series else None))
+        if velocity:
+            vdesc = velocity_desc(tables)
+            self._check(lib().xh_calib_gauge_velocity_objective_multi(
+                self.handle, nb, _host_ptr(nc), nmonths, spinup, nmem, npar, _host_ptr(pars), ptrs(pet_t), ptrs(precip_t),
+                ptrs(tmin_t), byref(desc), byref(vdesc), _host_ptr(obs), _host_ptr(ed),
+                _host_ptr(edg) if want_gauges else None, _host_ptr(series) if want_series else None))
+        else:
+            self._check(lib().xh_calib_gauge_objective_multi(self.handle, nb, _host_ptr(nc), nmonths, spinup, nmem, npar,
+                                                             _host_ptr(pars), ptrs(pet_t), ptrs(precip_t), ptrs(tmin_t),
+                                                             byref(desc), _host_ptr(obs), _host_ptr(ed),
+                                                             _host_ptr(edg) if want_gauges else None,
+                                                             _host_ptr(series) if want_series else None))
         out = (ed,) + ((series,) if want_series else ()) + ((edg,) if want_gauges else ())
         return out if len(out) > 1 else ed
 
@@ -789,10 +828,11 @@ class CalibDE:
     None) that must stay alive as long as the session; obs [nb, nmonths]; bounds [(lo, hi)] * npar; keys [nb] RNG
     stream of each basin (e.g. the basin number) so that a basin's search does not depend on its companions.
     flow: calibrate.flow_tables.FlowTables (the streamflow objective at the outlets) or calibrate.gauge_tables.GaugeTables
-    (at stream gauges; obs is then [ngauge, nmonths], NaN = missing)."""
+    (at stream gauges; obs is then [ngauge, nmonths], NaN = missing).  velocity (with flow): the last of the bounds is
+    that of the basins' velocity scale, which the search calibrates with the ABCD parameters."""
 
     def __init__(self, ctx, ncells, nmonths, spinup, nmembers, bounds, pet_t, precip_t, tmin_t, area, obs, seed=0,
-                 keys=None, flow=None):
+                 keys=None, flow=None, velocity=False):
         self.ctx = ctx
         nc = np.ascontiguousarray(ncells, dtype=np.int64)
         self.nb, self.n, self.d = int(nc.size), int(nmembers), len(bounds)
@@ -805,6 +845,17 @@ class CalibDE:
         ptrs = lambda lst: None if lst is None else (c_void_p * self.nb)(*[_dptr(x) for x in lst])
         self._keep = (pet_t, precip_t, tmin_t, area)
         h = c_void_p()
+        if velocity:                # the velocity forms: d - 1 ABCD genes, then v
+            if flow is None:
+                raise ValueError('the velocity scale belongs to the streamflow objective: flow is None')
+            create = lib().xh_calib_de_create_gauge_velocity if gauge_form else lib().xh_calib_de_create_flow_velocity
+            desc = gauge_desc(flow) if gauge_form else flow_desc(flow)
+            ctx._check(create(ctx.handle, self.nb, _host_ptr(nc), None if kk is None else _host_ptr(kk), nmonths, spinup,
+                              self.n, self.d - 1, ptrs(pet_t), ptrs(precip_t), ptrs(tmin_t), byref(desc),
+                              byref(velocity_desc(flow)), _host_ptr(obs), _host_ptr(lo), _host_ptr(hi),
+                              int(seed) & 0xFFFFFFFFFFFFFFFF, byref(h)))
+            self.handle = h.value
+            return
         if gauge_form:              # the streamflow objective at gauges: flow = calibrate.gauge_tables.GaugeTables
             ctx._check(lib().xh_calib_de_create_gauge(ctx.handle, self.nb, _host_ptr(nc),
                                                       None if kk is None else _host_ptr(kk), nmonths, spinup, self.n, self.d,

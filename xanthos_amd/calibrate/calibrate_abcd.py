@@ -23,6 +23,12 @@ With ``gauges`` (gauge_tables.Gauges: stream gauges on cells inside the network,
 scored at the gauges instead of the outlets: each basin is routed once per member on the union of its gauges' upstream
 closures, every gauge is scored over its finite months, and the basin's energy is the weighted mean of its gauges' ED
 (gauge_tables.py).  ``calibrate_all`` then also writes ``gauge_kge.csv``.
+
+With velocity bounds (``velocity_bounds = (lo, hi)``; ``[Calibrate] calibrate_velocity = 1``) the streamflow objective, in
+either form, has one more parameter per basin: the dimensionless velocity scale v, last in the vector [a, b, c, d, (m), v].
+The basin's own cells are routed with tau^-1 = (v ChV) / L, the closure's foreign cells with their own ChV / L (DESIGN
+4.4).  The reference's two files per basin keep their names and shapes (the ABCD columns only); v goes to
+``velocity_scale_basin_N.npy`` and ``calibrate_all`` writes ``velocity_scale.csv`` for a forward run (velocity_scale.py).
 """
 import logging
 import os
@@ -33,6 +39,7 @@ import numpy as np
 from .. import _hip
 from .flow_tables import FlowTables, check_forcing
 from .gauge_tables import GaugeTables
+from .velocity_scale import DEFAULT_BOUNDS, check_bounds, combined_scales, write_velocity_scale
 
 LB = 1e-4
 UB = 1 - LB
@@ -99,6 +106,11 @@ class BasinSet:
         # gauge form: one record per gauge [ngauge, nmonths], NaN = missing
         self.obs = self.flow.obs if self.gauge_form else np.stack([o.obs for o in self.objs])
         self.bounds = cals[0].bounds
+        # the velocity form: rows of parameters are [npar ABCD genes, v]
+        self.velocity = cals[0].velocity_bounds is not None
+        if any((c.velocity_bounds is not None) != self.velocity or c.bounds != self.bounds for c in cals):
+            raise ValueError('the basins of a set share their bounds')
+        self.nx = self.npar + (1 if self.velocity else 0)
 
     def args(self):
         o = self.objs
@@ -108,24 +120,29 @@ class BasinSet:
 
     def evaluate(self, pars, want_series=False, want_gauges=False):
         """ED for parameter sets pars [nbasins, nmembers, npar] in ONE launch (and the modelled series).  Gauge form: the
-        series is [ngauge, nmembers, nmonths], and ``want_gauges`` adds ED of every gauge [ngauge, nmembers]."""
+        series is [ngauge, nmembers, nmonths], and ``want_gauges`` adds ED of every gauge [ngauge, nmembers].  With
+        velocity bounds pars is [nbasins, nmembers, npar + 1], the velocity scale last."""
         nc, pet, pr, tn, ar = self.args()
-        pars = np.asarray(pars)[:, :, :self.npar]
+        pars = np.asarray(pars)
+        if pars.ndim != 3 or pars.shape[2] < self.nx:
+            raise ValueError('pars must be [nbasins, nmembers, {}]'.format(self.nx))
+        pars = pars[:, :, :self.nx]
         if self.gauge_form:
             return self.ctx.calib_gauge_objective_multi(nc, self.n_months, self.spinup, pars, pet, pr, tn, self.flow,
-                                                        want_series=want_series, want_gauges=want_gauges)
+                                                        want_series=want_series, want_gauges=want_gauges,
+                                                        velocity=self.velocity)
         if want_gauges:
             raise ValueError('want_gauges needs gauge tables')
         if self.flow is not None:
             return self.ctx.calib_flow_objective_multi(nc, self.n_months, self.spinup, pars, pet, pr, tn, self.flow,
-                                                       self.obs, want_series=want_series)
+                                                       self.obs, want_series=want_series, velocity=self.velocity)
         return self.ctx.calib_objective_multi(nc, self.n_months, self.spinup, pars, pet, pr, tn, ar, self.obs,
                                               want_series=want_series)
 
     def solver(self, nmembers, seed=0):
         nc, pet, pr, tn, ar = self.args()
         return _hip.CalibDE(self.ctx, nc, self.n_months, self.spinup, nmembers, self.bounds, pet, pr, tn, ar, self.obs,
-                            seed=seed, keys=[c.basin_num for c in self.cals], flow=self.flow)
+                            seed=seed, keys=[c.basin_num for c in self.cals], flow=self.flow, velocity=self.velocity)
 
     def close(self):
         for o in self.objs:
@@ -164,12 +181,20 @@ class Calibrate:
 
     def __init__(self, basin_num, basin_ids, basin_areas, precip, pet, obs, tmin, n_months, runoff_spinup,
                  set_calibrate, obs_unit, out_dir, router_func=None, device=0, seed=None, um=None, flow_dist=None,
-                 velocity=None, chs_prev=None, ndays=None, routing_spinup=0, dt=10800, flow=None, gauges=None):
+                 velocity=None, chs_prev=None, ndays=None, routing_spinup=0, dt=10800, flow=None, gauges=None,
+                 velocity_bounds=None):
         """set_calibrate = 1 also needs the routing inputs: ``um`` (routing.mrtm.upstream_genmatrix), ``flow_dist``,
         ``velocity``, ``chs_prev`` (None = zeros), ``ndays`` [nmonths] and ``routing_spinup`` -- or ``flow``, this
         basin's FlowTables.  ``router_func`` is kept for the reference's signature and not called.
         ``gauges`` (gauge_tables.Gauges; or ``flow`` = this basin's GaugeTables): score the basin at its stream gauges
-        instead of its outlets; ``obs`` may then be None."""
+        instead of its outlets; ``obs`` may then be None.
+        ``velocity_bounds`` = (lo, hi), 0 < lo < hi (set_calibrate = 1 only): also calibrate the basin's velocity scale;
+        the bounds list gains it as its last entry."""
+        if velocity_bounds is not None:
+            if set_calibrate != 1:
+                raise ValueError('velocity_bounds need set_calibrate = 1: the velocity scale acts on the routing')
+            velocity_bounds = check_bounds(velocity_bounds, 'velocity_bounds')
+        self.velocity_bounds = velocity_bounds
         if gauges is not None and set_calibrate != 1:
             raise ValueError('gauges need set_calibrate = 1')
         if set_calibrate not in (0, 1):
@@ -193,7 +218,10 @@ class Calibrate:
         self.bounds = [(LB, UB), (LB, 8 - LB), (LB, UB), (LB, UB), (LB, UB)]          # :62-64
         if self.nosnow:
             self.bounds.pop()
-        self.all_pars = np.zeros((1, len(self.bounds)))
+        self.all_pars = np.zeros((1, len(self.bounds)))                               # the ABCD columns only
+        self.velocity_scale = np.ones(1)
+        if velocity_bounds is not None:
+            self.bounds.append(velocity_bounds)
         self.kge_vals = np.zeros(1)
         self.basin_idx = np.where(np.asarray(basin_ids) == basin_num)
         self.bsn_areas = np.asarray(basin_areas)[self.basin_idx]
@@ -227,7 +255,8 @@ class Calibrate:
         logging.debug('\t\tFinished calibration for basin {0} which contains {1} grid cells.'.format(
             self.basin_num, self.basin_idx[0].shape[0]))
         logging.debug('\t\tPopulation size:  {}'.format(popsize))
-        logging.debug('\t\tParameter values ({}):  {}'.format(','.join(list(self.par_names())), x[0]))
+        logging.debug('\t\tParameter values ({}):  {}'.format(
+            ','.join(list(self.par_names()) + ['v'] * (self.velocity_bounds is not None)), x[0]))
         logging.debug('\t\tKGE:  {}'.format(1 - ed[0]))
         logging.debug('\t\tNumber of function evaluations:  {} in {} generations'.format(int(nfev[0]), int(nit[0])))
         logging.debug('\t\tCalibration time (seconds):  {}'.format(time.time() - st))
@@ -236,13 +265,19 @@ class Calibrate:
         return 'abcd' + 'm' * (not self.nosnow)
 
     def _store(self, x, ed, nfev, save=True):
-        self.all_pars[0, :] = x
+        """x = the best vector: the ABCD parameters, then the velocity scale if it was calibrated."""
+        nabcd = self.all_pars.shape[1]
+        self.all_pars[0, :] = x[:nabcd]
+        if self.velocity_bounds is not None:
+            self.velocity_scale[0] = x[nabcd]
         self.kge_vals[0] = 1 - ed
         self.nfev = nfev
         if save and self.out_dir is not None:
             os.makedirs(self.out_dir, exist_ok=True)
             np.save('{}/kge_result_basin_{}.npy'.format(self.out_dir, self.basin_num), self.kge_vals)
             np.save('{}/{}_parameters_basin_{}.npy'.format(self.out_dir, self.par_names(), self.basin_num), self.all_pars)
+            if self.velocity_bounds is not None:
+                np.save('{}/velocity_scale_basin_{}.npy'.format(self.out_dir, self.basin_num), self.velocity_scale)
 
 
 def objective_kge(pars, pet, precip, tmin, n_months, runoff_spinup, obs_unit, bsn_areas, bsn_robs, device=0):
@@ -266,7 +301,18 @@ def expand_str_range(str_ranges):
     return out
 
 
-def process_basin(basin_num, settings, data, pet, router_function=None, um=None, ndays=None, dt=10800):
+def settings_velocity_bounds(settings, velocity_bounds=None):
+    """The velocity bounds of a run: the keyword if given, else ``settings.velocity_scale_bounds`` (default 0.25, 4) when
+    ``settings.calibrate_velocity`` is on, else None."""
+    if velocity_bounds is not None:
+        return check_bounds(velocity_bounds, 'velocity_bounds')
+    if getattr(settings, 'calibrate_velocity', 0):
+        return check_bounds(getattr(settings, 'velocity_scale_bounds', None) or DEFAULT_BOUNDS)
+    return None
+
+
+def process_basin(basin_num, settings, data, pet, router_function=None, um=None, ndays=None, dt=10800,
+                  velocity_bounds=None):
     flow = None
     if settings.set_calibrate == 1:
         flow = flow_tables(settings, data, pet, [basin_num], um, ndays, dt)
@@ -274,7 +320,8 @@ def process_basin(basin_num, settings, data, pet, router_function=None, um=None,
                     basin_ids=data.basin_ids, basin_areas=data.area, precip=data.precip, pet=pet,
                     obs=getattr(data, 'cal_obs', None), tmin=data.tmin, n_months=settings.nmonths,
                     runoff_spinup=settings.runoff_spinup, router_func=router_function, out_dir=settings.calib_out_dir,
-                    device=getattr(settings, 'device', 0), flow=flow)
+                    device=getattr(settings, 'device', 0), flow=flow,
+                    velocity_bounds=settings_velocity_bounds(settings, velocity_bounds))
     cal.calibrate_basin()
     return cal
 
@@ -323,21 +370,22 @@ def gather_results(local, owner, group, root=0):
     return table
 
 
-def _make_calibrate(b, settings, data, pet, flow=None):
+def _make_calibrate(b, settings, data, pet, flow=None, velocity_bounds=None):
     return Calibrate(basin_num=b, set_calibrate=settings.set_calibrate, obs_unit=settings.obs_unit,
                      basin_ids=data.basin_ids, basin_areas=data.area, precip=data.precip, pet=pet,
                      obs=getattr(data, 'cal_obs', None), tmin=data.tmin, n_months=settings.nmonths,
                      runoff_spinup=settings.runoff_spinup, out_dir=settings.calib_out_dir, device=getattr(settings, 'device', 0),
-                     flow=None if flow is None else flow.subset([b]))
+                     flow=None if flow is None else flow.subset([b]), velocity_bounds=velocity_bounds)
 
 
-def _calibrate_local(mine, settings, data, pet, seed, popsize, nmembers, flow=None):
+def _calibrate_local(mine, settings, data, pet, seed, popsize, nmembers, flow=None, velocity_bounds=None):
     """This rank's share: rows [len(mine), npar + 3] = (parameters, ED, nfev, nit) and {basin: Calibrate}.
-    ``flow`` (set_calibrate = 1): the closure tables of at least these basins."""
-    npar = 5 if data.tmin is not None else 4
+    ``flow`` (set_calibrate = 1): the closure tables of at least these basins.  With ``velocity_bounds`` the parameters
+    end in the velocity scale and a row is one column longer."""
+    npar = (5 if data.tmin is not None else 4) + (1 if velocity_bounds is not None else 0)
     if not mine:
         return np.zeros((0, npar + 3)), {}
-    cals = [_make_calibrate(b, settings, data, pet, flow) for b in mine]
+    cals = [_make_calibrate(b, settings, data, pet, flow, velocity_bounds) for b in mine]
     bset = BasinSet(cals, settings.nmonths, settings.runoff_spinup, settings.obs_unit,
                     flow=None if flow is None else flow.subset(mine))
     try:
@@ -348,7 +396,7 @@ def _calibrate_local(mine, settings, data, pet, seed, popsize, nmembers, flow=No
 
 
 def calibrate_all(settings, data, pet, router_function=None, seed=None, popsize=15, nmembers=None, group=None, um=None,
-                  ndays=None, dt=10800):
+                  ndays=None, dt=10800, velocity_bounds=None):
     """Calibrate every requested basin (:256-262).
 
     All basins search in lock-step on the device (differential_evolution_device).  ``group`` = the job's process group
@@ -360,6 +408,11 @@ def calibrate_all(settings, data, pet, router_function=None, seed=None, popsize=
     With ``data.gauges`` (gauge_tables.Gauges) the basins are scored at their stream gauges (union closures; dealt by
     union-closure cells x (nmonths + routing_spinup)) and rank 0 also writes ``gauge_kge.csv`` to ``calib_out_dir``: per
     gauge its id, basin, cell (1-based), months used and KGE at the basin's best parameters.
+    ``velocity_bounds`` = (lo, hi) (or ``settings.calibrate_velocity`` with ``settings.velocity_scale_bounds``;
+    set_calibrate = 1 only): the basins' velocity scales are calibrated too.  The returned parameters then end in v, each
+    basin also gets ``velocity_scale_basin_N.npy``, and rank 0 writes ``velocity_scale.csv`` to ``calib_out_dir``: one row
+    for every basin of the grid, the calibrated basins with v times the scale the run had loaded (``data.velocity_scale``,
+    else 1) and every other basin with its loaded scale, so that the file is the next run's ``[[mrtm]] velocity_scale``.
     """
     if settings.set_calibrate not in (0, 1):
         raise ValueError('set_calibrate must be 0 or 1')
@@ -374,12 +427,16 @@ def calibrate_all(settings, data, pet, router_function=None, seed=None, popsize=
     if n_ranks > 1 and seed is None:
         raise ValueError('a multi-rank calibration needs the same explicit seed on every rank')
     st = time.time()
-    npar = 5 if data.tmin is not None else 4
+    vb = settings_velocity_bounds(settings, velocity_bounds)
+    if vb is not None and settings.set_calibrate != 1:
+        raise ValueError('velocity bounds need set_calibrate = 1: the velocity scale acts on the routing')
+    nabcd = 5 if data.tmin is not None else 4
+    npar = nabcd + (1 if vb is not None else 0)                  # the search's parameters: v last
     if settings.set_calibrate == 1:
         flow = flow_tables(settings, data, pet, basins, um, ndays, dt)
         owner = assign_basins(flow.weights, n_ranks)
         mine = [b for b, r in zip(basins, owner) if r == rank]
-        local, cals = _calibrate_local(mine, settings, data, pet, seed, popsize, nmembers, flow=flow)
+        local, cals = _calibrate_local(mine, settings, data, pet, seed, popsize, nmembers, flow=flow, velocity_bounds=vb)
     else:
         flow = None
         owner = assign_basins(sizes * settings.nmonths, n_ranks)
@@ -392,19 +449,23 @@ def calibrate_all(settings, data, pet, router_function=None, seed=None, popsize=
         len(basins), n_ranks, time.time() - st, int(table[:, npar + 1].sum())))
     results = {}
     for b, row in zip(basins, table):
-        c = cals[b] if b in cals else _make_calibrate(b, settings, data, pet, flow)
+        c = cals[b] if b in cals else _make_calibrate(b, settings, data, pet, flow, vb)
         c._store(row[:npar], row[npar], int(row[npar + 1]))
         results[b] = (row[:npar].copy(), 1 - row[npar])
     if getattr(flow, 'gauge_form', False) and settings.calib_out_dir is not None:
         write_gauge_kge(os.path.join(settings.calib_out_dir, 'gauge_kge.csv'), flow,
-                        gauge_kge(basins, table[:, :npar], settings, data, pet, flow))
+                        gauge_kge(basins, table[:, :npar], settings, data, pet, flow, velocity_bounds=vb))
+    if vb is not None and settings.calib_out_dir is not None:
+        n_basins = int(getattr(settings, 'n_basins', 0) or basin_ids.max())
+        write_velocity_scale(os.path.join(settings.calib_out_dir, 'velocity_scale.csv'),
+                             combined_scales(getattr(data, 'velocity_scale', None), basins, table[:, nabcd], n_basins))
     return results
 
 
-def gauge_kge(basins, best, settings, data, pet, flow):
-    """KGE of every gauge of ``flow`` (GaugeTables of ``basins``) at its basin's parameters ``best`` [nbasins, npar]:
-    one evaluation of one member per basin."""
-    cals = [_make_calibrate(b, settings, data, pet, flow) for b in basins]
+def gauge_kge(basins, best, settings, data, pet, flow, velocity_bounds=None):
+    """KGE of every gauge of ``flow`` (GaugeTables of ``basins``) at its basin's parameters ``best`` [nbasins, npar]
+    (with ``velocity_bounds``: [nbasins, npar + 1], the velocity scale included): one evaluation of one member per basin."""
+    cals = [_make_calibrate(b, settings, data, pet, flow, velocity_bounds) for b in basins]
     bset = BasinSet(cals, settings.nmonths, settings.runoff_spinup, settings.obs_unit, flow=flow.subset(basins))
     try:
         _, edg = bset.evaluate(np.asarray(best)[:, None, :], want_gauges=True)

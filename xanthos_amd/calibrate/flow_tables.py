@@ -62,7 +62,8 @@ class FlowTables:
 
     Arrays (as the C-ABI's xh_calib_flow_desc takes them): closure_ptr [nb + 1]; row_ptr [ncl + 1], cols [nnz] (closure
     local), sign [nnz]; basin_col [ncl] (column of the basin's own cell list, -1 outside the basin); outlet_rank [ncl];
-    tauinv, area, s0 [ncl]; ndays [nmonths]; plus per basin the closure and outlets as global cell indices and the
+    tauinv, area, s0 [ncl]; velocity, length [ncl] (ChV and L, tauinv == velocity / length in bits: what the velocity
+    form scales, xh_calib_velocity_desc); ndays [nmonths]; plus per basin the closure and outlets as global cell indices and the
     dealing weight closure cells x (nmonths + routing_spinup)."""
 
     def __init__(self, um, basin_ids, basins, flow_dist, velocity, area, chs_prev, ndays, nmonths, routing_spinup,
@@ -116,9 +117,16 @@ class FlowTables:
         self.basin_col = np.ascontiguousarray(cat(bcol), dtype=np.int32)
         self.outlet_rank = np.ascontiguousarray(cat(orank), dtype=np.int32)
         self.tauinv = np.ascontiguousarray(velocity[allc] / flow_dist[allc])           # ChV / L (mrtm.py:37)
+        self.velocity = np.ascontiguousarray(velocity[allc])
+        self.length = np.ascontiguousarray(flow_dist[allc])
         self.area = np.ascontiguousarray(area[allc])
         self.s0 = np.ascontiguousarray(s0[allc])
         self.weights = np.array([c.size for c in self.closures], dtype=np.int64) * (self.nmonths + self.routing_spinup)
+
+    @property
+    def foreign(self):
+        """[ncl] bool: closure rows outside their basin, which a velocity scale of the basin leaves alone."""
+        return self.basin_col < 0
 
     def part(self, i):
         """The tables of the i-th basin alone."""
@@ -131,7 +139,7 @@ class FlowTables:
         t.closure_ptr = np.array([0, c1 - c0], dtype=np.int64)
         t.row_ptr = np.ascontiguousarray(self.row_ptr[c0:c1 + 1] - e0)
         t.cols, t.sign = self.cols[e0:e1].copy(), self.sign[e0:e1].copy()
-        for name in ('basin_col', 'outlet_rank', 'tauinv', 'area', 's0'):
+        for name in ('basin_col', 'outlet_rank', 'tauinv', 'velocity', 'length', 'area', 's0'):
             setattr(t, name, np.ascontiguousarray(getattr(self, name)[c0:c1]))
         t.weights = self.weights[i:i + 1].copy()
         return t
@@ -147,7 +155,7 @@ class FlowTables:
         t.closure_ptr = np.concatenate([[0], np.cumsum([c.size for c in t.closures])]).astype(np.int64)
         off = np.cumsum([0] + [p.row_ptr[-1] for p in parts[:-1]])
         t.row_ptr = np.concatenate([[0]] + [p.row_ptr[1:] + o for p, o in zip(parts, off)]).astype(np.int64)
-        for name in ('cols', 'sign', 'basin_col', 'outlet_rank', 'tauinv', 'area', 's0', 'weights'):
+        for name in ('cols', 'sign', 'basin_col', 'outlet_rank', 'tauinv', 'velocity', 'length', 'area', 's0', 'weights'):
             setattr(t, name, np.ascontiguousarray(np.concatenate([getattr(p, name) for p in parts])))
         return t
 

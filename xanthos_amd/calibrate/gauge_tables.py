@@ -78,12 +78,13 @@ class GaugeTables:
 
     Arrays (as the C-ABI's xh_calib_gauge_desc takes them): closure_ptr [nb + 1]; row_ptr [ncl + 1], cols [nnz] (closure
     local), sign [nnz]; basin_col [ncl] (column of the basin's own cell list -- all of the basin's cells -- or -1 outside
-    the basin); tauinv, area, s0 [ncl]; ndays [nmonths]; gauge_ptr [nb + 1], gauge_row [ng], gauge_weight [ng]; plus
+    the basin); tauinv, area, s0 [ncl]; velocity, length [ncl] (ChV and L, tauinv == velocity / length in bits: what the
+    velocity form scales); ndays [nmonths]; gauge_ptr [nb + 1], gauge_row [ng], gauge_weight [ng]; plus
     gauge_id, gauge_cell, obs [ng, nmonths], per basin the closure as global cell indices and the dealing weight
     union-closure cells x (nmonths + routing_spinup)."""
 
     gauge_form = True
-    _ROW_ARRAYS = ('basin_col', 'tauinv', 'area', 's0')
+    _ROW_ARRAYS = ('basin_col', 'tauinv', 'velocity', 'length', 'area', 's0')
     _GAUGE_ARRAYS = ('gauge_id', 'gauge_cell', 'gauge_weight', 'gauge_row', 'obs')
 
     def __init__(self, um, basin_ids, basins, gauges, flow_dist, velocity, area, chs_prev, ndays, nmonths,
@@ -152,6 +153,8 @@ class GaugeTables:
         self.sign = np.ascontiguousarray(cat(sgn), dtype=np.int8)
         self.basin_col = np.ascontiguousarray(cat(bcol), dtype=np.int32)
         self.tauinv = np.ascontiguousarray(velocity[allc] / flow_dist[allc])           # ChV / L (mrtm.py:37)
+        self.velocity = np.ascontiguousarray(velocity[allc])
+        self.length = np.ascontiguousarray(flow_dist[allc])
         self.area = np.ascontiguousarray(area[allc])
         self.s0 = np.ascontiguousarray(s0[allc])
         self.gauge_ptr = np.asarray(gptr, dtype=np.int64)
@@ -161,6 +164,11 @@ class GaugeTables:
         self.gauge_row = np.ascontiguousarray(cat(grow), dtype=np.int32)
         self.obs = np.ascontiguousarray(cat(gobs), dtype=np.float64)
         self.weights = np.array([c.size for c in self.closures], dtype=np.int64) * (self.nmonths + self.routing_spinup)
+
+    @property
+    def foreign(self):
+        """[ncl] bool: closure rows outside their basin, which a velocity scale of the basin leaves alone."""
+        return self.basin_col < 0
 
     @property
     def gauge_basin(self):

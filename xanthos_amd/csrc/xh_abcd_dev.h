@@ -45,10 +45,12 @@ __host__ __device__ __forceinline__ double quot(double x, double d, double inv_d
     return __builtin_fma(__builtin_fma(-d, q, x), inv_d, q);
 }
 
-// Parameters of one calibration member: row `row` of pars [*, npar] = (a, b, c, d[, m]), b in the reference's units
-// (x 1000, abcd.py:48).  The runoff and the streamflow objectives both map a member this way.
-__device__ __forceinline__ AbcdPar calib_par(const double *__restrict__ pars, int npar, int64_t row) {
-    const double *p = pars + row * npar;
+// Parameters of one calibration member: row `row` of pars [*, pstride] = (a, b, c, d[, m], ...), b in the reference's
+// units (x 1000, abcd.py:48).  npar = 4 or 5 counts the ABCD genes (5 = with snow); pstride >= npar is the row length: a
+// row may carry further genes behind them (the velocity scale of the streamflow objective), which are not read here.
+// The runoff and the streamflow objectives both map a member this way.
+__device__ __forceinline__ AbcdPar calib_par(const double *__restrict__ pars, int pstride, int npar, int64_t row) {
+    const double *p = pars + row * pstride;
     AbcdPar P;
     const double a = p[0];
     P.b = p[1] * 1000.0;

@@ -16,6 +16,9 @@ struct xh_calib_basin {
 // A set of basins laid out for the objective kernels: tables and work arrays in ONE device allocation.
 struct xh_calib_problem {
     int nbasins = 0, nmonths = 0, spinup = 0, nmembers = 0, npar = 0;
+    // length of a member's row of d_pars: npar (the ABCD genes: 4, or 5 with snow) unless the streamflow objective
+    // calibrates the velocity scale, whose gene follows them (npar + 1); xh_calib_problem_place sets npar
+    int pstride = 0;
     size_t nchunks = 0;
     // 0: lanes <-> cells, 4 members per thread (any population).  1: lanes <-> members, 16 cells per wave, forcing as
     // scalar loads, no cross-lane sums (populations that fill waves of 64 members: 100 instead of 145 wave-instructions
@@ -63,9 +66,11 @@ int xh_calib_kge_enqueue(xh_ctx *ctx, const xh_calib_problem &P, const int *d_ac
 
 // Streamflow objective (xh_calib_flow.hip).  create: validates and uploads the closure tables of `desc` for a problem of
 // nbasins basins (h_ncell basin cells each) and nmembers members; enqueue: spin-up, the fused ABCD + routing march and
-// ED into d_ed (d_active as for xh_calib_enqueue).
+// ED into d_ed (d_active as for xh_calib_enqueue).  velocity != NULL (either form): the velocity form, whose members' rows
+// of d_pars are [npar ABCD genes, v]; the owner of the problem sets P.pstride = npar + 1.
 int xh_calib_flow_create(xh_ctx *ctx, int32_t nbasins, const int64_t *h_ncell, int32_t nmonths, int32_t nmembers,
-                         const xh_calib_flow_desc *desc, xh_calib_flow **out);
+                         const xh_calib_flow_desc *desc, xh_calib_flow **out,
+                         const xh_calib_velocity_desc *velocity = nullptr);
 void xh_calib_flow_destroy(xh_calib_flow *f);
 int xh_calib_flow_enqueue(xh_ctx *ctx, const xh_calib_problem &P, const double *d_pars, const int *d_active, double *d_ed);
 
@@ -73,7 +78,8 @@ int xh_calib_flow_enqueue(xh_ctx *ctx, const xh_calib_problem &P, const double *
 // xh_calib_flow_enqueue.  score: masked ED of every (gauge, member) into P.d_ed_gauge, then the basin's weighted mean in
 // gauge order into d_ed.
 int xh_calib_gauge_create(xh_ctx *ctx, int32_t nbasins, const int64_t *h_ncell, int32_t nmonths, int32_t nmembers,
-                          const xh_calib_gauge_desc *desc, xh_calib_flow **out);
+                          const xh_calib_gauge_desc *desc, xh_calib_flow **out,
+                          const xh_calib_velocity_desc *velocity = nullptr);
 int xh_calib_gauge_score_enqueue(xh_ctx *ctx, const xh_calib_problem &P, const int *d_active, int ngauge,
                                  const int *d_gauge_basin, const int *d_gauge_ptr, const double *d_weight,
                                  const double *d_series, double *d_ed);

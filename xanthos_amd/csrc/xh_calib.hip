@@ -62,7 +62,7 @@ template <bool SPINUP>
 __global__ void __launch_bounds__(64) k_calib_march(const CalibBasin *__restrict__ basins,
                                                     const int *__restrict__ chunk_basin,
                                                     const int *__restrict__ active, int nsteps, int nmembers,
-                                                    int npar, const double *__restrict__ pars,
+                                                    int npar, int pstride, const double *__restrict__ pars,
                                                     const double *__restrict__ sm0, const double *__restrict__ gw0,
                                                     double *__restrict__ dec_sum,    // [chunk][member][6]
                                                     int *__restrict__ dec_cnt,       // [chunk][member][6]
@@ -87,7 +87,7 @@ __global__ void __launch_bounds__(64) k_calib_march(const CalibBasin *__restrict
 #pragma unroll
     for (int j = 0; j < MB; ++j) {
         const int mem = min(mb0 + j, nmembers - 1);
-        P[j] = calib_par(pars, npar, b * nmembers + mem);
+        P[j] = calib_par(pars, pstride, npar, b * nmembers + mem);
         s[j].snowpack = 0.0;
         s[j].sm = SPINUP ? 100.0 : sm0[b * nmembers + mem];
         s[j].gw = SPINUP ? 500.0 : gw0[b * nmembers + mem];
@@ -318,7 +318,7 @@ template <bool SPINUP>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) k_calib_march_m(const xh_calib_basin *__restrict__ basins,
                                                       const int *__restrict__ chunk_basin,
                                                       const int *__restrict__ active, int nsteps, int nmembers, int npar,
-                                                      const double *__restrict__ pars, const double *__restrict__ sm0,
+                                                      int pstride, const double *__restrict__ pars, const double *__restrict__ sm0,
                                                       const double *__restrict__ gw0,
                                                       double *__restrict__ dec_sum,    // [chunk][6][member]
                                                       int *__restrict__ dec_cnt,       // [chunk][6][member]
@@ -334,7 +334,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3)))
     const bool ok = mem_raw < nmembers;
     const int mem = ok ? mem_raw : nmembers - 1;
     const bool snow_on = B.tn != nullptr;
-    const AbcdPar P = calib_par(pars, npar, b * nmembers + mem);
+    const AbcdPar P = calib_par(pars, pstride, npar, b * nmembers + mem);
     const XhExpConsts K = xh_exp_consts();
     AbcdState s[CM];
 #pragma unroll
@@ -578,6 +578,7 @@ int xh_calib_problem_place(xh_ctx *ctx, xh_calib_problem &P, int32_t nmonths, in
     P.spinup = spinup;
     P.nmembers = nmembers;
     P.npar = npar;
+    P.pstride = npar;
     P.nchunks = nchunks;
     P.member_lanes = member_lanes;
     P.split_done = false;
@@ -635,7 +636,7 @@ static int spinup_m(xh_ctx *ctx, const xh_calib_problem &P, const double *d_pars
         P.split_done = true;
     }
     int rc = xh_launch(ctx, nullptr, st, k_calib_march_m<true>, grid, block, 0, P.d_basins, P.d_chunk_basin, d_active,
-                       P.spinup, P.nmembers, P.npar, d_pars, (const double *)nullptr, (const double *)nullptr, P.d_dec,
+                       P.spinup, P.nmembers, P.npar, P.pstride, d_pars, (const double *)nullptr, (const double *)nullptr, P.d_dec,
                        P.d_cnt, (double *)nullptr);
     if (!rc)
         rc = xh_launch(ctx, nullptr, st, k_calib_init_m, xh_grid(ctx, nbm, 64), 64, 0, P.d_basins, d_active, P.nbasins,
@@ -649,7 +650,7 @@ static int spinup_c(xh_ctx *ctx, const xh_calib_problem &P, const double *d_pars
     const dim3 grid((unsigned)P.nchunks, (unsigned)((P.nmembers + MB - 1) / MB)), block(64);
     hipStream_t st = ctx->stream;
     int rc = xh_launch(ctx, nullptr, st, k_calib_march<true>, grid, block, 0, P.d_basins, P.d_chunk_basin, d_active,
-                       P.spinup, P.nmembers, P.npar, d_pars, (const double *)nullptr, (const double *)nullptr, P.d_dec,
+                       P.spinup, P.nmembers, P.npar, P.pstride, d_pars, (const double *)nullptr, (const double *)nullptr, P.d_dec,
                        P.d_cnt, (double *)nullptr);
     if (!rc)
         rc = xh_launch(ctx, nullptr, st, k_calib_init, xh_grid(ctx, nbm, 64), 64, 0, P.d_basins, d_active, P.nbasins,
@@ -687,7 +688,7 @@ static int calib_enqueue_m(xh_ctx *ctx, const xh_calib_problem &P, const double 
         int rc = spinup_m(ctx, P, d_pars, d_active);
         if (!rc)
             rc = xh_launch(ctx, nullptr, st, k_calib_march_m<false>, grid, block, 0, P.d_basins, P.d_chunk_basin, d_active,
-                           P.nmonths, P.nmembers, P.npar, d_pars, P.d_sm0, P.d_gw0, (double *)nullptr, (int *)nullptr,
+                           P.nmonths, P.nmembers, P.npar, P.pstride, d_pars, P.d_sm0, P.d_gw0, (double *)nullptr, (int *)nullptr,
                            P.d_part);
         return rc;
     });
@@ -719,7 +720,7 @@ int xh_calib_enqueue(xh_ctx *ctx, const xh_calib_problem &P, const double *d_par
         int rc = spinup_c(ctx, P, d_pars, d_active);
         if (!rc)
             rc = xh_launch(ctx, nullptr, st, k_calib_march<false>, grid, block, 0, P.d_basins, P.d_chunk_basin, d_active,
-                           P.nmonths, P.nmembers, P.npar, d_pars, P.d_sm0, P.d_gw0, (double *)nullptr, (int *)nullptr,
+                           P.nmonths, P.nmembers, P.npar, P.pstride, d_pars, P.d_sm0, P.d_gw0, (double *)nullptr, (int *)nullptr,
                            P.d_part);
         return rc;
     });

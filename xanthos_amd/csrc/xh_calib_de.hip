@@ -264,12 +264,13 @@ void xh_calib_de_destroy(xh_calib_de *de) {
 }
 
 // flow != NULL: the streamflow objective (xh_calib_flow.hip) on the same basins; gauge != NULL: its gauge form, with
-// h_obs [ngauge, nmonths]
+// h_obs [ngauge, nmonths]; vel != NULL (with either): the velocity form, whose search has one more gene than the npar
+// ABCD genes (h_lo, h_hi [npar + 1], v last)
 static int de_create(xh_ctx *ctx, int32_t nbasins, const int64_t *h_ncell, const uint64_t *h_basin_key, int32_t nmonths,
                      int32_t spinup, int32_t nmembers, int32_t npar, const double *const *h_pet_t,
                      const double *const *h_precip_t, const double *const *h_tmin_t, const double *const *h_area,
-                     const xh_calib_flow_desc *flow, const xh_calib_gauge_desc *gauge, const double *h_obs,
-                     const double *h_lo, const double *h_hi, uint64_t seed, xh_calib_de **out) {
+                     const xh_calib_flow_desc *flow, const xh_calib_gauge_desc *gauge,
+                     const xh_calib_velocity_desc *vel, const double *h_obs, const double *h_lo, const double *h_hi, uint64_t seed, xh_calib_de **out) {
     if (!ctx) return XH_ERR_ARG;
     XH_REQUIRE(ctx, out && h_obs && h_lo && h_hi, "xh_calib_de_create: NULL argument");
     *out = nullptr;
@@ -290,6 +291,8 @@ static int de_create(xh_ctx *ctx, int32_t nbasins, const int64_t *h_ncell, const
     xh_calib_de *de = new xh_calib_de();
     de->ctx = ctx;
     de->n = nmembers;
+    const int32_t nabcd = npar;                                      // the objective's ABCD genes
+    if (vel) npar += 1;                                              // the search's genes from here on
     de->d = npar;
     de->nb = nbasins;
     de->seed = seed;
@@ -302,10 +305,11 @@ static int de_create(xh_ctx *ctx, int32_t nbasins, const int64_t *h_ncell, const
         }                                                                                               \
     } while (0)
     DE_TRY(hipMalloc(&de->d_problem, bytes));
-    rc = xh_calib_problem_place(ctx, de->P, nmonths, spinup, nmembers, npar, basins, chunk_basin, h_obs, de->d_problem, ml,
+    rc = xh_calib_problem_place(ctx, de->P, nmonths, spinup, nmembers, nabcd, basins, chunk_basin, h_obs, de->d_problem, ml,
                                 ngauge);
-    if (!rc && flow) rc = xh_calib_flow_create(ctx, nbasins, h_ncell, nmonths, nmembers, flow, &de->P.flow);
-    if (!rc && gauge) rc = xh_calib_gauge_create(ctx, nbasins, h_ncell, nmonths, nmembers, gauge, &de->P.flow);
+    de->P.pstride = npar;
+    if (!rc && flow) rc = xh_calib_flow_create(ctx, nbasins, h_ncell, nmonths, nmembers, flow, &de->P.flow, vel);
+    if (!rc && gauge) rc = xh_calib_gauge_create(ctx, nbasins, h_ncell, nmonths, nmembers, gauge, &de->P.flow, vel);
     if (rc) {
         xh_calib_de_destroy(de);
         return rc;
@@ -348,7 +352,7 @@ int xh_calib_de_create(xh_ctx *ctx, int32_t nbasins, const int64_t *h_ncell, con
                        const double *const *h_area, const double *h_obs, const double *h_lo, const double *h_hi,
                        uint64_t seed, xh_calib_de **out) {
     return de_create(ctx, nbasins, h_ncell, h_basin_key, nmonths, spinup, nmembers, npar, h_pet_t, h_precip_t, h_tmin_t,
-                     h_area, nullptr, nullptr, h_obs, h_lo, h_hi, seed, out);
+                     h_area, nullptr, nullptr, nullptr, h_obs, h_lo, h_hi, seed, out);
 }
 
 int xh_calib_de_create_flow(xh_ctx *ctx, int32_t nbasins, const int64_t *h_ncell, const uint64_t *h_basin_key,
@@ -359,7 +363,7 @@ int xh_calib_de_create_flow(xh_ctx *ctx, int32_t nbasins, const int64_t *h_ncell
     if (!ctx) return XH_ERR_ARG;
     XH_REQUIRE(ctx, flow != nullptr, "xh_calib_de_create_flow: NULL flow tables");
     return de_create(ctx, nbasins, h_ncell, h_basin_key, nmonths, spinup, nmembers, npar, h_pet_t, h_precip_t, h_tmin_t,
-                     nullptr, flow, nullptr, h_obs, h_lo, h_hi, seed, out);
+                     nullptr, flow, nullptr, nullptr, h_obs, h_lo, h_hi, seed, out);
 }
 
 int xh_calib_de_create_gauge(xh_ctx *ctx, int32_t nbasins, const int64_t *h_ncell, const uint64_t *h_basin_key,
@@ -370,7 +374,31 @@ int xh_calib_de_create_gauge(xh_ctx *ctx, int32_t nbasins, const int64_t *h_ncel
     if (!ctx) return XH_ERR_ARG;
     XH_REQUIRE(ctx, gauge != nullptr, "xh_calib_de_create_gauge: NULL gauge tables");
     return de_create(ctx, nbasins, h_ncell, h_basin_key, nmonths, spinup, nmembers, npar, h_pet_t, h_precip_t, h_tmin_t,
-                     nullptr, nullptr, gauge, h_obs, h_lo, h_hi, seed, out);
+                     nullptr, nullptr, gauge, nullptr, h_obs, h_lo, h_hi, seed, out);
+}
+
+int xh_calib_de_create_flow_velocity(xh_ctx *ctx, int32_t nbasins, const int64_t *h_ncell, const uint64_t *h_basin_key,
+                                     int32_t nmonths, int32_t spinup, int32_t nmembers, int32_t npar,
+                                     const double *const *h_pet_t, const double *const *h_precip_t,
+                                     const double *const *h_tmin_t, const xh_calib_flow_desc *flow,
+                                     const xh_calib_velocity_desc *velocity, const double *h_obs, const double *h_lo,
+                                     const double *h_hi, uint64_t seed, xh_calib_de **out) {
+    if (!ctx) return XH_ERR_ARG;
+    XH_REQUIRE(ctx, flow && velocity, "xh_calib_de_create_flow_velocity: NULL tables");
+    return de_create(ctx, nbasins, h_ncell, h_basin_key, nmonths, spinup, nmembers, npar, h_pet_t, h_precip_t, h_tmin_t,
+                     nullptr, flow, nullptr, velocity, h_obs, h_lo, h_hi, seed, out);
+}
+
+int xh_calib_de_create_gauge_velocity(xh_ctx *ctx, int32_t nbasins, const int64_t *h_ncell, const uint64_t *h_basin_key,
+                                      int32_t nmonths, int32_t spinup, int32_t nmembers, int32_t npar,
+                                      const double *const *h_pet_t, const double *const *h_precip_t,
+                                      const double *const *h_tmin_t, const xh_calib_gauge_desc *gauge,
+                                      const xh_calib_velocity_desc *velocity, const double *h_obs, const double *h_lo,
+                                      const double *h_hi, uint64_t seed, xh_calib_de **out) {
+    if (!ctx) return XH_ERR_ARG;
+    XH_REQUIRE(ctx, gauge && velocity, "xh_calib_de_create_gauge_velocity: NULL tables");
+    return de_create(ctx, nbasins, h_ncell, h_basin_key, nmonths, spinup, nmembers, npar, h_pet_t, h_precip_t, h_tmin_t,
+                     nullptr, nullptr, gauge, velocity, h_obs, h_lo, h_hi, seed, out);
 }
 
 static int de_fill_active(xh_calib_de *de, int value) {

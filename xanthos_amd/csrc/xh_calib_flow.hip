@@ -31,6 +31,13 @@
 // share and the two barriers per month around it go.  k_calib_kge_masked then scores every (gauge, member) over the
 // months with a finite observation and k_calib_gauge_combine forms the basin's weighted mean (xh_calib.hip).
 //
+// Velocity form (xh_calib_velocity_desc, either form above): a member's row of parameters carries one more gene behind
+// the ABCD genes, the velocity scale v > 0 of its basin.  The instantiations with VEL route the basin's own cells with
+// tau^-1 = (v ChV) / L -- the product first, then the IEEE quotient, as mrtm.py:42 forms it on a scaled ChV -- and the
+// closure's foreign cells with the table's ChV / L: those belong to another basin's calibration.  v is read once per
+// (basin, member) and tau stays in the lane's registers, so nothing else of the sub-step changes.  (1.0 ChV) / L has the
+// bits of ChV / L: v = 1 returns the series of the instantiations without VEL, which are compiled as before.
+//
 // Everything is fp64 in the reference's operation order (-ffp-contract=off), summation orders are fixed, outputs are
 // written once: results are bit-identical run to run.
 #include <algorithm>
@@ -74,7 +81,8 @@ __device__ __forceinline__ double gather(const int *__restrict__ ent, int e_lo, 
 
 // GAUGE: g_orank holds, per closure row, the first gauge on that cell (index into the problem's gauges, which are sorted
 // by cell within a basin) or -1, g_grow the closure-local row of every gauge, and series is [gauge][member][month].
-template <int BT, int CPL, bool GAUGE>
+// VEL: pars rows are [npar ABCD genes, v]; g_chv, g_len [closure row] = ChV and L (else unused, NULL).
+template <int BT, int CPL, bool GAUGE, bool VEL>
 __global__ void __launch_bounds__(BT) k_calib_flow(const xh_calib_basin *__restrict__ basins,
                                                    const FlowBasin *__restrict__ fbs, const int2 *__restrict__ work,
                                                    const int *__restrict__ active, int nmonths, int rspin, double dt,
@@ -85,7 +93,8 @@ __global__ void __launch_bounds__(BT) k_calib_flow(const xh_calib_basin *__restr
                                                    const double *__restrict__ g_tau, const double *__restrict__ g_area,
                                                    const double *__restrict__ g_s0, const int *__restrict__ g_bcol,
                                                    const int *__restrict__ g_orank, const int *__restrict__ g_grow,
-                                                   double *__restrict__ series) {
+                                                   double *__restrict__ series, const double *__restrict__ g_chv,
+                                                   const double *__restrict__ g_len) {
     extern __shared__ double lds[];
     const int2 wk = work[blockIdx.x];
     const int b = wk.x;
@@ -107,7 +116,9 @@ __global__ void __launch_bounds__(BT) k_calib_flow(const xh_calib_basin *__restr
     if (t < 3) flag[t] = 0;
 
     const bool snow_on = B.tn != nullptr;
-    const AbcdPar P = calib_par(pars, npar, row);
+    const int pstride = VEL ? npar + 1 : npar;
+    const AbcdPar P = calib_par(pars, pstride, npar, row);
+    const double vscale = VEL ? pars[(int64_t)row * pstride + npar] : 1.0;
     const XhExpConsts K = xh_exp_consts();
     const double sm_init = sm0[row], gw_init = gw0[row];
     const double dtinv = 1.0 / dt;
@@ -127,6 +138,8 @@ __global__ void __launch_bounds__(BT) k_calib_flow(const xh_calib_basin *__restr
         bcol[k] = own[k] ? g_bcol[c] : -1;
         gfirst[k] = (GAUGE && own[k]) ? g_orank[c] : -1;
         tau[k] = own[k] ? g_tau[c] : 0.0;
+        if constexpr (VEL)
+            if (bcol[k] >= 0) tau[k] = (vscale * g_chv[c]) / g_len[c];           // mrtm.py:42 on the basin's scaled ChV
         S[k] = own[k] ? g_s0[c] : 0.0;
         F[k] = S[k] * tau[k];
         erl[k] = favg[k] = 0.0;
@@ -254,6 +267,7 @@ struct xh_calib_flow {
     int64_t *d_row_ptr = nullptr;
     int *d_ent = nullptr, *d_bcol = nullptr, *d_orank = nullptr, *d_ndays = nullptr, *d_nt = nullptr;
     double *d_tau = nullptr, *d_area = nullptr, *d_s0 = nullptr;
+    double *d_chv = nullptr, *d_len = nullptr;   // velocity form: ChV and L of every closure row (else NULL)
     // gauge form: d_orank holds the first gauge of each closure row; per gauge its closure-local row, basin and weight,
     // per basin its first gauge
     int ngauge = 0;                          // 0 = the outlet form
@@ -270,20 +284,23 @@ struct xh_calib_flow {
 
 namespace {
 
-template <int BT, int CPL, bool GAUGE>
+template <int BT, int CPL, bool GAUGE, bool VEL>
 int launch_form(xh_ctx *ctx, const xh_calib_problem &P, const xh_calib_flow &f, int kl, const double *d_pars,
                 const int *d_active) {
-    return xh_launch(ctx, nullptr, kl ? f.side[kl] : ctx->stream, k_calib_flow<BT, CPL, GAUGE>, dim3((unsigned)f.nwork[kl]), dim3(BT), f.lds[kl],
+    return xh_launch(ctx, nullptr, kl ? f.side[kl] : ctx->stream, k_calib_flow<BT, CPL, GAUGE, VEL>, dim3((unsigned)f.nwork[kl]), dim3(BT), f.lds[kl],
                      P.d_basins, f.d_fb, f.d_work + f.work0[kl], d_active, f.nmonths, f.rspin, f.dt, f.d_ndays, f.d_nt,
                      P.nmembers, P.npar, d_pars, P.d_sm0, P.d_gw0, f.d_row_ptr, f.d_ent, f.d_tau, f.d_area, f.d_s0,
-                     f.d_bcol, f.d_orank, f.d_grow, P.d_series);
+                     f.d_bcol, f.d_orank, f.d_grow, P.d_series, f.d_chv, f.d_len);
 }
 
 template <int BT, int CPL>
 int launch_klass(xh_ctx *ctx, const xh_calib_problem &P, const xh_calib_flow &f, int kl, const double *d_pars,
                  const int *d_active) {
-    return f.ngauge ? launch_form<BT, CPL, true>(ctx, P, f, kl, d_pars, d_active)
-                    : launch_form<BT, CPL, false>(ctx, P, f, kl, d_pars, d_active);
+    if (f.d_chv)
+        return f.ngauge ? launch_form<BT, CPL, true, true>(ctx, P, f, kl, d_pars, d_active)
+                        : launch_form<BT, CPL, false, true>(ctx, P, f, kl, d_pars, d_active);
+    return f.ngauge ? launch_form<BT, CPL, true, false>(ctx, P, f, kl, d_pars, d_active)
+                    : launch_form<BT, CPL, false, false>(ctx, P, f, kl, d_pars, d_active);
 }
 
 }  // namespace
@@ -312,13 +329,14 @@ struct GaugePart {
 };
 
 int flow_create(xh_ctx *ctx, int32_t nbasins, const int64_t *h_ncell, int32_t nmonths, int32_t nmembers,
-                const xh_calib_flow_desc *d, const GaugePart *gp, xh_calib_flow **out) {
+                const xh_calib_flow_desc *d, const GaugePart *gp, const xh_calib_velocity_desc *vd, xh_calib_flow **out) {
     XH_REQUIRE(ctx, d && out && h_ncell, "xh_calib_flow: NULL argument");
     *out = nullptr;
     XH_REQUIRE(ctx, d->h_ndays && d->h_closure_ptr && d->h_row_ptr && d->h_cols && d->h_sign && d->h_basin_col &&
                         (gp || d->h_outlet_rank) && d->h_tauinv && d->h_area && d->h_s0,
                "xh_calib_flow: NULL table");
     XH_REQUIRE(ctx, !gp || (gp->ptr && gp->row && gp->weight), "xh_calib_flow: NULL gauge table");
+    XH_REQUIRE(ctx, !vd || (vd->h_velocity && vd->h_length), "xh_calib_flow: NULL velocity table");
     const int64_t ngauge = gp ? gp->ptr[nbasins] : 0;
     XH_REQUIRE(ctx, !gp || (gp->ptr[0] == 0 && ngauge > 0 && ngauge < ((int64_t)1 << 24)), "xh_calib_flow: bad gauge_ptr");
     XH_REQUIRE(ctx, d->routing_spinup >= 0 && d->routing_spinup <= nmonths,
@@ -362,6 +380,11 @@ int flow_create(xh_ctx *ctx, int32_t nbasins, const int64_t *h_ncell, int32_t nm
                            "xh_calib_flow: basin %d: bad entry %lld", b, (long long)e);
                 ent[e] = d->h_sign[e] > 0 ? col : ~col;
             }
+            // (velocity form: the kernel divides by L and the scaled cells' tau^-1 must be what h_tauinv says at v = 1)
+            XH_REQUIRE(ctx, !vd || (vd->h_length[c] > 0.0 && std::isfinite(vd->h_length[c]) && vd->h_velocity[c] >= 0.0 &&
+                                    std::isfinite(vd->h_velocity[c]) && vd->h_velocity[c] / vd->h_length[c] == d->h_tauinv[c]),
+                       "xh_calib_flow: basin %d: row %lld: tauinv must be velocity / length, both finite, length positive", b,
+                       (long long)(c - c0));
             const int bc = d->h_basin_col[c];
             XH_REQUIRE(ctx, bc >= -1 && bc < h_ncell[b], "xh_calib_flow: basin %d: bad basin column %d", b, bc);
             nbc += bc >= 0;
@@ -436,7 +459,8 @@ int flow_create(xh_ctx *ctx, int32_t nbasins, const int64_t *h_ncell, int32_t nm
                  o_s0 = al(o_area + 8 * (size_t)ncl), o_work = al(o_s0 + 8 * (size_t)ncl),
                  o_grow = al(o_work + sizeof(int2) * std::max<size_t>(all.size(), 1)), o_gb = al(o_grow + 4 * (size_t)ngauge),
                  o_gp = al(o_gb + 4 * (size_t)ngauge), o_gw = al(o_gp + 4 * gptr.size()),
-                 total = al(o_gw + 8 * (size_t)ngauge);
+                 o_chv = al(o_gw + 8 * (size_t)ngauge), o_len = al(o_chv + (vd ? 8 * (size_t)ncl : 0)),
+                 total = al(o_len + (vd ? 8 * (size_t)ncl : 0));
     hipError_t e = hipMalloc(&f->d_buf, total);
     if (e != hipSuccess) {
         xh_calib_flow_destroy(f);
@@ -458,6 +482,10 @@ int flow_create(xh_ctx *ctx, int32_t nbasins, const int64_t *h_ncell, int32_t nm
     f->d_gbasin = reinterpret_cast<int *>(base + o_gb);
     f->d_gptr = reinterpret_cast<int *>(base + o_gp);
     f->d_gw = reinterpret_cast<double *>(base + o_gw);
+    if (vd) {
+        f->d_chv = reinterpret_cast<double *>(base + o_chv);
+        f->d_len = reinterpret_cast<double *>(base + o_len);
+    }
     const struct {
         void *dst;
         const void *src;
@@ -469,7 +497,9 @@ int flow_create(xh_ctx *ctx, int32_t nbasins, const int64_t *h_ncell, int32_t nm
               {f->d_area, d->h_area, 8 * (size_t)ncl},           {f->d_s0, d->h_s0, 8 * (size_t)ncl},
               {f->d_work, all.data(), sizeof(int2) * all.size()},
               {f->d_grow, gp ? gp->row : nullptr, 4 * (size_t)ngauge},   {f->d_gbasin, gbasin.data(), 4 * (size_t)ngauge},
-              {f->d_gptr, gptr.data(), 4 * gptr.size()},         {f->d_gw, gp ? gp->weight : nullptr, 8 * (size_t)ngauge}};
+              {f->d_gptr, gptr.data(), 4 * gptr.size()},         {f->d_gw, gp ? gp->weight : nullptr, 8 * (size_t)ngauge},
+              {f->d_chv, vd ? vd->h_velocity : nullptr, vd ? 8 * (size_t)ncl : 0},
+              {f->d_len, vd ? vd->h_length : nullptr, vd ? 8 * (size_t)ncl : 0}};
     for (const auto &u : up) {
         if (!u.n) continue;
         e = hipMemcpyAsync(u.dst, u.src, u.n, hipMemcpyHostToDevice, ctx->stream);
@@ -500,17 +530,17 @@ int flow_create(xh_ctx *ctx, int32_t nbasins, const int64_t *h_ncell, int32_t nm
 }  // namespace
 
 int xh_calib_flow_create(xh_ctx *ctx, int32_t nbasins, const int64_t *h_ncell, int32_t nmonths, int32_t nmembers,
-                         const xh_calib_flow_desc *d, xh_calib_flow **out) {
-    return flow_create(ctx, nbasins, h_ncell, nmonths, nmembers, d, nullptr, out);
+                         const xh_calib_flow_desc *d, xh_calib_flow **out, const xh_calib_velocity_desc *vel) {
+    return flow_create(ctx, nbasins, h_ncell, nmonths, nmembers, d, nullptr, vel, out);
 }
 
 int xh_calib_gauge_create(xh_ctx *ctx, int32_t nbasins, const int64_t *h_ncell, int32_t nmonths, int32_t nmembers,
-                          const xh_calib_gauge_desc *g, xh_calib_flow **out) {
+                          const xh_calib_gauge_desc *g, xh_calib_flow **out, const xh_calib_velocity_desc *vel) {
     XH_REQUIRE(ctx, g && out, "xh_calib_gauge: NULL argument");
     const xh_calib_flow_desc d = {g->routing_spinup, g->dt,        g->h_ndays, g->h_closure_ptr, g->h_row_ptr, g->h_cols,
                                   g->h_sign,         g->h_basin_col, nullptr,    g->h_tauinv,      g->h_area,    g->h_s0};
     const GaugePart gp = {g->h_gauge_ptr, g->h_gauge_row, g->h_gauge_weight};
-    return flow_create(ctx, nbasins, h_ncell, nmonths, nmembers, &d, &gp, out);
+    return flow_create(ctx, nbasins, h_ncell, nmonths, nmembers, &d, &gp, vel, out);
 }
 
 int xh_calib_flow_enqueue(xh_ctx *ctx, const xh_calib_problem &P, const double *d_pars, const int *d_active, double *d_ed) {
@@ -548,8 +578,9 @@ int xh_calib_flow_enqueue(xh_ctx *ctx, const xh_calib_problem &P, const double *
 static int objective_multi(xh_ctx *ctx, const char *who, int32_t nbasins, const int64_t *h_ncell, int32_t nmonths,
                            int32_t spinup, int32_t nmembers, int32_t npar, const double *h_pars,
                            const double *const *h_pet_t, const double *const *h_precip_t, const double *const *h_tmin_t,
-                           const xh_calib_flow_desc *flow, const xh_calib_gauge_desc *gauge, const double *h_obs,
-                           double *h_ed, double *h_ed_gauge, double *h_series) {
+                           const xh_calib_flow_desc *flow, const xh_calib_gauge_desc *gauge,
+                           const xh_calib_velocity_desc *vel, const double *h_obs, double *h_ed, double *h_ed_gauge,
+                           double *h_series) {
     if (!ctx) return XH_ERR_ARG;
     XH_REQUIRE(ctx, h_pars && h_obs && h_ed && (flow || gauge), "%s: NULL argument", who);
     XH_REQUIRE(ctx, !gauge || (gauge->h_gauge_ptr && nbasins > 0), "%s: NULL gauge table", who);
@@ -564,23 +595,25 @@ static int objective_multi(xh_ctx *ctx, const char *who, int32_t nbasins, const 
                                    nullptr, basins, chunk_basin, &bytes, &ml, ngauge);
     if (rc) return rc;
     xh_calib_flow *f = nullptr;
-    rc = gauge ? xh_calib_gauge_create(ctx, nbasins, h_ncell, nmonths, nmembers, gauge, &f)
-               : xh_calib_flow_create(ctx, nbasins, h_ncell, nmonths, nmembers, flow, &f);
+    rc = gauge ? xh_calib_gauge_create(ctx, nbasins, h_ncell, nmonths, nmembers, gauge, &f, vel)
+               : xh_calib_flow_create(ctx, nbasins, h_ncell, nmonths, nmembers, flow, &f, vel);
     if (rc) return rc;
     const size_t nbm = (size_t)nbasins * nmembers, nsm = (size_t)(gauge ? ngauge : nbasins) * nmembers;
-    const size_t io_bytes = ((nbm * npar + nbm) * sizeof(double) + 255) & ~size_t(255);
+    const size_t pstride = (size_t)npar + (vel ? 1 : 0);             // h_pars rows: the ABCD genes, then v
+    const size_t io_bytes = ((nbm * pstride + nbm) * sizeof(double) + 255) & ~size_t(255);
     void *buf = nullptr;
     rc = xh_scratch(ctx, 1, io_bytes + bytes, &buf);
     xh_calib_problem P;
     if (!rc) {
         double *d_pars = static_cast<double *>(buf);
-        double *d_ed = d_pars + nbm * npar;
-        const hipError_t e = hipMemcpyAsync(d_pars, h_pars, sizeof(double) * nbm * npar, hipMemcpyHostToDevice, ctx->stream);
+        double *d_ed = d_pars + nbm * pstride;
+        const hipError_t e = hipMemcpyAsync(d_pars, h_pars, sizeof(double) * nbm * pstride, hipMemcpyHostToDevice, ctx->stream);
         rc = e == hipSuccess ? XH_OK : xh_fail(ctx, XH_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
         if (!rc)
             rc = xh_calib_problem_place(ctx, P, nmonths, spinup, nmembers, npar, basins, chunk_basin, h_obs,
                                         static_cast<char *>(buf) + io_bytes, ml, ngauge);
         P.flow = f;
+        P.pstride = (int)pstride;
         if (!rc) rc = xh_calib_enqueue(ctx, P, d_pars, nullptr, d_ed);
         if (!rc) {
             hipError_t e2 = hipMemcpyAsync(h_ed, d_ed, sizeof(double) * nbm, hipMemcpyDeviceToHost, ctx->stream);
@@ -604,7 +637,7 @@ extern "C" int xh_calib_flow_objective_multi(xh_ctx *ctx, int32_t nbasins, const
                                              const double *const *h_tmin_t, const xh_calib_flow_desc *flow,
                                              const double *h_obs, double *h_ed, double *h_series) {
     return objective_multi(ctx, "xh_calib_flow_objective_multi", nbasins, h_ncell, nmonths, spinup, nmembers, npar, h_pars,
-                           h_pet_t, h_precip_t, h_tmin_t, flow, nullptr, h_obs, h_ed, nullptr, h_series);
+                           h_pet_t, h_precip_t, h_tmin_t, flow, nullptr, nullptr, h_obs, h_ed, nullptr, h_series);
 }
 
 extern "C" int xh_calib_gauge_objective_multi(xh_ctx *ctx, int32_t nbasins, const int64_t *h_ncell, int32_t nmonths,
@@ -613,5 +646,29 @@ extern "C" int xh_calib_gauge_objective_multi(xh_ctx *ctx, int32_t nbasins, cons
                                               const double *const *h_tmin_t, const xh_calib_gauge_desc *gauge,
                                               const double *h_obs, double *h_ed, double *h_ed_gauge, double *h_series) {
     return objective_multi(ctx, "xh_calib_gauge_objective_multi", nbasins, h_ncell, nmonths, spinup, nmembers, npar, h_pars,
-                           h_pet_t, h_precip_t, h_tmin_t, nullptr, gauge, h_obs, h_ed, h_ed_gauge, h_series);
+                           h_pet_t, h_precip_t, h_tmin_t, nullptr, gauge, nullptr, h_obs, h_ed, h_ed_gauge, h_series);
+}
+
+extern "C" int xh_calib_flow_velocity_objective_multi(xh_ctx *ctx, int32_t nbasins, const int64_t *h_ncell, int32_t nmonths,
+                                                      int32_t spinup, int32_t nmembers, int32_t npar, const double *h_pars,
+                                                      const double *const *h_pet_t, const double *const *h_precip_t,
+                                                      const double *const *h_tmin_t, const xh_calib_flow_desc *flow,
+                                                      const xh_calib_velocity_desc *velocity, const double *h_obs,
+                                                      double *h_ed, double *h_series) {
+    if (!ctx) return XH_ERR_ARG;
+    XH_REQUIRE(ctx, flow && velocity, "xh_calib_flow_velocity_objective_multi: NULL tables");
+    return objective_multi(ctx, "xh_calib_flow_velocity_objective_multi", nbasins, h_ncell, nmonths, spinup, nmembers, npar,
+                           h_pars, h_pet_t, h_precip_t, h_tmin_t, flow, nullptr, velocity, h_obs, h_ed, nullptr, h_series);
+}
+
+extern "C" int xh_calib_gauge_velocity_objective_multi(xh_ctx *ctx, int32_t nbasins, const int64_t *h_ncell, int32_t nmonths,
+                                                       int32_t spinup, int32_t nmembers, int32_t npar, const double *h_pars,
+                                                       const double *const *h_pet_t, const double *const *h_precip_t,
+                                                       const double *const *h_tmin_t, const xh_calib_gauge_desc *gauge,
+                                                       const xh_calib_velocity_desc *velocity, const double *h_obs,
+                                                       double *h_ed, double *h_ed_gauge, double *h_series) {
+    if (!ctx) return XH_ERR_ARG;
+    XH_REQUIRE(ctx, gauge && velocity, "xh_calib_gauge_velocity_objective_multi: NULL tables");
+    return objective_multi(ctx, "xh_calib_gauge_velocity_objective_multi", nbasins, h_ncell, nmonths, spinup, nmembers, npar,
+                           h_pars, h_pet_t, h_precip_t, h_tmin_t, nullptr, gauge, velocity, h_obs, h_ed, h_ed_gauge, h_series);
 }

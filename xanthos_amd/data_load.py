@@ -210,6 +210,14 @@ class DataLoader:
             self.flow_dist = self.load_routing_data(s.flow_distance, rep_val=1000)
             self.flow_dir = self.load_routing_data(s.flow_direction)
             self.str_velocity = self.load_routing_data(s.strm_veloc, rep_val=0)
+            # [[mrtm]] velocity_scale: every cell's velocity times its basin's scale, here, so that the routing plans, the
+            # calibration tables and the hydropower post-processors all see the scaled array; velocity_scale [n_basins] is
+            # what was loaded (ones without a file), which a calibration of the velocity multiplies into what it writes
+            self.velocity_scale = np.ones(int(s.n_basins))
+            if getattr(s, 'velocity_scale_file', None) is not None:
+                from .calibrate.velocity_scale import apply_velocity_scale, read_velocity_scale
+                self.velocity_scale = read_velocity_scale(s.velocity_scale_file, int(s.n_basins), '[[mrtm]] velocity_scale')
+                self.str_velocity = apply_velocity_scale(self.str_velocity, self.basin_ids, self.velocity_scale)
             self.instream_flow = np.zeros((s.ncell,), dtype=float)
             self.chs_prev = self.load_chs_data()
 

@@ -335,6 +335,11 @@ class ConfigReader:
             # chains of lanes, equal to the reference to rounding (<= 1e-9 relative; NOT bit for bit), twice as fast --, `exact`
             # -- every sum in scipy's stored order, ChStorage / Avg_ChFlow bit-identical to the reference --, or `default`: the
             # library's, which is `reassociated` since round 5 (XH_ROUTE_REASSOC=0 in the environment makes it `exact`)
+            # (not a key of the reference) per-basin scales of the channel velocity, as a calibration with
+            # calibrate_velocity = 1 writes them: csv basin_id,scale relative to the routing directory; the loader
+            # multiplies the velocity of every cell by its basin's scale (basins not listed: 1)
+            vs = m.get('velocity_scale')
+            self.velocity_scale_file = None if vs in (None, 'none') else os.path.join(self.rt_model_dir, vs)
             self.routing_form = str(m.get('routing_form', 'default')).strip().lower()
             if self.routing_form not in ('default', 'reassociated', 'exact'):
                 raise ValidationException("routing_form must be 'reassociated', 'exact' or 'default', not '{}'".format(
@@ -502,6 +507,30 @@ class ConfigReader:
         if self.cal_gauges is None and 'observed' not in cfg:
             raise ValidationException('[Calibrate] needs observed (or, with set_calibrate = 1, gauges and gauge_observed).')
         self.cal_observed = cfg.get('observed')
+        # (not keys of the reference) calibrate_velocity = 1: the streamflow objective also calibrates one velocity scale
+        # per basin inside velocity_scale_bounds = lo, hi (default 0.25, 4: a choice, not a measurement)
+        try:
+            self.calibrate_velocity = int(cfg.get('calibrate_velocity', 0))
+        except (TypeError, ValueError):
+            self.calibrate_velocity = -1
+        if self.calibrate_velocity not in (0, 1):
+            raise ValidationException('[Calibrate] calibrate_velocity = {!r} must be 0 or 1.'.format(
+                cfg.get('calibrate_velocity')))
+        if self.calibrate_velocity and self.set_calibrate != 1:
+            raise ValidationException('[Calibrate] calibrate_velocity = 1 calibrates the channel velocity against routed '
+                                      'streamflow and needs set_calibrate = 1; set_calibrate = {}.'.format(
+                                          self.set_calibrate))
+        raw = cfg.get('velocity_scale_bounds')
+        if raw is not None and not self.calibrate_velocity:
+            raise ValidationException('[Calibrate] velocity_scale_bounds is valid only with calibrate_velocity = 1.')
+        self.velocity_scale_bounds = None
+        if self.calibrate_velocity:
+            from .calibrate.velocity_scale import DEFAULT_BOUNDS, check_bounds
+            if raw is None:
+                raw = DEFAULT_BOUNDS
+            elif not isinstance(raw, (list, tuple)):
+                raw = [x for x in str(raw).replace(',', ' ').split()]
+            self.velocity_scale_bounds = check_bounds(raw, '[Calibrate] velocity_scale_bounds')
         self.obs_unit = self.ck_obs_unit(self.set_calibrate, cfg['obs_unit'])
         self.calib_out_dir = cfg['calib_out_dir']
         basins = cfg.get('calibration_basins')

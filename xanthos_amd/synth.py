@@ -217,7 +217,8 @@ def data_bag(world, forcing):
 def write_example(root, world, forcing, start_year, end_year, project='pm_abcd_mrtm_synth', runoff_spinup=36,
                   routing_spinup=None, output_vars=('q', 'avgchflow'), obs=None, post=False, aggregates=False,
                   hist_flag=True, ch_storage=None, output_format=1, output_in_year=0, set_calibrate=0,
-                  calibration_basins='1-2', gauges=None, gauge_obs=None, gauge_missing=None):
+                  calibration_basins='1-2', gauges=None, gauge_obs=None, gauge_missing=None, calibrate_velocity=0,
+                  velocity_scale_bounds=None, velocity_scale=None):
     """Write ``world`` + ``forcing`` as a Xanthos-style input tree under ``root`` and return the .ini path.
 
     Layout and file names follow the reference's example (ini_reader.py:254-279, 353-381, 399-416, 425-437):
@@ -235,6 +236,9 @@ def write_example(root, world, forcing, start_year, end_year, project='pm_abcd_m
     ``gauges`` (rows [gauge_id, cell_id (1-based)[, weight]]) + ``gauge_obs`` (rows [gauge_id, 0, 0, value], NaN =
     missing; ``gauge_missing``: a sentinel written to the ini) switch on ``set_calibrate = 1`` at stream gauges; ``obs``
     is then optional.
+    ``calibrate_velocity`` = 1 (with ``set_calibrate = 1`` or gauges) and ``velocity_scale_bounds`` = (lo, hi) go to
+    [Calibrate] as given; ``velocity_scale`` (rows [basin_id, scale], or a dict) is written as routing/mrtm/
+    velocity_scale.csv and named in [[mrtm]].
     """
     import os
     inp = os.path.join(root, 'input')
@@ -284,6 +288,16 @@ def write_example(root, world, forcing, start_year, end_year, project='pm_abcd_m
                  'calibration_basins = {}\n').format(int(set_calibrate), obs_file,
                                                      'm3_per_sec' if set_calibrate else 'km3_per_mth',
                                                      os.path.join(root, 'calib_out'), calibration_basins)
+    if calib and calibrate_velocity:
+        calib += 'calibrate_velocity = {}\n'.format(int(calibrate_velocity))
+    if calib and velocity_scale_bounds is not None:
+        calib += 'velocity_scale_bounds = {!r}, {!r}\n'.format(*[float(x) for x in velocity_scale_bounds])
+    vs_line = ''
+    if velocity_scale is not None:
+        rows = sorted(velocity_scale.items()) if isinstance(velocity_scale, dict) else np.atleast_2d(velocity_scale)
+        with open(os.path.join(dirs['rt'], 'velocity_scale.csv'), 'w') as fh:
+            fh.write('basin_id,scale\n' + ''.join('{},{!r}\n'.format(int(b), float(v)) for b, v in rows))
+        vs_line = 'velocity_scale = velocity_scale.csv\n'
     post_project = post_sections = ''
     if post:
         acc = os.path.join(inp, 'accessible')
@@ -375,7 +389,7 @@ routing_spinup = {rtsp}
 channel_velocity = velocity.npy
 flow_distance = flow_dist.npy
 flow_direction = flow_dir.npy
-{calib}{post_sections}'''.format(ofmt=int(output_format), oyear=int(output_in_year), chs=chs_lines, hist='True' if hist_flag else 'False', post_project=post_project, post_sections=post_sections, project=project, root=root, nb=world.n_basins, ncell=world.ncell, nrow=world.nrow, ncol=world.ncol,
+{vs}{calib}{post_sections}'''.format(vs=vs_line, ofmt=int(output_format), oyear=int(output_in_year), chs=chs_lines, hist='True' if hist_flag else 'False', post_project=post_project, post_sections=post_sections, project=project, root=root, nb=world.n_basins, ncell=world.ncell, nrow=world.nrow, ncol=world.ncol,
                   y0=start_year, y1=end_year, ov=', '.join(output_vars), cal=int(obs is not None or gauges is not None), nlcs=world.nlcs,
                   lcy=', '.join(str(y) for y in world.lc_years), rsp=runoff_spinup,
                   rtsp=nmonths if routing_spinup is None else routing_spinup,
