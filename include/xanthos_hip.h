@@ -50,6 +50,7 @@ int xh_device_name(xh_ctx *ctx, char *buf, size_t len);
 
 int xh_malloc(xh_ctx *ctx, size_t bytes, void **d_ptr);
 int xh_free(xh_ctx *ctx, void *d_ptr);
+int xh_mem_info(xh_ctx *ctx, size_t *free_bytes, size_t *total_bytes);         /* hipMemGetInfo of the context's device */
 int xh_memcpy_h2d(xh_ctx *ctx, void *d_dst, const void *h_src, size_t bytes);
 int xh_memcpy_d2h(xh_ctx *ctx, void *h_dst, const void *d_src, size_t bytes);   /* waits for the stream */
 int xh_memcpy_d2d(xh_ctx *ctx, void *d_dst, const void *d_src, size_t bytes);
@@ -85,7 +86,7 @@ int xh_transpose(xh_ctx *ctx, const double *d_src, int64_t rows, int64_t cols, d
 /* HIP-event timing of the kernels each entry point launches, accumulated per kernel name on the context's stream.
  * Names: "pm_pet", "abcd_spinup", "abcd_basin_mean", "abcd_sim", "mrtm_route", "calib_abcd", "calib_kge", "calib_de",
  * "agg_time", "agg_spatial", "drought_thresh", "drought_stats", "hargreaves_pet", "gwam_spinup", "gwam_sim",
- * "hs_pet", "trn_daylight", "trn_pet", "diag_cell_total", "diag_group_sum".  xh_timing_get waits for the stream, then
+ * "hs_pet", "trn_daylight", "trn_pet", "diag_cell_total", "diag_group_sum", "ens_stats".  xh_timing_get waits for the stream, then
  * returns total milliseconds and launch count. */
 int xh_timing_reset(xh_ctx *ctx);
 /* a caller-named span on the context's stream, read back with xh_timing_get like the library's own timers (one open
@@ -433,6 +434,25 @@ int xh_diag_cell_total(xh_ctx *ctx, int64_t ncell, int32_t ncols, const double *
                        double div2, double *d_out, int64_t out_stride);
 int xh_diag_group_sum(xh_ctx *ctx, int64_t ncell, int32_t k, int32_t ngroups, const int32_t *h_group, const double *d_vals,
                       double *d_sums, int64_t *d_counts);
+
+/* ------------------------------------------------------------------ ensemble statistics
+ * xh_ens_stats replaces no function of the reference: there an ensemble is a Python loop of whole runs and the
+ * across-run mean / spread / quantiles are a host-side reduction over the files.  n elements (rows x columns of one
+ * variable as written); h_d_members: host array of nmembers DEVICE pointers, [n] each; stat_mask: XH_ENS_* bits; h_q
+ * [nq] quantiles in [0, 1]; h_d_out: host array of DEVICE pointers, [n] each, one per requested statistic in the order
+ * mean, std, min, max (those whose bit is set), then the nq quantiles.  Every member array is read once per call.
+ * Definitions (numpy's over axis 0 of the stacked array, bit for bit, for finite or NaN values): mean = sum in member
+ * order from 0.0, / S; std = sample standard deviation (ddof = 1: sum in member order of (x - mean)^2, / (S - 1), sqrt;
+ * NaN for S = 1); min / max NaN-propagating; quantile q: ascending sort, h = (S - 1) q, lo = floor(h), hi = min(lo + 1,
+ * S - 1), g = h - lo, d = a[hi] - a[lo], g < 0.5 ? a[lo] + d g : a[hi] - d (1 - g); NaN if any member is NaN.
+ * XH_ERR_LIMIT: more than 64 members or 16 quantiles.  Asynchronous on the context's stream (after one upload of the
+ * pointer table, which waits for the stream).                                                                      */
+#define XH_ENS_MEAN 1u
+#define XH_ENS_STD 2u
+#define XH_ENS_MIN 4u
+#define XH_ENS_MAX 8u
+int xh_ens_stats(xh_ctx *ctx, int64_t n, int32_t nmembers, const double *const *h_d_members, uint32_t stat_mask,
+                 int32_t nq, const double *h_q, double *const *h_d_out);
 
 /* The same objective for SEVERAL basins in one launch, each basin with its own population: one basin alone is only
  * months x ~1.7 us of dependent chain, far too little to fill the chip.  h_ncell [nbasins]; h_pars [nbasins, nmembers,

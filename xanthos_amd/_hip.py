@@ -3,8 +3,10 @@
 This is the only place the shared library is loaded.  There is NO CPU fallback: if the library is missing, or no
 MI355X is visible, the calls raise :class:`HipUnavailable` -- the product path never routes through numpy.
 """
+import contextlib
 import ctypes
 import os
+import threading
 from ctypes import POINTER, Structure, byref, c_char_p, c_double, c_int, c_int8, c_int32, c_int64, c_size_t, \
     c_uint64, c_void_p
 
@@ -19,6 +21,8 @@ XH_ROUTE_TEST_FAULT, XH_ROUTE_VALIDATE = 16, 32
 XH_ROUTE_REASSOC, XH_ROUTE_EXACT = 128, 256      # reassociated (tolerance) form of the routing kernel / the bit-exact kernels
 XH_ROUTE_NO_PLAIN = 0x4000                       # (xh_common.h, what a guard trip re-routes with) pairs of sums in every unit: not the prepared plan
 XH_DAYLIGHT_REFERENCE, XH_DAYLIGHT_MONTHLY = 0, 1  # Thornthwaite's daylight order: the reference's repeat / every month its own
+XH_ERR_ARG, XH_ERR_HIP, XH_ERR_LIMIT, XH_ERR_DEVICE = 1, 2, 3, 4
+ENS_STAT_BITS = {'mean': 1, 'std': 2, 'min': 4, 'max': 8}       # XH_ENS_* of xh_ens_stats, in its output order
 
 
 class HipUnavailable(RuntimeError):
@@ -100,6 +104,7 @@ SIGNATURES = {
     'xh_device_name': (c_int, [_P, ctypes.c_char_p, c_size_t]),
     'xh_malloc': (c_int, [_P, c_size_t, POINTER(c_void_p)]),
     'xh_free': (c_int, [_P, _P]),
+    'xh_mem_info': (c_int, [_P, POINTER(c_size_t), POINTER(c_size_t)]),
     'xh_memcpy_h2d': (c_int, [_P, _P, _P, c_size_t]),
     'xh_memcpy_d2h': (c_int, [_P, _P, _P, c_size_t]),
     'xh_memcpy_d2d': (c_int, [_P, _P, _P, c_size_t]),
@@ -186,6 +191,7 @@ SIGNATURES = {
     'xh_hact_sim': (c_int, [_P, c_int32, c_int32, c_int32, c_int32, _P, c_double, c_double, _P, _P, _P, _P, _P, _P, _P]),
     'xh_diag_cell_total': (c_int, [_P, c_int64, c_int32, _P, c_double, _P, c_double, _P, c_int64]),
     'xh_diag_group_sum': (c_int, [_P, c_int64, c_int32, c_int32, _P, _P, _P, _P]),
+    'xh_ens_stats': (c_int, [_P, c_int64, c_int32, POINTER(c_void_p), ctypes.c_uint32, c_int32, _P, POINTER(c_void_p)]),
     'xh_synth_forcing': (c_int, [_P, c_uint64, c_double, c_int64, c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
 }
 
@@ -339,6 +345,19 @@ class Context:
 
     def sync(self):
         self._check(lib().xh_sync(self.handle))
+
+    def mem_info(self):
+        """(free, total) bytes of the device's memory right now (xh_mem_info)."""
+        free, total = c_size_t(), c_size_t()
+        self._check(lib().xh_mem_info(self.handle, byref(free), byref(total)))
+        return free.value, total.value
+
+    def d2d(self, dst, src):
+        """Enqueue device -> device on this context's stream (xh_memcpy_d2d); ``dst`` and ``src`` of one size."""
+        if dst.nbytes != src.nbytes:
+            raise ValueError('size mismatch: {} vs {}'.format(dst.shape, src.shape))
+        self._check(lib().xh_memcpy_d2d(self.handle, _dptr(dst), _dptr(src), dst.nbytes))
+        return dst
 
     def empty(self, shape, dtype=np.float64):
         return DeviceArray(self, shape, dtype)
@@ -689,6 +708,27 @@ class Context:
         self._check(lib().xh_diag_group_sum(self.handle, ncell, k, ngroups, _host_ptr(gi), _dptr(vals), _dptr(sums),
                                             _dptr(counts)))
 
+    # ---- ensemble statistics (csrc/xh_ens.hip)
+    def ens_stats(self, n, members, stats=(), quantiles=(), out=None):
+        """Across-member statistics of ``members`` (DeviceArrays / device pointers of n float64 each): ``stats`` out of
+        'mean', 'std', 'min', 'max' and ``quantiles`` in [0, 1].  ``out``: one DeviceArray / pointer per statistic, in the
+        library's order -- mean, std, min, max as requested, then the quantiles as given.  Every member array is read once."""
+        unknown = [s for s in stats if s not in ENS_STAT_BITS]
+        if unknown:
+            raise ValueError('unknown ensemble statistic {}'.format(unknown))
+        mask = 0
+        for s in stats:
+            mask |= ENS_STAT_BITS[s]
+        q = np.ascontiguousarray(quantiles, dtype=np.float64).reshape(-1)
+        nout = bin(mask).count('1') + q.size
+        if out is None or len(out) != nout:
+            raise ValueError('{} statistics need {} output arrays'.format(nout, nout))
+        nmem = len(members)
+        p_mem = (c_void_p * max(nmem, 1))(*[_dptr(m) for m in members])
+        p_out = (c_void_p * max(nout, 1))(*[_dptr(o) for o in out])
+        self._check(lib().xh_ens_stats(self.handle, int(n), nmem, p_mem, mask, q.size, _host_ptr(q) if q.size else None,
+                                       p_out))
+
     # ---- bench support
     def synth_forcing(self, seed, ncell, nmonths, lat, out, nan_frac=0.001, cell_ids=None):
         """out: dict name -> DeviceArray for synth.FORCING_NAMES (or only 'tas'). cell_ids: device int64 [ncell]
@@ -966,10 +1006,26 @@ def mrtm_um_csr(upid):
 
 
 _contexts = {}
+_thread = threading.local()
+
+
+@contextlib.contextmanager
+def thread_context(ctx):
+    """Inside the block, get_context() of ``ctx``'s device gives ``ctx`` to THIS host thread: a worker thread of the
+    ensemble driver runs the writer and the post-processors on a context of its own (a Context is not thread-safe)."""
+    before = getattr(_thread, 'ctx', None)
+    _thread.ctx = ctx
+    try:
+        yield ctx
+    finally:
+        _thread.ctx = before
 
 
 def get_context(device=0):
-    """Process-wide context per device."""
+    """Process-wide context per device (or the calling thread's own: thread_context)."""
+    own = getattr(_thread, 'ctx', None)
+    if own is not None and own.handle is not None and own.device == device:
+        return own
     ctx = _contexts.get(device)
     if ctx is None or ctx.handle is None:
         ctx = _contexts[device] = Context(device)

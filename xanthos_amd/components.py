@@ -30,12 +30,31 @@ _FORCING_DATA = {'pm': {'tas': 'tair_load', 'tmin': 'TMIN_load', 'rhs': 'rhs_loa
                  'thornthwaite': {'tas': 'tair'}, 'abcd': {'precip': 'precip', 'abcd_tmin': 'tmin'},
                  'gwam': {'precip': 'precip'}, 'none': {}}
 
+# DevicePipeline forcing name -> (setting that names its file or array, setting of its NetCDF variable, the loader's
+# nan_to_num), per module: how the loader fills the attributes above (data_load.py), for a caller that loads one member's
+# forcing without a second DataLoader (ensemble.py)
+_FORCING_SETTINGS = {'pm': {k: ('pm_' + k, None, True) for k in ('tas', 'tmin', 'rhs', 'wind', 'rsds', 'rlds')},
+                     'hargreaves': {'temp': ('TemperatureFile', 'TempVarName', False),
+                                    'dtr': ('DailyTemperatureRangeFile', 'DTRVarName', False)},
+                     'hs': {k: ('hs_' + k, None, False) for k in ('tas', 'tmax', 'tmin')},
+                     'thornthwaite': {'tas': ('trn_tas', None, True)},
+                     'abcd': {'precip': ('PrecipitationFile', 'PrecipVarName', False),
+                              'abcd_tmin': ('TempMinFile', 'TempMinVarName', True)},
+                     'gwam': {'precip': ('PrecipitationFile', 'PrecipVarName', False)}, 'none': {}}
+
 pet_mod = runoff_mod = routing_mod = None
 
 _TOPOLOGIES = {}      # (digest of coords + flow directions, grid shape) -> (dsid, upid, UM with its cached device plan)
 
 # result attribute -> name of the array in the device pipeline
 _RESULTS = {'PET': 'pet', 'AET': 'aet', 'Q': 'q', 'Sav': 'sav', 'ChStorage': 'chs', 'Avg_ChFlow': 'avg'}
+
+
+def runs_device_resident(s, run_pet=True, run_runoff=True):
+    """Whether ``Components.simulation`` keeps this configuration in HBM from the forcing to the six outputs: Hargreaves,
+    Hargreaves-Samani or Thornthwaite PET with any runoff module, or PM -> ABCD.  Anything else (a PET file, PM without
+    ABCD) runs stage by stage on host arrays."""
+    return bool(run_pet) and (s.pet_module in HGM_PET or (s.pet_module == 'pm' and s.runoff_module == 'abcd' and bool(run_runoff)))
 
 
 def _result(attr):
@@ -209,8 +228,7 @@ class Components:
         logging.info('---{} in progress...'.format(notify))
         t0 = time.time()
         s, group = self.s, self.group
-        hgm = s.pet_module in HGM_PET
-        if not run_pet or not (hgm or (s.pet_module == 'pm' and s.runoff_module == 'abcd' and run_runoff)):
+        if not runs_device_resident(s, run_pet, run_runoff):
             pet_out = self.calculate_pet()
             if run_runoff:
                 self.calculate_runoff(pet=pet_out)
@@ -219,15 +237,7 @@ class Components:
             return
         runoff = s.runoff_module if run_runoff else 'none'
         sharded = group is not None and group.size > 1
-        if hgm:
-            if sharded:
-                raise ValidationException('{}: {} PET and {} runoff run on one GPU; sharding them over several GPUs is not '
-                                          'implemented.'.format(s.mod_cfg, s.pet_module, s.runoff_module))
-            if runoff == 'gwam':
-                self._check_gwam_spinup()
-            elif runoff == 'abcd':
-                from .runoff import abcd as abcd_mod
-                abcd_mod._check_spinup(s.runoff_spinup, s.nmonths)
+        self.check_resident(runoff, sharded)
         ctx = _hip.get_context(s.device)
         t = time.time()
         um = self.topology() if (run_routing and s.routing_module == 'mrtm') else None
@@ -279,6 +289,31 @@ class Components:
             self.pipe = SimpleNamespace(out=gather.out, plan=pipe.plan, ncell=s.ncell, nmonths=s.nmonths) if self.is_root else None
         self.timings['download'] = 0.0
         logging.info('---{0} has finished successfully: {1} seconds ---'.format(notify, time.time() - t0))
+
+    def check_resident(self, runoff, sharded=False):
+        """What a device-resident run of Hargreaves / Hargreaves-Samani / Thornthwaite PET checks before it touches the
+        device: one GPU, and spin-ups inside the series."""
+        s = self.s
+        if s.pet_module in HGM_PET:
+            if sharded:
+                raise ValidationException('{}: {} PET and {} runoff run on one GPU; sharding them over several GPUs is not '
+                                          'implemented.'.format(s.mod_cfg, s.pet_module, s.runoff_module))
+            if runoff == 'gwam':
+                self._check_gwam_spinup()
+            elif runoff == 'abcd':
+                from .runoff import abcd as abcd_mod
+                abcd_mod._check_spinup(s.runoff_spinup, s.nmonths)
+
+    def member_view(self, settings, pipe):
+        """A Components of the same grid and static data whose results are ``pipe.out`` (anything with ``out``, ``plan``,
+        ``ncell``, ``nmonths``) and whose settings are ``settings``: what the post-processors and the writer of one
+        ensemble member run on.  Nothing is loaded or copied."""
+        import copy
+        c = copy.copy(self)
+        c.s, c.pipe = settings, pipe
+        c.timings, c._host = {}, {}
+        c._writer = c._q = c._ac = None
+        return c
 
     def _pipeline_args(self, runoff, um, cells=None):
         """DevicePipeline's keyword arguments for this configuration; ``cells``: one rank's rows of the grid."""
@@ -429,8 +464,9 @@ class Components:
             TimeSeriesPlot(self.s, q, ac, self._diag_maps())
             logging.info('---Plots has finished successfully: %s seconds ------' % (time.time() - t0))
 
-    def output_simulation(self):
-        """Aggregate / convert on the device and write the selected variables (components.py:441-474)."""
+    def output_simulation(self, keep_device=False, write_files=True):
+        """Aggregate / convert on the device and write the selected variables (components.py:441-474).  ``keep_device`` /
+        ``write_files = False`` (the ensemble driver): the arrays as written stay in HBM too / are formed without files."""
         from .data_writer.out_writer import OutWriter
         if not self.is_root:               # (a sharded run: rank 0 holds the gathered outputs and writes)
             return
@@ -440,8 +476,11 @@ class Components:
                            and (a != 'Avg_ChFlow' or self.pipe.plan is not None) else getattr(self, a))
                        for k, a in names.items() if k in self.s.output_vars or k in ('q', 'avgchflow')}
         writer = OutWriter(self.s, self.data.area, all_outputs)
+        writer.keep_device, writer.write_files = keep_device, write_files
         writer.write()
         self._writer, self._q, self._ac = writer, None, None
+        if not write_files:
+            return
         q_written = writer.get('q', host=False) if 'q' in writer.output_names else all_outputs['q']
         # always from the written runoff, or from self.Q when 'q' is not among the output variables (:461-472)
         writer.write_aggregates(self.data, q_written, self.s.AggregateRunoffBasin, self.s.AggregateRunoffCountry,

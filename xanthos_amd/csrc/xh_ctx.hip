@@ -365,6 +365,13 @@ int xh_malloc(xh_ctx *ctx, size_t bytes, void **d_ptr) {
     return XH_OK;
 }
 
+int xh_mem_info(xh_ctx *ctx, size_t *free_bytes, size_t *total_bytes) {
+    if (!ctx || !free_bytes || !total_bytes) return XH_ERR_ARG;
+    XH_HIP(ctx, hipSetDevice(ctx->device));
+    XH_HIP(ctx, hipMemGetInfo(free_bytes, total_bytes));
+    return XH_OK;
+}
+
 int xh_free(xh_ctx *ctx, void *d_ptr) {
     if (!ctx) return XH_ERR_ARG;
     if (!d_ptr) return XH_OK;

@@ -28,6 +28,10 @@ class OutWriter:
         self.ctx = _hip.get_context(getattr(settings, 'device', 0) if device is None else device)
         self.inputs = {o: all_outputs[o] for o in self.output_names}           # host ndarray or DeviceArray
         self.outputs = [None] * len(self.output_names)
+        # (the ensemble driver, ensemble.py) keep_device: the aggregated / converted arrays stay in HBM as well, for the
+        # across-member statistics; write_files = False: the arrays are formed as written but no file is
+        self.keep_device, self.write_files = False, True
+        self.device_outputs = {}
         self.grid_areas = np.asarray(grid_areas, dtype=np.float64)
         self.conversion_mm_km3 = self.grid_areas / 1e6
         self.proj_name = settings.ProjectName
@@ -51,6 +55,20 @@ class OutWriter:
             self.outputs[i] = self.outputs[i].download()
         return self.outputs[i]
 
+    def get_device(self, varstr):
+        """The written array of a variable in HBM, with keep_device: the aggregated / converted array write() kept, or the
+        run's own array for a monthly, unconverted variable (which the next run overwrites); a host array is uploaded.
+        Returns (DeviceArray, whether the caller owns it)."""
+        if varstr in self.device_outputs:
+            return self.device_outputs.pop(varstr), True
+        a = self.inputs[varstr]
+        if self.output_in_year or (self.out_unit == UNIT_KM3_MTH and varstr != 'avgchflow'):
+            a = self.get(varstr)
+        return (a, False) if isinstance(a, _hip.DeviceArray) else (self.ctx.upload(np.asarray(a, dtype=np.float64)), True)
+
+    def unit_of(self, var):
+        return 'm3persec' if var == 'avgchflow' else self.out_unit_str
+
     # ---- device helpers
     def _on_device(self, arr):
         if isinstance(arr, _hip.DeviceArray):
@@ -61,13 +79,15 @@ class OutWriter:
         """[ncell, nmonths] -> [ncell, nyears] (:237-248), optionally x scale[c] afterwards. Returns a host array."""
         return self._agg(arr, NMONTHS, 0 if func == 'sum' else 1, scale)
 
-    def _agg(self, arr, group, mode, scale):
+    def _agg(self, arr, group, mode, scale, keep=None):
         src, mine = self._on_device(arr)
         ncell, ncols = src.shape
         dst = self.ctx.empty((ncell, ncols // group))
         d_scale = None if scale is None else self.ctx.upload(scale)
         self.ctx.agg_time(ncell, ncols, group, mode, d_scale, src, dst)
         out = dst.download()
+        if keep is not None and self.keep_device:
+            self.device_outputs[keep], dst = dst, None
         for b in (dst, d_scale, src if mine else None):
             if b is not None:
                 b.free()
@@ -103,14 +123,19 @@ class OutWriter:
             unit = 'm3persec' if flow else self.out_unit_str
             scale = self.conversion_mm_km3 if (self.out_unit == UNIT_KM3_MTH and not flow) else None
             if self.output_in_year:
-                self.outputs[i] = self._agg(self.inputs[var], NMONTHS, 1 if flow else 0, scale)
+                self.outputs[i] = self._agg(self.inputs[var], NMONTHS, 1 if flow else 0, scale, keep=var)
             elif scale is not None:
-                self.outputs[i] = self._agg(self.inputs[var], 1, 0, scale)
+                self.outputs[i] = self._agg(self.inputs[var], 1, 0, scale, keep=var)
             else:
                 a = self.inputs[var]
                 # a device array is saved from HBM (npy) or fetched for the csv writer
                 keep = isinstance(a, _hip.DeviceArray) and self.out_format == FORMAT_NPY
+                if not self.write_files:
+                    self.outputs[i] = a
+                    continue
                 self.outputs[i] = a if keep else (a.download() if isinstance(a, _hip.DeviceArray) else np.asarray(a))
+            if not self.write_files:
+                continue
             filename = os.path.join(self.out_folder, '{}_{}_{}'.format(var, unit, self.proj_name))
             self.write_data(filename, var, self.outputs[i], self.time_steps, first_id=1)
         if self._npy_from_device:

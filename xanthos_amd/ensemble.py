@@ -1,0 +1,465 @@
+"""An ensemble of forcing scenarios through one grid in one device-resident pass.
+
+The reference's way to run S forcing sets is a Python loop of ``Xanthos.execute(args)``: every run reads the static inputs
+again, and the across-run statistics are formed afterwards on the host.  ``run_ensemble`` keeps one ``Components``, one
+``DevicePipeline``, one topology and one routing plan; the members stream through two buffer sets -- member k + 1's forcing
+is read and uploaded on a second context while member k's kernels run on the main one and member k - 1's post-processors
+and write-out proceed on a third -- and the mean / spread / quantiles over the members are formed in HBM by
+``xh_ens_stats`` on the arrays as written (after OutputInYear and OutputUnit).
+
+Member ``name`` is written to ``<OutputFolder>/<name>/`` with exactly the files
+``Xanthos(ini).execute({**overrides, 'OutputFolder': ...})`` writes (the log stays in ``<OutputFolder>``); the statistics
+go to ``<OutputFolder>/ensemble/<var>_<unit>_<ProjectName>_<stat>.<ext>`` through ``OutWriter.write_data``.
+
+Only the settings that name the forcing arrays of the configured PET / runoff modules may vary per member
+(``ConfigReader.forcing_settings``).  There is no host fallback: without a device the call raises ``HipUnavailable``.
+"""
+import copy
+import csv
+import logging
+import os
+import threading
+import time
+from types import SimpleNamespace
+
+import numpy as np
+
+from . import _hip, launch
+from .components import _FORCING_DATA, _FORCING_SETTINGS, Components, runs_device_resident
+from .configurations import ConfigRunner
+from .ini_reader import ValidationException, parse_statistic
+from .pipeline import OUTPUTS, DevicePipeline
+
+MAX_MEMBERS_WITH_STATISTICS = 64        # xh_ens_stats' compiled limit
+STATISTICS_DIR = 'ensemble'
+# output variable -> result attribute (Components.output_simulation)
+_WRITTEN = ('pet', 'aet', 'q', 'soilmoisture', 'avgchflow')
+
+
+def refuse(member, key, why):
+    """The ValidationException of an ensemble refusal: names the member (None: the ensemble itself) and the key."""
+    who = 'the ensemble' if member is None else "member '{}'".format(member)
+    return ValidationException('[Ensemble] {}, {}: {}'.format(who, key, why))
+
+
+class EnsemblePlan(SimpleNamespace):
+    """What validate() made of a request: names, overrides (one dict per member), statistics [(label, q or None)],
+    statistics_vars, member_outputs, ncols (columns of an array as written), bytes_needed."""
+
+
+def read_members(config, path):
+    """The members table of [Ensemble]: a header row with ``name`` and setting names, one row per member; every cell is
+    resolved as the same key's value in the ini would be, an empty cell keeps the ini's value."""
+    if not os.path.isfile(path):
+        raise refuse(None, 'members', 'the members table {} does not exist'.format(path))
+    with open(path, newline='') as fh:
+        rows = [[c.strip() for c in r] for r in csv.reader(fh) if any(c.strip() for c in r)]
+    if not rows or 'name' not in rows[0]:
+        raise refuse(None, 'members', "{} needs a header row with a 'name' column".format(path))
+    header, known = rows[0], config.forcing_settings()
+    members = []
+    for r in rows[1:]:
+        cells = dict(zip(header, r + [''] * (len(header) - len(r))))
+        name = cells.pop('name')
+        # (a column that names no forcing setting is kept as written: validate() refuses it with the member's name)
+        members.append((name, {k: (config.resolve_forcing_setting(k, v) if k in known else v)
+                               for k, v in cells.items() if v != ''}))
+    return members
+
+
+def _normalise(members):
+    out = []
+    for m in members:
+        if isinstance(m, dict):
+            if 'name' not in m:
+                raise refuse(None, 'name', "a member given as a dict needs a 'name' key")
+            out.append((m['name'], {k: v for k, v in m.items() if k != 'name'}))
+        else:
+            name, overrides = m
+            out.append((name, dict(overrides or {})))
+    return out
+
+
+def _shape_of(value):
+    """Shape of a forcing override without reading it (an ndarray, or the header of a .npy); None when only the loader can
+    tell (NetCDF, MATLAB, text)."""
+    if isinstance(value, np.ndarray):
+        return value.shape
+    if isinstance(value, str) and value.endswith('.npy'):
+        return np.load(value, mmap_mode='r').shape
+    return None
+
+
+def written_vars(config):
+    return [v for v in config.output_vars if v in _WRITTEN and (v != 'avgchflow' or config.routing_module == 'mrtm')]
+
+
+def validate(config, members, statistics=(), statistics_vars=None, member_outputs=1, gpus=None):
+    """Every refusal of an ensemble request, before any GPU work; returns the EnsemblePlan."""
+    s = config
+    if getattr(s, 'calibrate', 0):
+        raise refuse(None, 'Calibrate', '[Ensemble] and Calibrate = 1 ([Calibrate]) exclude each other')
+    env_gpus = int(os.environ.get('XH_GPUS') or 1)
+    if (gpus and int(gpus) > 1) or env_gpus > 1 or launch.env_world()[2] > 1:
+        raise refuse(None, 'gpus', 'members dealt over several GPUs are not implemented; run the ensemble on one GPU')
+    runner = ConfigRunner(s)
+    if not runs_device_resident(s, runner.run_pet, runner.run_runoff):
+        raise refuse(None, 'pet_module / runoff_module', "the configuration {} runs stage by stage on host arrays, not device "
+                     'resident (device resident: hargreaves / hs / thornthwaite PET, or pm with abcd)'.format(s.mod_cfg))
+    members = _normalise(members)
+    if not members:
+        raise refuse(None, 'members', 'no members')
+    allowed = s.forcing_settings()
+    seen = set()
+    for name, overrides in members:
+        if not isinstance(name, str) or not name.strip():
+            raise refuse(name, 'name', 'a member needs a non-empty name')
+        if name != name.strip() or name in ('.', '..', STATISTICS_DIR) or os.path.basename(name) != name or \
+                any(ch in name for ch in '/\\\0') or (os.altsep and os.altsep in name):
+            raise refuse(name, 'name', "not a plain directory name ('{}' is kept for the statistics)".format(STATISTICS_DIR))
+        if name in seen:
+            raise refuse(name, 'name', 'duplicate member name')
+        seen.add(name)
+        for key, value in overrides.items():
+            if key not in allowed:
+                raise refuse(name, key, 'may not vary per member: only the forcing arrays of pet_module = {} / runoff_module = {} '
+                             'may ({})'.format(s.pet_module, s.runoff_module, ', '.join(sorted(allowed))))
+            if getattr(s, key, None) is None:
+                raise refuse(name, key, 'the configuration runs without it (no {} in the ini): a member cannot switch it on'.format(key))
+            if not isinstance(value, (str, np.ndarray)):
+                raise refuse(name, key, 'a path or an ndarray is expected, not {}'.format(type(value).__name__))
+            if isinstance(value, str) and not os.path.isfile(value):
+                raise refuse(name, key, 'file {} does not exist'.format(value))
+            shape = _shape_of(value)
+            if shape is not None and tuple(shape) != (s.ncell, s.nmonths):
+                raise refuse(name, key, 'the forcing array has shape {}, expected [ncell, nmonths] = {}'.format(
+                    tuple(shape), (s.ncell, s.nmonths)))
+    stats, labels = [], set()
+    for text in (statistics or ()):
+        try:
+            label, q = parse_statistic(text)
+        except ValidationException as exc:
+            raise refuse(None, 'statistics', str(exc))
+        if label not in labels:
+            labels.add(label)
+            stats.append((label, q))
+    outputs = written_vars(s)
+    if statistics_vars is None:
+        statistics_vars = list(outputs)
+    statistics_vars = list(statistics_vars) if stats else []
+    for v in statistics_vars:
+        if v not in outputs:
+            raise refuse(None, 'statistics_vars', "'{}' is not among the variables the run writes ({})".format(v, ', '.join(outputs)))
+    member_outputs = int(member_outputs)
+    if member_outputs not in (0, 1):
+        raise refuse(None, 'member_outputs', 'must be 0 or 1')
+    if not member_outputs and not (stats and statistics_vars):
+        raise refuse(None, 'member_outputs', 'member_outputs = 0 without statistics writes nothing')
+    if stats and len(members) > MAX_MEMBERS_WITH_STATISTICS:
+        raise refuse(None, 'statistics', '{} members exceed the {} the statistics kernel takes'.format(
+            len(members), MAX_MEMBERS_WITH_STATISTICS))
+    ncols = s.nmonths // 12 if s.OutputInYear else s.nmonths
+    nforcing = sum(len(_FORCING_DATA[m]) for m in (s.pet_module, s.runoff_module))
+    # the member stack of every statistics variable, one variable's statistics, and the two buffer sets
+    need = 8 * s.ncell * (ncols * (len(members) * len(statistics_vars) + len(stats)) + 2 * s.nmonths * (nforcing + len(OUTPUTS)))
+    return EnsemblePlan(names=[n for n, _ in members], overrides=[o for _, o in members], statistics=stats,
+                        statistics_vars=statistics_vars, member_outputs=member_outputs, ncols=ncols, bytes_needed=need)
+
+
+def check_fits(plan, free_bytes):
+    """The member stack against the free HBM."""
+    if plan.statistics and plan.bytes_needed > free_bytes:
+        raise refuse(None, 'statistics', 'the stack of {} members x {} variables and the buffer sets need {} bytes of HBM, {} '
+                     'bytes are free'.format(len(plan.names), len(plan.statistics_vars), plan.bytes_needed, free_bytes))
+
+
+class _Aborted(Exception):
+    pass
+
+
+def run_schedule(n, upload, compute, write, overlap=True, nsets=2):
+    """Members 0 .. n - 1 through ``upload(k, i)``, ``compute(k, i)``, ``write(k, i)`` (i: buffer set).  ``overlap``:
+    uploads on one host thread, write-outs on another, computes on the caller's, over ``nsets`` buffer sets -- member k's
+    compute starts only when its upload has completed, its write-out when its compute has; a set's forcing is
+    uploaded anew only when the compute that read it has ended, its outputs are computed anew only when their write-out
+    has.  Otherwise strictly one after the other on set 0.  The first exception of any stage ends the run and is raised."""
+    if not overlap:
+        for k in range(n):
+            upload(k, 0)
+            compute(k, 0)
+            write(k, 0)
+        return
+    uploaded, computed, written = ([threading.Event() for _ in range(n)] for _ in range(3))
+    abort, errors = threading.Event(), []
+
+    def wait(event):
+        while not event.wait(0.05):
+            if abort.is_set():
+                raise _Aborted()
+        if abort.is_set():
+            raise _Aborted()
+
+    def guarded(body):
+        def run():
+            try:
+                body()
+            except _Aborted:
+                pass
+            except BaseException as exc:          # handed to the caller's thread
+                errors.append(exc)
+                abort.set()
+        return run
+
+    def uploads():
+        for k in range(n):
+            if k >= nsets:
+                wait(computed[k - nsets])
+            upload(k, k % nsets)
+            uploaded[k].set()
+
+    def computes():
+        for k in range(n):
+            wait(uploaded[k])
+            if k >= nsets:
+                wait(written[k - nsets])
+            compute(k, k % nsets)
+            computed[k].set()
+
+    def writes():
+        for k in range(n):
+            wait(computed[k])
+            write(k, k % nsets)
+            written[k].set()
+
+    threads = [threading.Thread(target=guarded(uploads), name='xh-ens-upload'),
+               threading.Thread(target=guarded(writes), name='xh-ens-write')]
+    for t in threads:
+        t.start()
+    guarded(computes)()
+    for t in threads:
+        t.join()
+    if errors:
+        raise errors[0]
+
+
+class _Lazy(dict):
+    """stat -> host array; an array still in HBM is fetched (and released there) the first time it is read."""
+
+    def __getitem__(self, key):
+        v = dict.__getitem__(self, key)
+        if isinstance(v, _hip.DeviceArray):
+            host = v.download()
+            v.free()
+            dict.__setitem__(self, key, host)
+            v = host
+        return v
+
+    def get(self, key, default=None):
+        return self[key] if key in self else default
+
+    def items(self):
+        return [(k, self[k]) for k in self]
+
+    def values(self):
+        return [self[k] for k in self]
+
+
+class EnsembleResult:
+    """names, member_dirs, statistics[var][stat] (host arrays, fetched from HBM on first read), timings (seconds per
+    member: 'upload', 'kernels', 'post', 'write'; 'statistics' and 'total' for the run)."""
+
+    def __init__(self, names, member_dirs, statistics, timings):
+        self.names, self.member_dirs, self.statistics, self.timings = names, member_dirs, statistics, timings
+
+
+def run(config, members=None, statistics=None, statistics_vars=None, member_outputs=None, overlap=True):
+    """The driver behind run_ensemble / Xanthos.execute_ensemble; ``config``: a staged ConfigReader."""
+    s = config
+    ens = getattr(s, 'ensemble', None) or {}
+    if members is None:
+        if not ens:
+            raise refuse(None, 'members', 'neither a members argument nor an [Ensemble] section')
+        members = read_members(s, ens['members'])
+    statistics = ens.get('statistics', ()) if statistics is None else statistics
+    statistics_vars = ens.get('statistics_vars') if statistics_vars is None else statistics_vars
+    member_outputs = ens.get('member_outputs', 1) if member_outputs is None else member_outputs
+    plan = validate(s, members, statistics, statistics_vars, member_outputs)
+    ctx = _hip.get_context(s.device)                      # HipUnavailable without a device: there is no host fallback
+    check_fits(plan, ctx.mem_info()[0])
+    return _Driver(s, plan, ctx, overlap).run()
+
+
+class _Driver:
+    def __init__(self, s, plan, ctx, overlap):
+        self.s, self.plan, self.ctx, self.overlap = s, plan, ctx, bool(overlap)
+        n = len(plan.names)
+        self.timings = {k: [0.0] * n for k in ('upload', 'kernels', 'post', 'write')}
+        self.member_dirs = [os.path.join(s.OutputFolder, name) for name in plan.names]
+        self.settings = []
+        for k in range(n):
+            cfg = copy.copy(s)
+            for key, value in plan.overrides[k].items():
+                setattr(cfg, key, value)
+            cfg.OutputFolder = self.member_dirs[k]
+            self.settings.append(cfg)
+        self.stack = {v: [] for v in plan.statistics_vars}
+        self.up = self.wr = None
+
+    # ---- set-up: everything static, once
+    def setup(self):
+        s, ctx = self.s, self.ctx
+        runner = ConfigRunner(s)
+        self.c = c = Components(s)
+        self.runoff = s.runoff_module if runner.run_runoff else 'none'
+        c.check_resident(self.runoff)
+        um = c.topology() if (runner.run_routing and s.routing_module == 'mrtm') else None
+        self.pipe = pipe = DevicePipeline(ctx, **c._pipeline_args(self.runoff, um))
+        pipe.plan                                         # the one routing plan of all members (waits for the partition)
+        shape = (pipe.ncell, pipe.nmonths)
+        if not self.overlap:
+            self.up = self.wr = ctx
+            self.sets = [(pipe.forcing, pipe.out)]
+            return
+        # two buffer sets: the forcing belongs to the uploading context, the outputs to the writing one (a DeviceArray's
+        # copies run on the context that made it, and a context serves one host thread); the kernels only take pointers
+        self.up, self.wr = _hip.Context(ctx.device), _hip.Context(ctx.device)
+        for a in pipe.out.values():
+            a.free()
+        self.sets = []
+        for _ in range(2):
+            out = {k: self.wr.empty(shape) for k in OUTPUTS}
+            if self.runoff == 'none':
+                for k in ('aet', 'q', 'sav'):
+                    out[k].zero()
+            self.sets.append(({}, out))
+        self.wr.sync()
+        pipe.forcing, pipe.out = self.sets[0]
+
+    def member_forcing(self, k):
+        """Host forcing of member k by DevicePipeline name: the member's own arrays / memory maps where it overrides a
+        setting (loaded as DataLoader loads them), the run's otherwise."""
+        s, cfg, data = self.s, self.settings[k], self.c.data
+        loader = copy.copy(data)
+        loader.s = cfg
+        host = {}
+        for module in (s.pet_module, self.runoff):
+            for name, attr in _FORCING_DATA[module].items():
+                setting, varkey, clean = _FORCING_SETTINGS[module][name]
+                if setting in self.plan.overrides[k]:
+                    try:
+                        host[name] = loader.load_to_array(getattr(cfg, setting), setting, nan_to_num=clean,
+                                                          key=getattr(cfg, varkey, None) if varkey else None)
+                    except ValidationException as exc:
+                        raise refuse(self.plan.names[k], setting, str(exc))
+                else:
+                    host[name] = getattr(data, attr, None)
+        return host
+
+    # ---- the three stages of a member
+    def upload(self, k, i):
+        t = time.time()
+        self.pipe.set_forcing(self.member_forcing(k), ctx=self.up, into=self.sets[i][0])
+        self.up.sync()
+        self.timings['upload'][k] = time.time() - t
+
+    def compute(self, k, i):
+        t = time.time()
+        pipe = self.pipe
+        pipe.forcing, pipe.out = self.sets[i]
+        pipe.run(fed=False, fused=False)                  # the stages strictly in order, as Components.simulation
+        self.ctx.sync()
+        self.timings['kernels'][k] = time.time() - t
+
+    def write(self, k, i):
+        if self.wr is not self.ctx:
+            with _hip.thread_context(self.wr):
+                self._write(k, i)
+        else:
+            self._write(k, i)
+
+    def _write(self, k, i):
+        plan, pipe, cfg = self.plan, self.pipe, self.settings[k]
+        view = SimpleNamespace(out=self.sets[i][1], plan=pipe.plan, ncell=pipe.ncell, nmonths=pipe.nmonths)
+        c = self.c.member_view(cfg, view)
+        logging.info("---ensemble member '{}' ({} of {})".format(plan.names[k], k + 1, len(plan.names)))
+        t = time.time()
+        if plan.member_outputs:                           # the phases of ConfigRunner.run() after the simulation, in its order
+            os.makedirs(cfg.OutputFolder, exist_ok=True)
+            c.accessible_water()
+            c.drought()
+            c.hydropower_potential()
+            c.hydropower_actual()
+            c.diagnostics()
+        self.timings['post'][k] = time.time() - t
+        t = time.time()
+        c.output_simulation(keep_device=bool(plan.statistics_vars), write_files=bool(plan.member_outputs))
+        if plan.member_outputs and cfg.CreateTimeSeriesPlot:
+            c.plots()
+        w = c._writer
+        for var in plan.statistics_vars:                  # the array as written joins the member stack in HBM
+            arr, owned = w.get_device(var)
+            if not owned:                                 # the run's own array: the next member of this set overwrites it
+                arr = w.ctx.d2d(w.ctx.empty(arr.shape), arr)
+            self.stack[var].append(arr)
+        for a in w.device_outputs.values():
+            a.free()
+        w.device_outputs = {}
+        w.ctx.sync()
+        self.timings['write'][k] = time.time() - t
+
+    # ---- the across-member statistics
+    def statistics(self):
+        from .data_writer.out_writer import FORMAT_NPY, OutWriter
+        plan, s, ctx = self.plan, self.s, self.ctx
+        result = {}
+        if not plan.statistics_vars:
+            return result
+        cfg = copy.copy(s)
+        cfg.OutputFolder = os.path.join(s.OutputFolder, STATISTICS_DIR)
+        w = OutWriter(cfg, self.c.data.area, {})
+        plain = [label for label in _hip.ENS_STAT_BITS if any(label == l for l, _ in plan.statistics)]      # the library's order
+        quant = [(label, q) for label, q in plan.statistics if q is not None]
+        for var in plan.statistics_vars:
+            members = self.stack[var]
+            shape = members[0].shape
+            outs = [ctx.empty(shape) for _ in range(len(plain) + len(quant))]
+            ctx.ens_stats(members[0].size, members, plain, [q for _, q in quant], outs)
+            ctx.sync()
+            for a in members:
+                a.free()
+            self.stack[var] = []
+            result[var] = _Lazy()
+            for label, arr in zip(plain + [label for label, _ in quant], outs):
+                filename = os.path.join(cfg.OutputFolder, '{}_{}_{}_{}'.format(var, w.unit_of(var), s.ProjectName, label))
+                if w.out_format != FORMAT_NPY:            # the csv writer takes host arrays
+                    host = arr.download()
+                    arr.free()
+                    arr = host
+                w.write_data(filename, var, arr, w.time_steps)
+                dict.__setitem__(result[var], label, arr)
+        return result
+
+    def run(self):
+        plan = self.plan
+        t0 = time.time()
+        logging.info('---ensemble of {} members in progress ({})...'.format(
+            len(plan.names), 'overlapped' if self.overlap else 'one after the other'))
+        try:
+            self.setup()
+            run_schedule(len(plan.names), self.upload, self.compute, self.write, overlap=self.overlap)
+            t = time.time()
+            stats = self.statistics()
+            self.timings['statistics'] = time.time() - t
+        finally:
+            for owned in self.stack.values():
+                for a in owned:
+                    a.free()
+            for extra in (self.up, self.wr):
+                if extra is not None and extra is not self.ctx:
+                    extra.close()
+        self.timings['total'] = time.time() - t0
+        n = max(len(plan.names), 1)
+        logging.info('ensemble phases (s per member): ' + ', '.join(
+            '{} {:.3f}'.format(k, sum(self.timings[k]) / n) for k in ('upload', 'kernels', 'post', 'write')) +
+            '; statistics {:.3f} s, total {:.3f} s'.format(self.timings['statistics'], self.timings['total']))
+        return EnsembleResult(list(plan.names), list(self.member_dirs) if plan.member_outputs else [], stats, self.timings)

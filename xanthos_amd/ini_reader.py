@@ -5,7 +5,7 @@ The reference parses the file with ``configobj`` (not installed here) and flatte
 ``[[subsection]]``, ``key = value``, ``#`` comments, comma lists, optional quotes) and builds the same attributes for
 the sections the hot path reads: ``[Project]``, ``[PET][[penman-monteith]]`` / ``[[hargreaves]]`` /
 ``[[hargreaves-samani]]`` / ``[[thornthwaite]]``,
-``[Runoff][[abcd]]`` / ``[[gwam]]``, ``[Routing][[mrtm]]``, ``[Calibrate]`` and the post-processors' sections.  Selector strings are lower-cased and validated exactly like the
+``[Runoff][[abcd]]`` / ``[[gwam]]``, ``[Routing][[mrtm]]``, ``[Calibrate]``, ``[Ensemble]`` and the post-processors' sections.  Selector strings are lower-cased and validated exactly like the
 reference (:214, :309, :397); selectors that belong to other reference modules are rejected with a clear message
 because only the MI355X hot path is implemented here.  ``update()`` keeps the in-memory override hook (:598-607).
 """
@@ -85,6 +85,33 @@ def check_calibration(s):
     if getattr(s, 'calibrate', 0) and getattr(s, 'set_calibrate', 0) == 1 and getattr(s, 'routing_module', None) != 'mrtm':
         raise ValidationException("[Calibrate] set_calibrate = 1 calibrates against routed streamflow and needs "
                                   "routing_module = mrtm, not '{}'.".format(getattr(s, 'routing_module', None)))
+
+
+# The settings that name forcing arrays, per PET / runoff module, and the attribute of the directory their ini value is
+# joined to (None: taken as written).  These are the settings an ensemble member may vary ([Ensemble], ensemble.py); a
+# cell of the members table is resolved by resolve_forcing_setting exactly as configure_pet / configure_runoff resolve
+# the same key of the ini.
+FORCING_SETTINGS = {
+    'pm': {k: 'pet_dir' for k in ('pm_tas', 'pm_tmin', 'pm_rhs', 'pm_wind', 'pm_rsds', 'pm_rlds')},
+    'hargreaves': {'TemperatureFile': 'pet_dir', 'DailyTemperatureRangeFile': 'pet_dir'},
+    'hs': {'hs_tas': 'pet_dir', 'hs_tmax': 'pet_dir', 'hs_tmin': 'pet_dir'},
+    'thornthwaite': {'trn_tas': 'pet_dir'},
+    'abcd': {'PrecipitationFile': None, 'TempMinFile': None},
+    'gwam': {'PrecipitationFile': 'ro_model_dir'},
+    'none': {},
+}
+ENSEMBLE_STATISTICS = ('mean', 'std', 'min', 'max')
+
+
+def parse_statistic(text):
+    """'mean' / 'std' / 'min' / 'max' -> (name, None); 'qNN' (NN an integer 0-100) -> ('qNN', NN / 100)."""
+    t = str(text).strip().lower()
+    if t in ENSEMBLE_STATISTICS:
+        return t, None
+    if t[:1] == 'q' and t[1:].isdigit() and 0 <= int(t[1:]) <= 100:
+        return 'q{}'.format(int(t[1:])), int(t[1:]) / 100.0
+    raise ValidationException("[Ensemble] statistics: '{}' is not one of mean, std, min, max or qNN with NN an integer "
+                              "from 0 to 100.".format(text))
 
 
 def _subsection(cfg, name, section):
@@ -178,6 +205,9 @@ class ConfigReader:
                 raise ValidationException('Calibrate = 1 but no [Calibrate] section.')
             self.configure_calibration(c['Calibrate'])
             check_calibration(self)
+        self.ensemble = None
+        if isinstance(c.get('Ensemble'), dict):
+            self.configure_ensemble(c['Ensemble'])
 
     # ------------------------------------------------------------------ modules
     def configure_pet(self, cfg):
@@ -538,6 +568,47 @@ class ConfigReader:
             self.cal_basins = ['1-{}'.format(self.n_basins)]
         else:
             self.cal_basins = basins if isinstance(basins, list) else [basins]
+
+    def forcing_settings(self):
+        """{setting: directory attribute or None} of the forcing arrays of the configured PET and runoff modules."""
+        out = dict(FORCING_SETTINGS.get(self.pet_module, {}))
+        out.update(FORCING_SETTINGS.get(self.runoff_module, {}))
+        return out
+
+    def resolve_forcing_setting(self, key, value):
+        """``value`` as the ini's ``key = value`` would be stored (a path joined to the module's directory, or as written)."""
+        where = self.forcing_settings()
+        if key not in where:
+            raise ValidationException("'{}' does not name a forcing array of pet_module = {} / runoff_module = {}.".format(
+                key, self.pet_module, self.runoff_module))
+        return value if where[key] is None else os.path.join(getattr(self, where[key]), value)
+
+    def configure_ensemble(self, cfg):
+        """[Ensemble] (not a section of the reference): members = <csv> (header ``name`` + forcing settings, one row per
+        member, an empty cell keeps the ini's value), statistics = mean, std, min, max, qNN (default: none),
+        statistics_vars (default: output_vars), member_outputs = 1 | 0.  Kept as ``self.ensemble``; model.run_model hands
+        a configuration that has it to ensemble.run_ensemble."""
+        if self.calibrate:
+            raise ValidationException('[Ensemble] and Calibrate = 1 ([Calibrate]) exclude each other: a calibration is '
+                                      'not a member run.')
+        if 'members' not in cfg:
+            raise ValidationException('members is required in the [Ensemble] section of the config file.')
+        path = cfg['members'] if isinstance(cfg['members'], str) else ','.join(cfg['members'])
+        path = path if os.path.isabs(path) else os.path.join(self.root, path)
+
+        def as_list(v):
+            return [] if v in (None, '') else ([x for x in v if x != ''] if isinstance(v, list) else [v])
+        stats = as_list(cfg.get('statistics'))
+        for t in stats:
+            parse_statistic(t)
+        try:
+            member_outputs = int(cfg.get('member_outputs', 1))
+        except (TypeError, ValueError):
+            member_outputs = -1
+        if member_outputs not in (0, 1):
+            raise ValidationException('[Ensemble] member_outputs = {!r} must be 0 or 1.'.format(cfg.get('member_outputs')))
+        self.ensemble = {'members': path, 'statistics': stats,
+                         'statistics_vars': as_list(cfg.get('statistics_vars')) or None, 'member_outputs': member_outputs}
 
     @staticmethod
     def ck_obs_unit(set_calib, unit):

@@ -40,6 +40,17 @@ class Xanthos:
         finally:
             self.cleanup()
 
+    def execute_ensemble(self, members=None, statistics=None, statistics_vars=None, member_outputs=None, overlap=True):
+        """Run ``members`` (a list of (name, overrides) pairs or of dicts with a ``name`` key; overrides as ``execute``
+        takes them; None: the [Ensemble] section's table) through one device-resident pass; see ``ensemble.py``.
+        Returns the EnsembleResult."""
+        from . import ensemble
+        self.stage({})
+        try:
+            return ensemble.run(self.config, members, statistics, statistics_vars, member_outputs, overlap)
+        finally:
+            self.cleanup()
+
     def cleanup(self):
         logging.info('End of {0}'.format(self.config.ProjectName))
         logger = logging.getLogger()
@@ -57,6 +68,23 @@ def check_single_device(config):
                                   'implemented.'.format(config.mod_cfg, config.pet_module, config.runoff_module))
 
 
+def run_ensemble(config_file, members=None, statistics=None, statistics_vars=None, member_outputs=None, overlap=True):
+    """An ensemble of forcing scenarios through the configuration's grid in one device-resident pass: static data stays
+    in HBM, the members stream through with their transfers and write-out overlapped, the across-member statistics are
+    formed on the device.  ``members`` / ``statistics`` / ``statistics_vars`` / ``member_outputs`` default to the ini's
+    [Ensemble] section; ``overlap=False`` runs the members strictly one after the other (same bits).  Member ``name`` is
+    written to <OutputFolder>/<name>/, the statistics to <OutputFolder>/ensemble/.  Returns an EnsembleResult."""
+    try:
+        return Xanthos(config_file).execute_ensemble(members, statistics, statistics_vars, member_outputs, overlap)
+    finally:
+        launch.close_group()
+
+
+def has_ensemble(config_file):
+    from .ini_reader import parse_ini
+    return isinstance(config_file, str) and isinstance(parse_ini(config_file).get('Ensemble'), dict)
+
+
 def run_model(config_file, gpus=None):
     """Run Xanthos from a configuration file (model.py:111-121).
 
@@ -66,6 +94,11 @@ def run_model(config_file, gpus=None):
     the files).  Under a launcher (RANK / WORLD_SIZE set) the call IS one rank."""
     if gpus is None and os.environ.get('XH_GPUS'):
         gpus = int(os.environ['XH_GPUS'])
+    if has_ensemble(config_file):          # an ini with an [Ensemble] section runs the ensemble driver (one GPU)
+        from . import ensemble
+        if gpus and int(gpus) > 1:
+            ensemble.validate(ConfigReader(config_file), [], gpus=gpus)      # refuses: members over several GPUs
+        return run_ensemble(config_file)
     if gpus and int(gpus) > 1 and 'RANK' not in os.environ and 'WORLD_SIZE' not in os.environ:
         check_single_device(ConfigReader(config_file))
         env = dict(os.environ)             # the rank processes import this very package, wherever the caller found it

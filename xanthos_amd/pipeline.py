@@ -150,12 +150,17 @@ class DevicePipeline:
                 self.forcing[k] = self.ctx.empty((self.ncell, self.nmonths))
         return self.forcing
 
-    def set_forcing(self, host, tairprev=None):
+    def set_forcing(self, host, tairprev=None, ctx=None, into=None):
         """host: dict of [ncell, nmonths] arrays keyed by the modules' forcing names (MODULE_FORCING; a missing or None
         entry is left as it is, e.g. abcd_tmin when use_snow is False).  A read-only memory map of a .npy
         (np.load(mmap_mode='r'), what DataLoader keeps) is copied straight out of the mapping (no host copy: the runtime
         pins the page-cache pages); tairprev=None leaves PM's previous-cell temperature to the PM kernel (it reads the row
-        above of ``tas``, data_load.py:127-128)."""
+        above of ``tas``, data_load.py:127-128).
+        ``ctx`` / ``into``: another context of the same device and another set of forcing arrays (allocated by that
+        context): the ensemble driver uploads the next member on a second stream while this pipeline runs."""
+        own = ctx is None and into is None
+        ctx = self.ctx if ctx is None else ctx
+        forcing = self.forcing if into is None else into
         for k in self.forcing_names:
             src = host.get(k)
             if src is None:
@@ -166,15 +171,17 @@ class DevicePipeline:
             arr = src if where is not None else np.asarray(src, dtype=np.float64)
             if arr.shape != (self.ncell, self.nmonths):
                 raise ValueError('forcing {} has shape {}, expected {}'.format(k, arr.shape, (self.ncell, self.nmonths)))
-            if k not in self.forcing:
-                self.forcing[k] = self.ctx.empty((self.ncell, self.nmonths))
+            if k not in forcing:
+                forcing[k] = ctx.empty((self.ncell, self.nmonths))
             if where is not None:
-                self.ctx.upload_file(self.forcing[k], where[0], where[1], src.nbytes)
+                ctx.upload_file(forcing[k], where[0], where[1], src.nbytes)
             else:
-                self.forcing[k].upload(arr)
+                forcing[k].upload(arr)
             if k in self._nan_to_num:
-                self.ctx.nan_to_num(self.forcing[k])
+                ctx.nan_to_num(forcing[k])
         if tairprev is not None:
+            if not own:
+                raise ValueError('tairprev belongs to the pipeline: set it without ctx / into')
             self.d_tairprev = self.ctx.nan_to_num(self.ctx.upload(tairprev))
 
     # ---- stages (asynchronous; call ctx.sync() or download to wait)

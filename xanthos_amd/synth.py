@@ -397,6 +397,48 @@ flow_direction = flow_dir.npy
     return ini
 
 
+def write_ensemble_example(root, world, forcings, start_year, end_year, names=None, statistics=(), statistics_vars=None,
+                           member_outputs=1, section=True, output_unit=0, **kw):
+    """``write_example`` of ``forcings[0]`` plus one forcing set per member under input/ensemble/<name>/ and the
+    members table input/ensemble/members.csv (PM's files relative to the PET directory, as the ini names them; ABCD's
+    two as full paths, as the ini does).  ``section``: an [Ensemble] section naming the table, ``statistics``,
+    ``statistics_vars`` and ``member_outputs`` is appended to the ini; ``output_unit``: OutputUnit of the ini.
+    Returns (ini path, [(name, {setting: full path})]) -- the second is what ``run_ensemble(ini, members=...)`` takes."""
+    import os
+    ini = write_example(root, world, forcings[0], start_year, end_year, **kw)
+    names = ['m{:02d}'.format(k) for k in range(len(forcings))] if names is None else list(names)
+    ens = os.path.join(root, 'input', 'ensemble')
+    pet_dir = os.path.join(root, 'input', 'pet', 'penman_monteith')
+    pm = {'pm_tas': 'tas', 'pm_tmin': 'tmin', 'pm_rhs': 'rhs', 'pm_wind': 'wind', 'pm_rsds': 'rsds', 'pm_rlds': 'rlds'}
+    ro = {'PrecipitationFile': 'precip', 'TempMinFile': 'abcd_tmin'}
+    members, rows = [], ['name,' + ','.join(list(pm) + list(ro))]
+    for name, f in zip(names, forcings):
+        d = os.path.join(ens, name)
+        os.makedirs(d, exist_ok=True)
+        paths = {}
+        for setting, key in list(pm.items()) + list(ro.items()):
+            paths[setting] = os.path.join(d, key + '.npy')
+            np.save(paths[setting], f[key])
+        members.append((name, paths))
+        rows.append(','.join([name] + [os.path.relpath(paths[k], pet_dir) for k in pm] + [paths[k] for k in ro]))
+    table = os.path.join(ens, 'members.csv')
+    with open(table, 'w') as fh:
+        fh.write('\n'.join(rows) + '\n')
+    text = open(ini).read()
+    if output_unit:
+        text = text.replace('OutputUnit = 0', 'OutputUnit = {}'.format(int(output_unit)))
+    if section:
+        text += '\n[Ensemble]\nmembers = {}\n'.format(table)
+        if statistics:
+            text += 'statistics = {}\n'.format(', '.join(statistics))
+        if statistics_vars:
+            text += 'statistics_vars = {}\n'.format(', '.join(statistics_vars))
+        text += 'member_outputs = {}\n'.format(int(member_outputs))
+    with open(ini, 'w') as fh:
+        fh.write(text)
+    return ini, members
+
+
 def hgm_forcing(world, forcing):
     """Hargreaves inputs from a ``make_forcing`` set: temperature = tas, daily temperature range = tas - tmin."""
     return {'temp': forcing['tas'], 'dtr': forcing['tas'] - forcing['tmin'], 'precip': forcing['precip'],
