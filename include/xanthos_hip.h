@@ -73,6 +73,30 @@ int xh_download_file(xh_ctx *ctx, const void *d_src, const char *path, uint64_t 
 /* Several device arrays to several files at once (n <= 16), one writer thread per file: the output variables of one run. */
 int xh_download_files(xh_ctx *ctx, int n, const void *const *d_srcs, const char *const *paths, const uint64_t *offsets,
                       const size_t *bytes);
+/* Csv text from HBM: the csv branch of data_writer/out_writer.py (out_writer.py:187-194, the reference's
+ * df.to_csv(..., index_label='id')) without the doubles crossing PCIe.  d_arr is [nrows, ncols] row-major; a line is
+ * str(first_id + r) + ',' + ','.join(fields) + '\n', a field Python's repr(float) -- the shortest digits that read back as
+ * the same double, fixed notation for decimal exponents -4 .. 15, d[.ddd]e+XX otherwise -- and NaN the empty field, byte
+ * for byte what the host loop writes.  first_id >= 0.
+ * xh_csv_format replaces the formatting loop alone: the text into d_text (16-byte aligned, `cap` bytes; XH_ERR_LIMIT and
+ * nothing written when the text is longer), the offset of every line and the total length into d_row_offsets[nrows + 1].
+ * It waits for the lengths; the text is enqueued on the context's stream. */
+int xh_csv_format(xh_ctx *ctx, const double *d_arr, int64_t nrows, int64_t ncols, int64_t first_id, char *d_text, size_t cap,
+                  int64_t *d_row_offsets);
+/* xh_csv_write replaces the loop and its fh.write (out_writer.py:189-194): the text goes to `path` from byte `offset` on
+ * (the caller has written the header line; the file is created when missing, never truncated, as with xh_download_file),
+ * in chunks of whole lines of at most chunk_bytes of text (0: the transfer slot's size, which also is the most; a longer
+ * line goes alone) -- chunk k + 1 is formatted while chunk k crosses PCIe into the page-locked slots of
+ * xh_download_file and chunk k - 1 is in write().  *bytes_written (may be NULL) receives the length of the text.  Waits
+ * for earlier work of the context, returns when the file is complete.  XH_ERR_ARG on file errors (xh_last_error has
+ * errno's text), XH_ERR_LIMIT for a line longer than a transfer slot. */
+int xh_csv_write(xh_ctx *ctx, const double *d_arr, int64_t nrows, int64_t ncols, int64_t first_id, const char *path,
+                 uint64_t offset, size_t chunk_bytes, uint64_t *bytes_written);
+/* Several arrays to several files at once (n <= 16), one writer thread per file as in xh_download_files: the variables of
+ * one OutWriter.write() (out_writer.py:81-125 calls write_data, :187-194, once per variable). */
+int xh_csv_write_many(xh_ctx *ctx, int n, const double *const *d_arrs, const int64_t *nrows, const int64_t *ncols,
+                      const int64_t *first_ids, const char *const *paths, const uint64_t *offsets, size_t chunk_bytes,
+                      uint64_t *bytes_written);
 int xh_memset(xh_ctx *ctx, void *d_ptr, int value, size_t bytes);
 int xh_sync(xh_ctx *ctx);
 /* Gather / scatter whole rows of a [nrows_total, ncols] device array by row index (shard packing, samples). */

@@ -115,6 +115,10 @@ SIGNATURES = {
     'xh_upload_file': (c_int, [_P, _P, c_char_p, ctypes.c_uint64, c_size_t, c_int]),
     'xh_download_file': (c_int, [_P, _P, c_char_p, ctypes.c_uint64, c_size_t, c_int]),
     'xh_download_files': (c_int, [_P, c_int, POINTER(c_void_p), POINTER(c_char_p), POINTER(ctypes.c_uint64), POINTER(c_size_t)]),
+    'xh_csv_format': (c_int, [_P, _P, c_int64, c_int64, c_int64, _P, c_size_t, _P]),
+    'xh_csv_write': (c_int, [_P, _P, c_int64, c_int64, c_int64, c_char_p, ctypes.c_uint64, c_size_t, POINTER(ctypes.c_uint64)]),
+    'xh_csv_write_many': (c_int, [_P, c_int, POINTER(c_void_p), POINTER(c_int64), POINTER(c_int64), POINTER(c_int64),
+                                  POINTER(c_char_p), POINTER(ctypes.c_uint64), c_size_t, POINTER(ctypes.c_uint64)]),
     'xh_memset': (c_int, [_P, _P, c_int, c_size_t]),
     'xh_sync': (c_int, [_P]),
     'xh_gather_rows': (c_int, [_P, _P, _P, c_int64, c_int64, _P]),
@@ -422,6 +426,46 @@ class Context:
             offs = (ctypes.c_uint64 * n)(*offsets)
             sizes = (c_size_t * n)(*[src.nbytes for _, src in part])
             self._check(lib().xh_download_files(self.handle, n, srcs, paths, offs, sizes))
+
+    def csv_format(self, src, first_id=1, cap=None):
+        """The csv lines of DeviceArray ``src`` [nrows, ncols] formatted in HBM (xh_csv_format), downloaded for inspection:
+        (text as bytes, int64 offsets [nrows + 1] of the lines).  ``cap``: bytes of the text buffer (default: the most
+        the shape can take)."""
+        nrows, ncols = src.shape
+        if cap is None:
+            cap = nrows * (ncols * 25 + 21)
+        text, offs = self.empty((max(int(cap), 1),), dtype=np.uint8), self.empty((nrows + 1,), dtype=np.int64)
+        try:
+            self._check(lib().xh_csv_format(self.handle, _dptr(src), nrows, ncols, int(first_id), _dptr(text), int(cap),
+                                            _dptr(offs)))
+            offsets = offs.download()
+            return text.download()[:int(offsets[-1])].tobytes(), offsets
+        finally:
+            text.free()
+            offs.free()
+
+    def csv_write(self, path, src, first_id=1, offset=0, chunk_bytes=0):
+        """The csv lines of DeviceArray ``src`` -> bytes ``offset ...`` of file ``path`` (xh_csv_write); returns their
+        number.  The caller has written the header line."""
+        return self.csv_write_many([(path, src, first_id, offset)], chunk_bytes)[0]
+
+    def csv_write_many(self, items, chunk_bytes=0):
+        """[(path, DeviceArray, first_id, offset), ...] -> the csv lines of each array into its file, the files written
+        side by side (xh_csv_write_many, <= 16 per call); returns the bytes written per file."""
+        items, written = list(items), []
+        for k in range(0, len(items), 16):
+            part = items[k:k + 16]
+            n = len(part)
+            srcs = (c_void_p * n)(*[_dptr(src) for _, src, _, _ in part])
+            nrows = (c_int64 * n)(*[src.shape[0] for _, src, _, _ in part])
+            ncols = (c_int64 * n)(*[src.shape[1] for _, src, _, _ in part])
+            first = (c_int64 * n)(*[int(f) for _, _, f, _ in part])
+            paths = (c_char_p * n)(*[os.fsencode(path) for path, _, _, _ in part])
+            offs = (ctypes.c_uint64 * n)(*[int(o) for _, _, _, o in part])
+            out = (ctypes.c_uint64 * n)()
+            self._check(lib().xh_csv_write_many(self.handle, n, srcs, nrows, ncols, first, paths, offs, int(chunk_bytes), out))
+            written += [int(v) for v in out]
+        return written
 
     def timing_reset(self):
         self._check(lib().xh_timing_reset(self.handle))

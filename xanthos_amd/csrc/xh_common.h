@@ -127,6 +127,11 @@ struct xh_ctx {
     // call's routing kernel waited in vain for its months (serialised kernels, e.g. under a counter-collecting profiler)
     uint64_t runoff_seq = 0;
     bool feed_queue_ok = true, feed_disabled = false;
+    // xh_csv_* (xh_csv.hip): the digit generator's power-of-ten table (uploaded once per context) and the row offsets and
+    // text slots of the files being written (grow-only; the text crosses PCIe into io_ring)
+    void *csv_pow10 = nullptr;
+    void *csv_dev = nullptr;
+    size_t csv_dev_bytes = 0;
 };
 
 // Fault code of the routing kernel's plain units: an input outside the argument that lets them gather one value per term

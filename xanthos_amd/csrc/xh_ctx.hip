@@ -346,6 +346,8 @@ void xh_ctx_destroy(xh_ctx *ctx) {
     if (ctx->d_fault) (void)hipFree(ctx->d_fault);
     if (ctx->h_fault) (void)hipHostFree(ctx->h_fault);
     if (ctx->io_ring) (void)hipHostFree(ctx->io_ring);
+    if (ctx->csv_dev) (void)hipFree(ctx->csv_dev);
+    if (ctx->csv_pow10) (void)hipFree(ctx->csv_pow10);
     (void)hipStreamDestroy(ctx->stream);
     delete ctx;
 }

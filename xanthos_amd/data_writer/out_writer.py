@@ -7,7 +7,9 @@ Same constructor and methods as the reference class (:33-265): ``OutWriter(setti
 pandas' compensated order so that the values written equal the reference's bit for bit; only the (12x smaller
 for yearly output) results cross PCIe.  Files are written as ``.csv`` (OutputFormat 1, the reference's layout:
 an ``id`` column of 1-based cell ids and one column per time step) or ``.npy`` (4); NetCDF / MATLAB / parquet
-(0, 2, 3) need pandas writers outside the hot path and raise.
+(0, 2, 3) need pandas writers outside the hot path and raise.  The csv text of a table without names is formatted in
+HBM as well (csrc/xh_csv.hip: repr(float) per value, NaN the empty field) and only text crosses PCIe; the small tables
+with a ``name`` column (basin / country / region sums) are written by the host loop.
 """
 import logging
 import os
@@ -32,6 +34,7 @@ class OutWriter:
         # across-member statistics; write_files = False: the arrays are formed as written but no file is
         self.keep_device, self.write_files = False, True
         self.device_outputs = {}
+        self._npy_from_device = self._csv_from_device = None      # lists while write() collects the files it flushes together
         self.grid_areas = np.asarray(grid_areas, dtype=np.float64)
         self.conversion_mm_km3 = self.grid_areas / 1e6
         self.proj_name = settings.ProjectName
@@ -79,16 +82,17 @@ class OutWriter:
         """[ncell, nmonths] -> [ncell, nyears] (:237-248), optionally x scale[c] afterwards. Returns a host array."""
         return self._agg(arr, NMONTHS, 0 if func == 'sum' else 1, scale)
 
-    def _agg(self, arr, group, mode, scale, keep=None):
+    def _agg(self, arr, group, mode, scale, keep=None, on_device=False):
+        """on_device: the result stays in HBM and is returned as a DeviceArray (the csv writer formats it there)."""
         src, mine = self._on_device(arr)
         ncell, ncols = src.shape
         dst = self.ctx.empty((ncell, ncols // group))
         d_scale = None if scale is None else self.ctx.upload(scale)
         self.ctx.agg_time(ncell, ncols, group, mode, d_scale, src, dst)
-        out = dst.download()
+        out = dst if on_device else dst.download()
         if keep is not None and self.keep_device:
             self.device_outputs[keep], dst = dst, None
-        for b in (dst, d_scale, src if mine else None):
+        for b in (None if on_device else dst, d_scale, src if mine else None):
             if b is not None:
                 b.free()
         return out
@@ -118,18 +122,22 @@ class OutWriter:
             logging.debug('No valid output variables specified')
             return
         self._npy_from_device = []                      # monthly, unconverted npy outputs still in HBM: saved side by side
+        self._csv_from_device = []                      # csv outputs: formatted in HBM and written side by side
+        # csv: an aggregated / converted array stays in HBM for the formatter (get() fetches it on demand); with keep_device
+        # that array goes to the caller afterwards, so the host copy is made here as before
+        lazy = self.out_format == FORMAT_CSV and self.write_files and not self.keep_device
         for i, var in enumerate(self.output_names):
             flow = var == 'avgchflow'
             unit = 'm3persec' if flow else self.out_unit_str
             scale = self.conversion_mm_km3 if (self.out_unit == UNIT_KM3_MTH and not flow) else None
             if self.output_in_year:
-                self.outputs[i] = self._agg(self.inputs[var], NMONTHS, 1 if flow else 0, scale, keep=var)
+                self.outputs[i] = self._agg(self.inputs[var], NMONTHS, 1 if flow else 0, scale, keep=var, on_device=lazy)
             elif scale is not None:
-                self.outputs[i] = self._agg(self.inputs[var], 1, 0, scale, keep=var)
+                self.outputs[i] = self._agg(self.inputs[var], 1, 0, scale, keep=var, on_device=lazy)
             else:
                 a = self.inputs[var]
-                # a device array is saved from HBM (npy) or fetched for the csv writer
-                keep = isinstance(a, _hip.DeviceArray) and self.out_format == FORMAT_NPY
+                # a device array is saved (npy) or formatted (csv) from HBM
+                keep = isinstance(a, _hip.DeviceArray) and self.out_format in (FORMAT_NPY, FORMAT_CSV)
                 if not self.write_files:
                     self.outputs[i] = a
                     continue
@@ -137,10 +145,18 @@ class OutWriter:
             if not self.write_files:
                 continue
             filename = os.path.join(self.out_folder, '{}_{}_{}'.format(var, unit, self.proj_name))
-            self.write_data(filename, var, self.outputs[i], self.time_steps, first_id=1)
+            data = self.outputs[i]
+            if self.out_format == FORMAT_CSV:           # the array as written that is in HBM already, if any
+                data = self.device_outputs.get(var, data)
+            self.write_data(filename, var, data, self.time_steps, first_id=1)
         if self._npy_from_device:
             self.ctx.save_npy_many(self._npy_from_device)
-            self._npy_from_device = []
+        if self._csv_from_device:
+            self.ctx.csv_write_many([item for item, _ in self._csv_from_device])
+            for (_, dev, _, _), mine in self._csv_from_device:
+                if mine:
+                    dev.free()
+        self._npy_from_device = self._csv_from_device = None
 
     def write_aggregates(self, ref, values, basin, country, region):
         """Spatial sums of ``values`` (the written runoff) by basin / country / GCAM region (:126-158).
@@ -176,13 +192,25 @@ class OutWriter:
         os.makedirs(self.out_folder, exist_ok=True)
         if self.out_format == FORMAT_NPY:
             if isinstance(data, _hip.DeviceArray):
-                if getattr(self, '_npy_from_device', None) is not None and var in self.output_names:
+                if self._npy_from_device is not None and var in self.output_names:
                     self._npy_from_device.append((filename + '.npy', data))      # flushed at the end of write()
                 else:
                     self.ctx.save_npy(filename + '.npy', data)
             else:
                 np.save(filename + '.npy', data)
-        elif self.out_format == FORMAT_CSV:
+        elif self.out_format == FORMAT_CSV and names is None:
+            # the lines are formatted in HBM (xh_csv_write): header here, the text of the table behind it
+            dev, mine = self._on_device(data)
+            with open(filename + '.csv', 'w') as fh:
+                fh.write('id,' + ','.join(col_names[:dev.shape[1]]) + '\n')
+                item = (filename + '.csv', dev, first_id, fh.tell())
+            if self._csv_from_device is not None and var in self.output_names:
+                self._csv_from_device.append((item, mine))                       # flushed at the end of write()
+            else:
+                self.ctx.csv_write(*item)
+                if mine:
+                    dev.free()
+        elif self.out_format == FORMAT_CSV:             # a table with names (a few hundred rows): the host loop
             ids = np.arange(first_id, first_id + data.shape[0])
             header = 'id,' + ('name,' if names is not None else '') + ','.join(col_names[:data.shape[1]])
             fmt = lambda v: '' if v != v else repr(float(v))                    # pandas writes NaN as an empty field

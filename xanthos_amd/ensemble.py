@@ -409,7 +409,7 @@ class _Driver:
 
     # ---- the across-member statistics
     def statistics(self):
-        from .data_writer.out_writer import FORMAT_NPY, OutWriter
+        from .data_writer.out_writer import OutWriter
         plan, s, ctx = self.plan, self.s, self.ctx
         result = {}
         if not plan.statistics_vars:
@@ -431,11 +431,7 @@ class _Driver:
             result[var] = _Lazy()
             for label, arr in zip(plain + [label for label, _ in quant], outs):
                 filename = os.path.join(cfg.OutputFolder, '{}_{}_{}_{}'.format(var, w.unit_of(var), s.ProjectName, label))
-                if w.out_format != FORMAT_NPY:            # the csv writer takes host arrays
-                    host = arr.download()
-                    arr.free()
-                    arr = host
-                w.write_data(filename, var, arr, w.time_steps)
+                w.write_data(filename, var, arr, w.time_steps)      # npy and csv are written from HBM
                 dict.__setitem__(result[var], label, arr)
         return result
 
