@@ -43,7 +43,8 @@ __global__ void __launch_bounds__(LANES) __attribute__((amdgpu_waves_per_eu(2, 2
     const int p = A(unit_p)[unit];       // 0x400 | 1 (reads the inflow entry) | 2 (reads the chain entry)
     const bool has_ghost = A(ghost_edge)[(int64_t)unit * LANES + threadIdx.x] >= 0;      // lane k: the unit's k-th import
     const bool g = __any(has_ghost), g2 = __any(has_ghost && threadIdx.x >= 8);
-    const bool x = __any(A(export_edge)[(int64_t)unit * LANES + threadIdx.x] >= 0);
+    const int nxo = __popcll(__ballot(A(export_edge)[(int64_t)unit * LANES + threadIdx.x] >= 0));      // outlets of the unit
+    const bool x = nxo > 0;
     char *l = reinterpret_cast<char *>(lds);
     __attribute__((address_space(3))) unsigned *qst = (__attribute__((address_space(3))) unsigned *)qstage_sh;
     __attribute__((address_space(3))) double *fnd = (__attribute__((address_space(3))) double *)fend_sh;
@@ -54,11 +55,22 @@ __global__ void __launch_bounds__(LANES) __attribute__((amdgpu_waves_per_eu(2, 2
         return;
     }
     bool bad = false;
+    // Pair units know their rounds of 8 outlets at compile time (NXR: none, one; more than 8 outlets: the run-time form): looked
+    // up at run time, the outlet's LDS read and its store sit behind four branches per block of 8 sub-steps, which cost a lone
+    // wave 8 - 13 cycles per sub-step (profiles/pace/outlet_isa.txt, ab.txt).  The single units keep the run-time form: built
+    // the same way they failed the first call's cross-check (profiles/pace/ab.txt).
+#define XH_BY_OUTLETS(...)                                                                 \
+    do {                                                                                   \
+        if (nxo > 8) wave_unit<__VA_ARGS__, -1>(ap, l, xtab, qst, fnd, unit);              \
+        else if (x) wave_unit<__VA_ARGS__, 1>(ap, l, xtab, qst, fnd, unit);                \
+        else wave_unit<__VA_ARGS__, 0>(ap, l, xtab, qst, fnd, unit);                       \
+    } while (0)
     if (p & 16) {             // pair unit of a single-sum plan: the step of the plan of pairs + the exit guard
         if (!(p & 8) || (p & 4)) bad = true;
-        else if (g2) wave_unit<1, 0, 2, true, true, false, 2>(ap, l, xtab, qst, fnd, unit);
-        else if (g) wave_unit<1, 0, 1, true, true, false, 2>(ap, l, xtab, qst, fnd, unit);
-        else wave_unit<1, 0, 0, true, true, false, 2>(ap, l, xtab, qst, fnd, unit);
+        else if (g2) XH_BY_OUTLETS(1, 0, 2, true, true, false, 2);
+        else if (g) XH_BY_OUTLETS(1, 0, 1, true, true, false, 2);
+        else XH_BY_OUTLETS(1, 0, 0, true, true, false, 2);
+#undef XH_BY_OUTLETS
     } else if (p & 8) {      // single unit: one running sum, 8-byte entries
         if (p & 4) {          // (a unit that carries folded leaves has no imports: xh_flow_rsum.cpp)
             if (g || !A(fold_cell)) bad = true;

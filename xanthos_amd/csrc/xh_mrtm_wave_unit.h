@@ -202,7 +202,9 @@ template <> struct Val<true> {
 // it), initial storages and -- month by month -- lateral inflows are >= 0 up to a rounding error of the runoff model, and
 // the outflow of every exit lane (lane_flags bit 1: a cell in pair form whose downstream cell is not) stays >= -SGL_XEPS:
 // then every flow a single unit receives is >= 0, and its cells outside the marked set cannot fire.
-template <int PRE, int POST, int NG, bool CHAIN, bool RSUM = false, bool FOLD = false, int SGL = 0>
+// NXR (pair units): rounds of 8 outlets known at compile time (0, 1; -1: looked up at run time, as every other shape does):
+// the run-time form branches four times per block around the outlet's LDS read and its store.
+template <int PRE, int POST, int NG, bool CHAIN, bool RSUM = false, bool FOLD = false, int SGL = 0, int NXR = -1>
 __device__ __forceinline__ void wave_unit(WaveArgsK *ap, char *lds_generic, uint2 *xtab,
                                           __attribute__((address_space(3))) unsigned *qstage,
                                           __attribute__((address_space(3))) double *fend, const int unit) {
@@ -273,8 +275,9 @@ __device__ __forceinline__ void wave_unit(WaveArgsK *ap, char *lds_generic, uint
     const int gedge = A(ghost_edge)[slot];
     const bool has_x = xedge >= 0, has_g = gedge >= 0;
     const unsigned long long xmask = __ballot(has_x), gmask = __ballot(has_g);
-    const bool any_x = xmask != 0, any_g = HAS_G;
     const int nx_out = __popcll(xmask), ng = __popcll(gmask);       // outlets / imports of this unit
+    static_assert(NXR >= -1 && NXR <= 1, "outlet rounds known at compile time: none or one");
+    const bool any_x = NXR < 0 ? xmask != 0 : NXR > 0, any_g = HAS_G;
     const int lmax = A(unit_lmax)[unit], glmax = A(unit_glmax)[unit];
     const int lag_g = has_g ? A(ghost_lag)[slot] : 0;
     const unsigned *ready_p = A(ready) + (has_g ? gedge : 0);
@@ -293,7 +296,7 @@ __device__ __forceinline__ void wave_unit(WaveArgsK *ap, char *lds_generic, uint
     //      `oob`, which the buffer resource answers with zeros / drops, and writes ghost entry k, which no row refers to.
     if (has_x) xtab[__popcll(xmask & ((1ull << lane) - 1ull))] = make_uint2((unsigned)lane, (unsigned)xedge);
     const int sub = lane & 7, grp = lane >> 3;
-    const bool x2 = nx_out > 8;                          // a second round of outlet stores is needed (uniform)
+    const bool x2 = NXR < 0 && nx_out > 8;               // a second round of outlet stores is needed (uniform)
     unsigned gfull[SK_R], xbyte[SK_R];      // ring base | position of the next import block; ring base + 16 i for stores
     lds_mv *gdst[SK_R];
     lds_cv *xsrc[SK_R];
