@@ -97,6 +97,13 @@ int xh_csv_write(xh_ctx *ctx, const double *d_arr, int64_t nrows, int64_t ncols,
 int xh_csv_write_many(xh_ctx *ctx, int n, const double *const *d_arrs, const int64_t *nrows, const int64_t *ncols,
                       const int64_t *first_ids, const char *const *paths, const uint64_t *offsets, size_t chunk_bytes,
                       uint64_t *bytes_written);
+/* The body of a NetCDF-classic 'f4' variable from HBM: the reference's save_netcdf (out_writer.py:196-223) assigns the
+ * float64 array to an 'f4' variable, which scipy writes as numpy's a.astype('>f4').tobytes().  d_dst receives n IEEE
+ * binary32 values, most significant byte first, each d_src[i] rounded to nearest even: overflow gives +/-inf, binary32
+ * subnormals are kept, zero keeps its sign, the NaN 0x7ff8000000000000 becomes 0x7fc00000.  d_src 8-byte, d_dst 16-byte
+ * aligned (XH_ERR_ARG otherwise); enqueued on the context's stream, timer "pack_f32_be".  The caller writes the header
+ * and sends the 4 n bytes out with xh_download_files.  (MATLAB's column-major body is xh_transpose.) */
+int xh_pack_f32_be(xh_ctx *ctx, const double *d_src, int64_t n, void *d_dst);
 int xh_memset(xh_ctx *ctx, void *d_ptr, int value, size_t bytes);
 int xh_sync(xh_ctx *ctx);
 /* Gather / scatter whole rows of a [nrows_total, ncols] device array by row index (shard packing, samples). */
@@ -110,7 +117,7 @@ int xh_transpose(xh_ctx *ctx, const double *d_src, int64_t rows, int64_t cols, d
 /* HIP-event timing of the kernels each entry point launches, accumulated per kernel name on the context's stream.
  * Names: "pm_pet", "abcd_spinup", "abcd_basin_mean", "abcd_sim", "mrtm_route", "calib_abcd", "calib_kge", "calib_de",
  * "agg_time", "agg_spatial", "drought_thresh", "drought_stats", "hargreaves_pet", "gwam_spinup", "gwam_sim",
- * "hs_pet", "trn_daylight", "trn_pet", "diag_cell_total", "diag_group_sum", "ens_stats".  xh_timing_get waits for the stream, then
+ * "hs_pet", "trn_daylight", "trn_pet", "diag_cell_total", "diag_group_sum", "ens_stats", "pack_f32_be".  xh_timing_get waits for the stream, then
  * returns total milliseconds and launch count. */
 int xh_timing_reset(xh_ctx *ctx);
 /* a caller-named span on the context's stream, read back with xh_timing_get like the library's own timers (one open

@@ -119,6 +119,7 @@ SIGNATURES = {
     'xh_csv_write': (c_int, [_P, _P, c_int64, c_int64, c_int64, c_char_p, ctypes.c_uint64, c_size_t, POINTER(ctypes.c_uint64)]),
     'xh_csv_write_many': (c_int, [_P, c_int, POINTER(c_void_p), POINTER(c_int64), POINTER(c_int64), POINTER(c_int64),
                                   POINTER(c_char_p), POINTER(ctypes.c_uint64), c_size_t, POINTER(ctypes.c_uint64)]),
+    'xh_pack_f32_be': (c_int, [_P, _P, c_int64, _P]),
     'xh_memset': (c_int, [_P, _P, c_int, c_size_t]),
     'xh_sync': (c_int, [_P]),
     'xh_gather_rows': (c_int, [_P, _P, _P, c_int64, c_int64, _P]),
@@ -426,6 +427,49 @@ class Context:
             offs = (ctypes.c_uint64 * n)(*offsets)
             sizes = (c_size_t * n)(*[src.nbytes for _, src in part])
             self._check(lib().xh_download_files(self.handle, n, srcs, paths, offs, sizes))
+
+    def pack_f32_be(self, src, n, dst):
+        """``n`` doubles at ``src`` -> ``n`` big-endian binary32 values at ``dst`` (xh_pack_f32_be: numpy's
+        astype('>f4')), enqueued.  ``src`` / ``dst``: DeviceArrays or raw device addresses (a row slice); the source
+        8-byte, the destination 16-byte aligned."""
+        self._check(lib().xh_pack_f32_be(self.handle, _dptr(src), int(n), _dptr(dst)))
+
+    def _save_bodies(self, items, nbytes_of, form):
+        """[(path, header bytes, DeviceArray [nrows, ncols]), ...] -> files of header + body, <= 16 at a time: the headers
+        are written here, ``form(src, scratch)`` enqueues the body of ``nbytes_of(src)`` bytes into a scratch DeviceArray,
+        and the bodies leave side by side behind their headers (xh_download_files).  The scratch is freed after the flush."""
+        items = list(items)
+        for k in range(0, len(items), 16):
+            part, bodies = items[k:k + 16], []
+            try:
+                for path, header, src in part:
+                    if src.dtype != np.float64 or len(src.shape) != 2:
+                        raise ValueError('{}: a [nrows, ncols] float64 DeviceArray is expected'.format(path))
+                    with open(path, 'wb') as fh:
+                        fh.write(header)
+                    bodies.append(self.empty((max(nbytes_of(src), 1),), dtype=np.uint8))
+                    if src.size:
+                        form(src, bodies[-1])
+                n = len(part)
+                srcs = (c_void_p * n)(*[_dptr(b) for b in bodies])
+                paths = (c_char_p * n)(*[os.fsencode(path) for path, _, _ in part])
+                offs = (ctypes.c_uint64 * n)(*[len(header) for _, header, _ in part])
+                sizes = (c_size_t * n)(*[nbytes_of(src) for _, _, src in part])
+                self._check(lib().xh_download_files(self.handle, n, srcs, paths, offs, sizes))
+            finally:
+                for b in bodies:
+                    b.free()
+
+    def save_nc_many(self, items):
+        """[(path, header, DeviceArray), ...] -> NetCDF-classic files: ``header`` is data_writer.formats.nc_header(...) of
+        the array's shape, the body its values as big-endian binary32, row-major, packed in HBM (xh_pack_f32_be)."""
+        self._save_bodies(items, lambda src: src.size * 4, lambda src, body: self.pack_f32_be(src, src.size, body))
+
+    def save_mat_many(self, items):
+        """[(path, header, DeviceArray), ...] -> MAT-5 files: ``header`` is data_writer.formats.mat_header(...) of the
+        array's name and shape, the body its doubles column-major (xh_transpose in HBM)."""
+        self._save_bodies(items, lambda src: src.nbytes,
+                          lambda src, body: self.transpose(src, src.shape[0], src.shape[1], body))
 
     def csv_format(self, src, first_id=1, cap=None):
         """The csv lines of DeviceArray ``src`` [nrows, ncols] formatted in HBM (xh_csv_format), downloaded for inspection:

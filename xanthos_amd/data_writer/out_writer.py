@@ -6,10 +6,15 @@ Same constructor and methods as the reference class (:33-265): ``OutWriter(setti
 (:250-265) run as HIP kernels (csrc/xh_agg.hip, xh_diag.hip) on arrays that may already be resident in HBM, adding in
 pandas' compensated order so that the values written equal the reference's bit for bit; only the (12x smaller
 for yearly output) results cross PCIe.  Files are written as ``.csv`` (OutputFormat 1, the reference's layout:
-an ``id`` column of 1-based cell ids and one column per time step) or ``.npy`` (4); NetCDF / MATLAB / parquet
-(0, 2, 3) need pandas writers outside the hot path and raise.  The csv text of a table without names is formatted in
-HBM as well (csrc/xh_csv.hip: repr(float) per value, NaN the empty field) and only text crosses PCIe; the small tables
-with a ``name`` column (basin / country / region sums) are written by the host loop.
+an ``id`` column of 1-based cell ids and one column per time step), ``.npy`` (4), ``.nc`` (0: the NetCDF-classic file of
+the reference's ``save_netcdf``, one 'f4' variable ``data``) or ``.mat`` (2: ``scipy.io.savemat``'s MAT-5 file of the
+array); parquet (3) raises.  The csv text of a table without names is formatted in HBM as well (csrc/xh_csv.hip:
+repr(float) per value, NaN the empty field) and only text crosses PCIe; the small tables with a ``name`` column (basin /
+country / region sums) are written by the host loop.  NetCDF and MATLAB files are a header that depends on the shape and
+the names alone (formats.py, made here) and a body formed in HBM (csrc/xh_pack.hip: big-endian binary32; xh_transpose:
+column-major doubles) that leaves through the npy writer's path; the tables with names are cell arrays under MATLAB
+(``savemat`` on the host), and NetCDF cannot hold them -- the reference fails there, this writer refuses the combination
+when it is constructed.
 """
 import logging
 import os
@@ -17,6 +22,8 @@ import os
 import numpy as np
 
 from .. import _hip
+from ..ini_reader import ValidationException
+from . import formats
 
 FORMAT_NETCDF, FORMAT_CSV, FORMAT_MAT, FORMAT_PARQUET, FORMAT_NPY = 0, 1, 2, 3, 4
 UNIT_MM_MTH, UNIT_KM3_MTH = 0, 1
@@ -26,6 +33,15 @@ NMONTHS = 12
 class OutWriter:
 
     def __init__(self, settings, grid_areas, all_outputs, device=None):
+        # the reference's agg_spatial tables have a name column, which its save_netcdf cannot index (InvalidIndexError
+        # after the whole run): refused before anything is computed for the writer
+        aggregates = [k for k in ('AggregateRunoffBasin', 'AggregateRunoffCountry', 'AggregateRunoffGCAMRegion')
+                      if getattr(settings, k, 0)]
+        if settings.OutputFormat == FORMAT_NETCDF and aggregates:
+            raise ValidationException(
+                'OutputFormat = 0 (NetCDF) cannot hold the tables of {} = 1: they carry a name column, and the file has one '
+                'float variable; use OutputFormat 1 (csv) or 2 (MATLAB), or switch the aggregation off'.format(
+                    ' / '.join(aggregates)))
         self.output_names = [o for o in settings.output_vars if o in all_outputs.keys()]
         self.ctx = _hip.get_context(getattr(settings, 'device', 0) if device is None else device)
         self.inputs = {o: all_outputs[o] for o in self.output_names}           # host ndarray or DeviceArray
@@ -34,7 +50,8 @@ class OutWriter:
         # across-member statistics; write_files = False: the arrays are formed as written but no file is
         self.keep_device, self.write_files = False, True
         self.device_outputs = {}
-        self._npy_from_device = self._csv_from_device = None      # lists while write() collects the files it flushes together
+        # lists while write() collects the files it flushes together
+        self._npy_from_device = self._csv_from_device = self._bodies_from_device = None
         self.grid_areas = np.asarray(grid_areas, dtype=np.float64)
         self.conversion_mm_km3 = self.grid_areas / 1e6
         self.proj_name = settings.ProjectName
@@ -77,6 +94,9 @@ class OutWriter:
         if isinstance(arr, _hip.DeviceArray):
             return arr, False
         return self.ctx.upload(np.asarray(arr, dtype=np.float64)), True
+
+    def _save_bodies(self, items):
+        (self.ctx.save_nc_many if self.out_format == FORMAT_NETCDF else self.ctx.save_mat_many)(items)
 
     def agg_to_year(self, arr, func='sum', scale=None):
         """[ncell, nmonths] -> [ncell, nyears] (:237-248), optionally x scale[c] afterwards. Returns a host array."""
@@ -123,9 +143,11 @@ class OutWriter:
             return
         self._npy_from_device = []                      # monthly, unconverted npy outputs still in HBM: saved side by side
         self._csv_from_device = []                      # csv outputs: formatted in HBM and written side by side
+        self._bodies_from_device = []                   # NetCDF / MATLAB outputs: bodies formed in HBM, written side by side
         # csv: an aggregated / converted array stays in HBM for the formatter (get() fetches it on demand); with keep_device
         # that array goes to the caller afterwards, so the host copy is made here as before
-        lazy = self.out_format == FORMAT_CSV and self.write_files and not self.keep_device
+        # (NetCDF / MATLAB: the same, for the kernels that form the file's body)
+        lazy = self.out_format in (FORMAT_CSV, FORMAT_NETCDF, FORMAT_MAT) and self.write_files and not self.keep_device
         for i, var in enumerate(self.output_names):
             flow = var == 'avgchflow'
             unit = 'm3persec' if flow else self.out_unit_str
@@ -136,8 +158,8 @@ class OutWriter:
                 self.outputs[i] = self._agg(self.inputs[var], 1, 0, scale, keep=var, on_device=lazy)
             else:
                 a = self.inputs[var]
-                # a device array is saved (npy) or formatted (csv) from HBM
-                keep = isinstance(a, _hip.DeviceArray) and self.out_format in (FORMAT_NPY, FORMAT_CSV)
+                # a device array is saved (npy, NetCDF, MATLAB) or formatted (csv) from HBM
+                keep = isinstance(a, _hip.DeviceArray) and self.out_format != FORMAT_PARQUET
                 if not self.write_files:
                     self.outputs[i] = a
                     continue
@@ -146,7 +168,7 @@ class OutWriter:
                 continue
             filename = os.path.join(self.out_folder, '{}_{}_{}'.format(var, unit, self.proj_name))
             data = self.outputs[i]
-            if self.out_format == FORMAT_CSV:           # the array as written that is in HBM already, if any
+            if self.out_format in (FORMAT_CSV, FORMAT_NETCDF, FORMAT_MAT):      # the array as written that is in HBM already, if any
                 data = self.device_outputs.get(var, data)
             self.write_data(filename, var, data, self.time_steps, first_id=1)
         if self._npy_from_device:
@@ -156,7 +178,12 @@ class OutWriter:
             for (_, dev, _, _), mine in self._csv_from_device:
                 if mine:
                     dev.free()
-        self._npy_from_device = self._csv_from_device = None
+        if self._bodies_from_device:
+            self._save_bodies([item for item, _ in self._bodies_from_device])
+            for (_, _, dev), mine in self._bodies_from_device:
+                if mine:
+                    dev.free()
+        self._npy_from_device = self._csv_from_device = self._bodies_from_device = None
 
     def write_aggregates(self, ref, values, basin, country, region):
         """Spatial sums of ``values`` (the written runoff) by basin / country / GCAM region (:126-158).
@@ -219,6 +246,24 @@ class OutWriter:
                 for k, (i, row) in enumerate(zip(ids, data)):
                     label = '' if names is None else str(names[k]) + ','
                     fh.write(str(i) + ',' + label + ','.join(fmt(v) for v in row) + '\n')
+        elif self.out_format == FORMAT_MAT and names is not None:      # a table with names: a cell array, on the host
+            formats.save_mat_table(filename + '.mat', var, data, names)
+        elif self.out_format in (FORMAT_NETCDF, FORMAT_MAT):
+            # the header here, the body formed in HBM behind it (xh_pack_f32_be / xh_transpose)
+            nc = self.out_format == FORMAT_NETCDF
+            if names is not None:
+                raise ValidationException('OutputFormat = 0 (NetCDF) cannot hold table {} with its name column'.format(var))
+            nrows, ncols = data.shape
+            header = (formats.nc_header(nrows, ncols, self.output_in_year, self.out_unit_str, var) if nc else
+                      formats.mat_header(var, nrows, ncols))
+            dev, mine = self._on_device(data)
+            item = (filename + ('.nc' if nc else '.mat'), header, dev)
+            if self._bodies_from_device is not None and var in self.output_names:
+                self._bodies_from_device.append((item, mine))                    # flushed at the end of write()
+            else:
+                self._save_bodies([item])
+                if mine:
+                    dev.free()
         else:
-            raise RuntimeError('OutputFormat {} (NetCDF / MATLAB / parquet) is written by the reference\'s pandas '
-                               'writers, outside the MI355X hot path; use 1 (csv) or 4 (npy)'.format(self.out_format))
+            raise RuntimeError('OutputFormat 3 (parquet) is not written: the reference needs fastparquet for it; use 0 '
+                               '(NetCDF), 1 (csv), 2 (MATLAB) or 4 (npy)')
