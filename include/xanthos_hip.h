@@ -104,6 +104,19 @@ int xh_csv_write_many(xh_ctx *ctx, int n, const double *const *d_arrs, const int
  * aligned (XH_ERR_ARG otherwise); enqueued on the context's stream, timer "pack_f32_be".  The caller writes the header
  * and sends the 4 n bytes out with xh_download_files.  (MATLAB's column-major body is xh_transpose.) */
 int xh_pack_f32_be(xh_ctx *ctx, const double *d_src, int64_t n, void *d_dst);
+/* The reader's side of the same: forcing as it is stored -> native doubles, in HBM (the loader of data_load.py:342-390
+ * byte-swaps NetCDF variables and widens single precision on the host; here the stored bytes cross PCIe and are widened
+ * behind it).  d_dst receives numpy's a.astype(np.float64) of the n stored values at d_src: every non-NaN value exactly
+ * (binary32 subnormals widened, not flushed; the sign of zero and both infinities kept), NaN stays NaN, the quiet NaN
+ * 0x7fc00000 becomes 0x7ff8000000000000 (other payloads are only promised to stay NaN); XH_SRC_F64_BE is a byte swap and
+ * keeps every bit pattern.  n >= 0; the pointers may be NULL only when n == 0; d_src aligned to its element, d_dst to 8
+ * bytes.  XH_SRC_F64_BE may run in place (d_src == d_dst exactly); every other overlap of the two ranges, an unknown kind
+ * or a misaligned pointer is XH_ERR_ARG (xh_last_error says which) and nothing is launched.  Enqueued on the context's
+ * stream, timer "widen". */
+#define XH_SRC_F32_LE 1             /* native float32 (a .npy saved as '<f4')        */
+#define XH_SRC_F32_BE 2             /* NetCDF-classic `float`, numpy '>f4'            */
+#define XH_SRC_F64_BE 3             /* NetCDF-classic `double`, numpy '>f8': a swap   */
+int xh_widen(xh_ctx *ctx, const void *d_src, int kind, int64_t n, double *d_dst);
 int xh_memset(xh_ctx *ctx, void *d_ptr, int value, size_t bytes);
 int xh_sync(xh_ctx *ctx);
 /* Gather / scatter whole rows of a [nrows_total, ncols] device array by row index (shard packing, samples). */
@@ -117,7 +130,7 @@ int xh_transpose(xh_ctx *ctx, const double *d_src, int64_t rows, int64_t cols, d
 /* HIP-event timing of the kernels each entry point launches, accumulated per kernel name on the context's stream.
  * Names: "pm_pet", "abcd_spinup", "abcd_basin_mean", "abcd_sim", "mrtm_route", "calib_abcd", "calib_kge", "calib_de",
  * "agg_time", "agg_spatial", "drought_thresh", "drought_stats", "hargreaves_pet", "gwam_spinup", "gwam_sim",
- * "hs_pet", "trn_daylight", "trn_pet", "diag_cell_total", "diag_group_sum", "ens_stats", "pack_f32_be".  xh_timing_get waits for the stream, then
+ * "hs_pet", "trn_daylight", "trn_pet", "diag_cell_total", "diag_group_sum", "ens_stats", "pack_f32_be", "widen".  xh_timing_get waits for the stream, then
  * returns total milliseconds and launch count. */
 int xh_timing_reset(xh_ctx *ctx);
 /* a caller-named span on the context's stream, read back with xh_timing_get like the library's own timers (one open

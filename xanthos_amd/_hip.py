@@ -22,6 +22,10 @@ XH_ROUTE_REASSOC, XH_ROUTE_EXACT = 128, 256      # reassociated (tolerance) form
 XH_ROUTE_NO_PLAIN = 0x4000                       # (xh_common.h, what a guard trip re-routes with) pairs of sums in every unit: not the prepared plan
 XH_DAYLIGHT_REFERENCE, XH_DAYLIGHT_MONTHLY = 0, 1  # Thornthwaite's daylight order: the reference's repeat / every month its own
 XH_ERR_ARG, XH_ERR_HIP, XH_ERR_LIMIT, XH_ERR_DEVICE = 1, 2, 3, 4
+XH_SRC_F32_LE, XH_SRC_F32_BE, XH_SRC_F64_BE = 1, 2, 3          # xh_widen's kinds: how the source values are stored
+# dtype of a forcing array that may cross PCIe as stored -> (xh_widen kind, label of DevicePipeline.forcing_upload)
+NARROW_KINDS = {np.dtype('<f4'): (XH_SRC_F32_LE, 'f32'), np.dtype('>f4'): (XH_SRC_F32_BE, 'f32be'),
+                np.dtype('>f8'): (XH_SRC_F64_BE, 'f64be')}
 ENS_STAT_BITS = {'mean': 1, 'std': 2, 'min': 4, 'max': 8}       # XH_ENS_* of xh_ens_stats, in its output order
 
 
@@ -120,6 +124,7 @@ SIGNATURES = {
     'xh_csv_write_many': (c_int, [_P, c_int, POINTER(c_void_p), POINTER(c_int64), POINTER(c_int64), POINTER(c_int64),
                                   POINTER(c_char_p), POINTER(ctypes.c_uint64), c_size_t, POINTER(ctypes.c_uint64)]),
     'xh_pack_f32_be': (c_int, [_P, _P, c_int64, _P]),
+    'xh_widen': (c_int, [_P, _P, c_int, c_int64, _P]),
     'xh_memset': (c_int, [_P, _P, c_int, c_size_t]),
     'xh_sync': (c_int, [_P]),
     'xh_gather_rows': (c_int, [_P, _P, _P, c_int64, c_int64, _P]),
@@ -433,6 +438,12 @@ class Context:
         astype('>f4')), enqueued.  ``src`` / ``dst``: DeviceArrays or raw device addresses (a row slice); the source
         8-byte, the destination 16-byte aligned."""
         self._check(lib().xh_pack_f32_be(self.handle, _dptr(src), int(n), _dptr(dst)))
+
+    def widen(self, src, kind, n, dst):
+        """``n`` stored values at ``src`` (``kind``: XH_SRC_F32_LE / XH_SRC_F32_BE / XH_SRC_F64_BE) -> ``n`` native doubles
+        at ``dst`` (xh_widen: numpy's astype(np.float64)), enqueued.  ``src`` / ``dst``: DeviceArrays or raw device addresses
+        (a row slice); the source aligned to its element, the destination to 8 bytes; only XH_SRC_F64_BE may run in place."""
+        self._check(lib().xh_widen(self.handle, _dptr(src), int(kind), int(n), _dptr(dst)))
 
     def _save_bodies(self, items, nbytes_of, form):
         """[(path, header bytes, DeviceArray [nrows, ncols]), ...] -> files of header + body, <= 16 at a time: the headers

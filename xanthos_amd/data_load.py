@@ -14,6 +14,9 @@ changes its inputs:
 * Hargreaves-Samani: tas, tmin and tmax as loaded, NaN kept (:86-90); Thornthwaite: tas through nan_to_num (:137-138),
   on the device after upload unless ``device_transforms = False``
 * diagnostics: the four comparison tables as loaded (:216-220)
+* forcing stored as float32 or as a NetCDF-classic `float` / `double` variable stays AS STORED (a read-only map of the
+  file) when the run reads it only through ``DevicePipeline.set_forcing`` -- the stored bytes cross PCIe and ``xh_widen``
+  makes the doubles in HBM, exactly ``astype(float64)``; every other run gets float64 here (``DataLoader.keeps_stored``)
 * routing: flow distance < 1000 -> 1000 (:204-205), velocity < 0 -> 0 (:207-208), 2-D DRT maps flattened with the
   reference's ``vectorize`` (:415-425), zero initial channel storage in historic mode (:427-438)
 
@@ -30,7 +33,8 @@ from .ini_reader import ValidationException
 def load_file(fn, header_num=0, key=None, mmap=False):
     """.npy / .csv / .txt / .nc (NetCDF classic) / .mat reader, same dispatch as data_load.py:342-390.
     mmap: a .npy comes back as a read-only memory map (np.load(mmap_mode='r')): nothing is read until someone looks, and
-    the pipeline sends the file's bytes to the GPU itself (xh_upload_file)."""
+    the pipeline sends the file's bytes to the GPU itself (xh_upload_file).  So does a `float` or `double` variable of a
+    .nc that is one block of the file (nc_header.variable_range): a read-only map of its big-endian values, as stored."""
     if isinstance(fn, np.ndarray):
         return fn
     if not os.path.isfile(fn):
@@ -41,6 +45,11 @@ def load_file(fn, header_num=0, key=None, mmap=False):
         import scipy.io as sio
         return sio.loadmat(fn)[key]
     if fn.endswith('.nc'):
+        if mmap:
+            from .nc_header import variable_range
+            where = variable_range(fn, key)
+            if where is not None:
+                return np.memmap(fn, dtype=where[0], mode='r', offset=where[2], shape=where[1])
         import scipy.io as sio
         grp = sio.netcdf_file(fn, 'r', mmap=False)
         data = grp.variables[key][:].copy()
@@ -55,6 +64,15 @@ def load_file(fn, header_num=0, key=None, mmap=False):
         except ValueError:      # missing fields (the reference fills them with 0), ragged or non-numeric columns
             return np.genfromtxt(fn, delimiter=delim, skip_header=header_num, filling_values='0')
     raise RuntimeError('File {} has unrecognized extension'.format(fn))
+
+
+def stored_kind(arr):
+    """(xh_widen kind, label) of a forcing array that may cross PCIe as it is stored -- a C-contiguous 2-D ndarray or
+    memory map of float32, big-endian float32 or big-endian float64 -- or None."""
+    from ._hip import NARROW_KINDS
+    if isinstance(arr, np.ndarray) and arr.ndim == 2 and arr.flags.c_contiguous:
+        return NARROW_KINDS.get(arr.dtype)
+    return None
 
 
 def load_gauges(gauges_file, observed_file, nmonths, missing=None):
@@ -233,7 +251,7 @@ class DataLoader:
         """Previous-row air temperature (data_load.py:127-128: zeros_like, then rows 1.. = rows ..-1 of tair_load)."""
         if self._tairprev is None:
             self._tairprev = np.zeros(self.tair_load.shape)
-            self._tairprev[1:, :] = np.nan_to_num(self.tair_load[:-1, :])
+            self._tairprev[1:, :] = np.nan_to_num(np.asarray(self.tair_load[:-1, :], dtype=float))
         return self._tairprev
 
     @tairprev_load.setter
@@ -281,7 +299,12 @@ class DataLoader:
     def load_to_array(self, f, var_name, nan_to_num=False, key=None):
         # the big forcing files stay on disk as read-only memory maps (mmap_inputs = False restores host arrays)
         lazy = getattr(self.s, 'device_transforms', True) and getattr(self.s, 'mmap_inputs', True)
-        arr = np.asanyarray(load_file(f, key=key, mmap=lazy), dtype=float)      # a float64 memory map stays one
+        arr = load_file(f, key=key, mmap=lazy)
+        # single precision and NetCDF's big-endian values stay AS STORED when nothing but DevicePipeline.set_forcing will
+        # read them: their bytes cross PCIe and xh_widen makes the doubles in HBM (exact, so no result changes).  Every run
+        # that hands the forcing to host code gets float64 here as before -- host code would compute in single precision
+        if not (self.keeps_stored() and stored_kind(arr) is not None):
+            arr = np.asanyarray(arr, dtype=float)      # a float64 memory map stays one
         # np.nan_to_num of the big forcing arrays (data_load.py:120-125, :194-195) is applied on the device right after
         # the upload (xh_nan_to_num) unless device_transforms is switched off: a host pass over 2.6 GB costs seconds
         if nan_to_num and not getattr(self.s, 'device_transforms', True):
@@ -290,6 +313,18 @@ class DataLoader:
             raise ValidationException('Error: Inconsistent {0} data grid size. Expecting size: {1}. Received size: {2}'
                                       .format(var_name, (self.s.ncell, self.s.nmonths), arr.shape))
         return arr
+
+    def keeps_stored(self):
+        """Whether this run consumes its forcing only through DevicePipeline.set_forcing: a device-resident configuration
+        (components.runs_device_resident, the predicate of the ensemble) without calibration, with the device transforms
+        and the memory-mapped inputs on.  Stage-by-stage runs and the calibration read the arrays on the host."""
+        s = self.s
+        if not (getattr(s, 'device_transforms', True) and getattr(s, 'mmap_inputs', True)) or getattr(s, 'calibrate', 0):
+            return False
+        from .components import runs_device_resident
+        from .configurations import ConfigRunner
+        return runs_device_resident(s, getattr(s, 'pet_module', None) in ConfigRunner.PET_COMPONENTS,
+                                    getattr(s, 'runoff_module', None) in ConfigRunner.RUNOFF_COMPONENTS)
 
     def load_routing_data(self, fn, rep_val=None):
         """Per-cell vector from a 1-D array or a 2-D DRT map (data_load.py:392-413)."""

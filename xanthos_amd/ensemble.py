@@ -24,7 +24,7 @@ from types import SimpleNamespace
 
 import numpy as np
 
-from . import _hip, launch
+from . import _hip, launch, nc_header
 from .components import _FORCING_DATA, _FORCING_SETTINGS, Components, runs_device_resident
 from .configurations import ConfigRunner
 from .ini_reader import ValidationException, parse_statistic
@@ -80,14 +80,25 @@ def _normalise(members):
     return out
 
 
-def _shape_of(value):
-    """Shape of a forcing override without reading it (an ndarray, or the header of a .npy); None when only the loader can
-    tell (NetCDF, MATLAB, text)."""
+def _header_of(value, key=None):
+    """(shape, dtype as stored) of a forcing override without reading it: an ndarray, the header of a .npy, or the header of
+    a NetCDF-classic file whose variable ``key`` is one block of values (nc_header); (None, None) when only the loader can
+    tell (MATLAB, text, any other NetCDF)."""
     if isinstance(value, np.ndarray):
-        return value.shape
+        return value.shape, value.dtype
     if isinstance(value, str) and value.endswith('.npy'):
-        return np.load(value, mmap_mode='r').shape
-    return None
+        mm = np.load(value, mmap_mode='r')
+        return mm.shape, mm.dtype
+    if isinstance(value, str) and value.endswith('.nc'):
+        where = nc_header.variable_range(value, key)
+        if where is not None:
+            return where[1], where[0]
+    return None, None
+
+
+def _through_scratch(dtype):
+    """Whether an array stored as ``dtype`` passes through the uploading context's scratch (single precision, sent as stored)."""
+    return dtype is not None and dtype in _hip.NARROW_KINDS and dtype.itemsize == 4
 
 
 def written_vars(config):
@@ -110,6 +121,13 @@ def validate(config, members, statistics=(), statistics_vars=None, member_output
     if not members:
         raise refuse(None, 'members', 'no members')
     allowed = s.forcing_settings()
+    # setting that names a forcing file -> setting that names its NetCDF variable (None: the file format has no names)
+    varkeys = {setting: varkey for m in (s.pet_module, s.runoff_module) for setting, varkey, _ in _FORCING_SETTINGS[m].values()}
+    single = False                     # some member sends single-precision values: they pass through a scratch array in HBM
+    for setting, varkey in varkeys.items():      # (the run's own arrays, which the members share where they override nothing)
+        value = getattr(s, setting, None)
+        if isinstance(value, np.ndarray) or (isinstance(value, str) and os.path.isfile(value)):
+            single |= _through_scratch(_header_of(value, getattr(s, varkey, None) if varkey else None)[1])
     seen = set()
     for name, overrides in members:
         if not isinstance(name, str) or not name.strip():
@@ -130,10 +148,12 @@ def validate(config, members, statistics=(), statistics_vars=None, member_output
                 raise refuse(name, key, 'a path or an ndarray is expected, not {}'.format(type(value).__name__))
             if isinstance(value, str) and not os.path.isfile(value):
                 raise refuse(name, key, 'file {} does not exist'.format(value))
-            shape = _shape_of(value)
+            varkey = varkeys.get(key)
+            shape, stored = _header_of(value, getattr(s, varkey, None) if varkey else None)
             if shape is not None and tuple(shape) != (s.ncell, s.nmonths):
                 raise refuse(name, key, 'the forcing array has shape {}, expected [ncell, nmonths] = {}'.format(
                     tuple(shape), (s.ncell, s.nmonths)))
+            single |= _through_scratch(stored)
     stats, labels = [], set()
     for text in (statistics or ()):
         try:
@@ -162,6 +182,8 @@ def validate(config, members, statistics=(), statistics_vars=None, member_output
     nforcing = sum(len(_FORCING_DATA[m]) for m in (s.pet_module, s.runoff_module))
     # the member stack of every statistics variable, one variable's statistics, and the two buffer sets
     need = 8 * s.ncell * (ncols * (len(members) * len(statistics_vars) + len(stats)) + 2 * s.nmonths * (nforcing + len(OUTPUTS)))
+    if single:                         # the uploading context's scratch of one array as stored (pipeline._upload_stored)
+        need += 4 * s.ncell * s.nmonths
     return EnsemblePlan(names=[n for n, _ in members], overrides=[o for _, o in members], statistics=stats,
                         statistics_vars=statistics_vars, member_outputs=member_outputs, ncols=ncols, bytes_needed=need)
 
@@ -266,10 +288,12 @@ class _Lazy(dict):
 
 class EnsembleResult:
     """names, member_dirs, statistics[var][stat] (host arrays, fetched from HBM on first read), timings (seconds per
-    member: 'upload', 'kernels', 'post', 'write'; 'statistics' and 'total' for the run)."""
+    member: 'upload', 'kernels', 'post', 'write'; 'statistics' and 'total' for the run), forcing_upload (per member, what
+    DevicePipeline.set_forcing sent: {forcing name: (kind, bytes host -> device)})."""
 
-    def __init__(self, names, member_dirs, statistics, timings):
+    def __init__(self, names, member_dirs, statistics, timings, forcing_upload=None):
         self.names, self.member_dirs, self.statistics, self.timings = names, member_dirs, statistics, timings
+        self.forcing_upload = forcing_upload
 
 
 def run(config, members=None, statistics=None, statistics_vars=None, member_outputs=None, overlap=True):
@@ -294,6 +318,7 @@ class _Driver:
         self.s, self.plan, self.ctx, self.overlap = s, plan, ctx, bool(overlap)
         n = len(plan.names)
         self.timings = {k: [0.0] * n for k in ('upload', 'kernels', 'post', 'write')}
+        self.forcing_upload = [{} for _ in range(n)]
         self.member_dirs = [os.path.join(s.OutputFolder, name) for name in plan.names]
         self.settings = []
         for k in range(n):
@@ -361,6 +386,7 @@ class _Driver:
         self.pipe.set_forcing(self.member_forcing(k), ctx=self.up, into=self.sets[i][0])
         self.up.sync()
         self.timings['upload'][k] = time.time() - t
+        self.forcing_upload[k] = dict(self.pipe.forcing_upload)
 
     def compute(self, k, i):
         t = time.time()
@@ -450,6 +476,8 @@ class _Driver:
             for owned in self.stack.values():
                 for a in owned:
                     a.free()
+            if getattr(self, 'pipe', None) is not None:
+                self.pipe.close()
             for extra in (self.up, self.wr):
                 if extra is not None and extra is not self.ctx:
                     extra.close()
@@ -458,4 +486,5 @@ class _Driver:
         logging.info('ensemble phases (s per member): ' + ', '.join(
             '{} {:.3f}'.format(k, sum(self.timings[k]) / n) for k in ('upload', 'kernels', 'post', 'write')) +
             '; statistics {:.3f} s, total {:.3f} s'.format(self.timings['statistics'], self.timings['total']))
-        return EnsembleResult(list(plan.names), list(self.member_dirs) if plan.member_outputs else [], stats, self.timings)
+        return EnsembleResult(list(plan.names), list(self.member_dirs) if plan.member_outputs else [], stats, self.timings,
+                              self.forcing_upload)

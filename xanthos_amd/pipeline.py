@@ -10,6 +10,8 @@ import threading
 
 import numpy as np
 
+from ._hip import NARROW_KINDS
+from .data_load import stored_kind
 from .pet import hargreaves as hg_mod, hargreaves_samani as hs_mod, penman_monteith as pm_mod, thornthwaite as trn_mod
 from .routing import mrtm as mrtm_mod
 from .runoff import gwam as gwam_mod
@@ -28,12 +30,16 @@ FORCING = MODULE_FORCING['pm'] + MODULE_FORCING['abcd']
 OUTPUTS = ('pet', 'aet', 'q', 'sav', 'chs', 'avg')
 
 
-def file_range_of(arr):
+def file_range_of(arr, stored=False):
     """(path, byte offset) of the first element of a C-contiguous float64 np.memmap in its file, or None.  The position
     is taken from the addresses (the array's data pointer against the start of its mapping), not from ``arr.offset``,
-    which a slice of a memory map inherits unchanged from its parent."""
+    which a slice of a memory map inherits unchanged from its parent.  ``stored``: the maps that cross PCIe as they are
+    stored count as well (float32, big-endian float32 and float64: _hip.NARROW_KINDS)."""
     import mmap
-    if not (isinstance(arr, np.memmap) and arr.dtype == np.float64 and arr.dtype.isnative and arr.flags.c_contiguous
+    if not isinstance(arr, np.memmap):
+        return None
+    wanted = arr.dtype == np.float64 and arr.dtype.isnative
+    if not ((wanted or (stored and arr.dtype in NARROW_KINDS)) and arr.flags.c_contiguous
             and getattr(arr, 'filename', None) is not None and getattr(arr, '_mmap', None) is not None):
         return None
     base = np.frombuffer(arr._mmap, dtype=np.uint8)
@@ -68,6 +74,10 @@ class DevicePipeline:
         self.forcing_names = MODULE_FORCING[pet_module] + MODULE_FORCING[runoff_module]
         self._nan_to_num = NAN_TO_NUM.get(pet_module, ()) + NAN_TO_NUM.get(runoff_module, ())
         self.forcing = {}
+        # what set_forcing sent last, by forcing name: (kind, bytes host -> device), kind 'f64' for doubles sent as they are,
+        # 'f32' / 'f32be' / 'f64be' for values sent as stored and widened in HBM (xh_widen)
+        self.forcing_upload = {}
+        self._stored_scratch = {}          # uploading context -> its scratch DeviceArray for single-precision bytes
         self.d_tairprev = None
         self._setup_pet(pm_tables, lct, elev, lc_years, water_idx, snow_idx, lat_radians, lat_degrees, daylight)
         if runoff_module == 'abcd':
@@ -157,17 +167,30 @@ class DevicePipeline:
         pins the page-cache pages); tairprev=None leaves PM's previous-cell temperature to the PM kernel (it reads the row
         above of ``tas``, data_load.py:127-128).
         ``ctx`` / ``into``: another context of the same device and another set of forcing arrays (allocated by that
-        context): the ensemble driver uploads the next member on a second stream while this pipeline runs."""
+        context): the ensemble driver uploads the next member on a second stream while this pipeline runs.
+        A C-contiguous float32, big-endian float32 or big-endian float64 array of the right shape (what DataLoader keeps of
+        a single-precision .npy or a NetCDF variable) crosses PCIe as it is stored and becomes doubles in HBM (xh_widen):
+        exactly ``src.astype(np.float64)``.  ``forcing_upload`` records what was sent."""
         own = ctx is None and into is None
         ctx = self.ctx if ctx is None else ctx
         forcing = self.forcing if into is None else into
+        from_file = os.environ.get('XH_UPLOAD_FROM_FILE', '0') == '1'
         for k in self.forcing_names:
             src = host.get(k)
             if src is None:
                 continue
+            stored = stored_kind(src)
+            if stored is not None and src.shape == (self.ncell, self.nmonths):
+                if k not in forcing:
+                    forcing[k] = ctx.empty((self.ncell, self.nmonths))
+                self._upload_stored(ctx, src, stored, forcing[k], file_range_of(src, stored=True) if from_file else None)
+                self.forcing_upload[k] = (stored[1], src.nbytes)
+                if k in self._nan_to_num:
+                    ctx.nan_to_num(forcing[k])
+                continue
             # XH_UPLOAD_FROM_FILE=1: through xh_upload_file (maps the file range itself: 34 GB/s with its own map /
             # unmap per array); default: xh_memcpy_h2d out of numpy's mapping, which stays alive in the loader (51 GB/s)
-            where = file_range_of(src) if os.environ.get('XH_UPLOAD_FROM_FILE', '0') == '1' else None
+            where = file_range_of(src) if from_file else None
             arr = src if where is not None else np.asarray(src, dtype=np.float64)
             if arr.shape != (self.ncell, self.nmonths):
                 raise ValueError('forcing {} has shape {}, expected {}'.format(k, arr.shape, (self.ncell, self.nmonths)))
@@ -177,12 +200,46 @@ class DevicePipeline:
                 ctx.upload_file(forcing[k], where[0], where[1], src.nbytes)
             else:
                 forcing[k].upload(arr)
+            self.forcing_upload[k] = ('f64', forcing[k].nbytes)
             if k in self._nan_to_num:
                 ctx.nan_to_num(forcing[k])
         if tairprev is not None:
             if not own:
                 raise ValueError('tairprev belongs to the pipeline: set it without ctx / into')
             self.d_tairprev = self.ctx.nan_to_num(self.ctx.upload(tairprev))
+
+    def _upload_stored(self, ctx, src, stored, dst, where):
+        """``src`` (float32 / big-endian float32 / big-endian float64, as stored) -> the doubles of ``dst``: its bytes through
+        the movers (``where``: its file range, through xh_upload_file; otherwise out of the array or its mapping), then
+        xh_widen.  Single precision lands in the context's scratch first -- one per uploading context, kept until close():
+        the movers are enqueued on the context's stream and wait for it, so the next array's bytes arrive behind this
+        array's widen; big-endian float64 lands in ``dst`` and is swapped in place."""
+        kind, _ = stored
+        if src.dtype.itemsize == 8:
+            raw = dst
+        else:
+            raw = self._stored_scratch.get(ctx)
+            if raw is None or raw.ptr is None or raw.nbytes != src.nbytes:
+                if raw is not None:
+                    raw.free()
+                raw = self._stored_scratch[ctx] = ctx.empty((src.nbytes,), dtype=np.uint8)
+        if where is not None:
+            ctx.upload_file(raw, where[0], where[1], src.nbytes)
+        else:
+            raw.upload(src.view(raw.dtype))                   # the bytes as they are stored, whatever they mean
+        ctx.widen(raw, kind, src.size, dst)
+
+    def close(self):
+        """Release the scratch of the stored-forcing uploads (the arrays of the pipeline go with their contexts)."""
+        for a in self._stored_scratch.values():
+            a.free()
+        self._stored_scratch = {}
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
     # ---- stages (asynchronous; call ctx.sync() or download to wait)
     def run_pet(self):
