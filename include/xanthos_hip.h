@@ -498,6 +498,22 @@ int xh_diag_group_sum(xh_ctx *ctx, int64_t ncell, int32_t k, int32_t ngroups, co
 int xh_ens_stats(xh_ctx *ctx, int64_t n, int32_t nmembers, const double *const *h_d_members, uint32_t stat_mask,
                  int32_t nq, const double *h_q, double *const *h_d_out);
 
+/* ------------------------------------------------------------------ member skill
+ * xh_basin_kge: the Kling-Gupta distance of a run's runoff against observed basin runoff, per basin, on the Q of the run
+ * in HBM ([ncell, nmonths], mm per month, before any conversion of the writer).  The reference forms the same number inside
+ * its calibration only: the basin series of calibrate_abcd.py:156-162 -- np.nansum over the basin's cells of rsim * area *
+ * 1e-6 (km3_per_mth) or of rsim (mm_per_mth) -- and the distance of :196-213, ED = sqrt((r - 1)^2 + (sd_s / sd_o - 1)^2 +
+ * (mean_s / mean_o - 1)^2) with population standard deviations and np.corrcoef's r; KGE = 1 - ED.
+ * d_start [nbasins + 1] / d_cells: the cells of basin b, ascending, are d_cells[d_start[b] .. d_start[b + 1]); d_area
+ * [ncell] in km2, NULL for mm_per_mth; d_obs [nbasins, nmonths]; d_series [nbasins, nmonths] optional out (NULL: kept in
+ * the context's scratch); d_ed [nbasins] out.  The series is summed in cell order, a NaN term adding nothing; the moments
+ * run over the months in a fixed tree; no atomics: two calls give the same bits.  A constant series or record gives NaN,
+ * as numpy does.  XH_ERR_ARG: a NULL array other than d_area / d_series, nbasins <= 0 or > 65535, nmonths < 2, ncell < 1.
+ * Asynchronous on the context's stream; nothing is uploaded (the tables are the caller's, made once, in HBM).       */
+int xh_basin_kge(xh_ctx *ctx, int64_t ncell, int32_t nmonths, int32_t nbasins, const int64_t *d_start,
+                 const int32_t *d_cells, const double *d_q, const double *d_area, const double *d_obs, double *d_series,
+                 double *d_ed);
+
 /* The same objective for SEVERAL basins in one launch, each basin with its own population: one basin alone is only
  * months x ~1.7 us of dependent chain, far too little to fill the chip.  h_ncell [nbasins]; h_pars [nbasins, nmembers,
  * npar]; h_pet_t / h_precip_t / h_tmin_t / h_area: host arrays of nbasins DEVICE pointers ([nmonths, ncell_b] each;

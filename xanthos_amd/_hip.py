@@ -202,6 +202,7 @@ SIGNATURES = {
     'xh_diag_cell_total': (c_int, [_P, c_int64, c_int32, _P, c_double, _P, c_double, _P, c_int64]),
     'xh_diag_group_sum': (c_int, [_P, c_int64, c_int32, c_int32, _P, _P, _P, _P]),
     'xh_ens_stats': (c_int, [_P, c_int64, c_int32, POINTER(c_void_p), ctypes.c_uint32, c_int32, _P, POINTER(c_void_p)]),
+    'xh_basin_kge': (c_int, [_P, c_int64, c_int32, c_int32, _P, _P, _P, _P, _P, _P, _P]),
     'xh_synth_forcing': (c_int, [_P, c_uint64, c_double, c_int64, c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
 }
 
@@ -827,6 +828,14 @@ class Context:
         p_out = (c_void_p * max(nout, 1))(*[_dptr(o) for o in out])
         self._check(lib().xh_ens_stats(self.handle, int(n), nmem, p_mem, mask, q.size, _host_ptr(q) if q.size else None,
                                        p_out))
+
+    # ---- member skill (csrc/xh_skill.hip)
+    def basin_kge(self, ncell, nmonths, nbasins, start, cells, q, area, obs, ed, series=None):
+        """ED per basin of ``q`` [ncell, nmonths] against ``obs`` [nbasins, nmonths] (xh_basin_kge); all device arrays:
+        ``start`` int64 [nbasins + 1] into ``cells`` int32 (ascending per basin), ``area`` None for mm_per_mth, ``series``
+        an optional [nbasins, nmonths] output.  Asynchronous."""
+        self._check(lib().xh_basin_kge(self.handle, int(ncell), int(nmonths), int(nbasins), _dptr(start), _dptr(cells),
+                                       _dptr(q), _dptr(area), _dptr(obs), _dptr(series), _dptr(ed)))
 
     # ---- bench support
     def synth_forcing(self, seed, ncell, nmonths, lat, out, nan_frac=0.001, cell_ids=None):

@@ -1,4 +1,4 @@
-"""An ensemble of forcing scenarios through one grid in one device-resident pass.
+"""An ensemble of forcing scenarios and ABCD parameter sets through one grid in one device-resident pass.
 
 The reference's way to run S forcing sets is a Python loop of ``Xanthos.execute(args)``: every run reads the static inputs
 again, and the across-run statistics are formed afterwards on the host.  ``run_ensemble`` keeps one ``Components``, one
@@ -12,7 +12,12 @@ Member ``name`` is written to ``<OutputFolder>/<name>/`` with exactly the files
 go to ``<OutputFolder>/ensemble/<var>_<unit>_<ProjectName>_<stat>.<ext>`` through ``OutWriter.write_data``.
 
 Only the settings that name the forcing arrays of the configured PET / runoff modules may vary per member
-(``ConfigReader.forcing_settings``).  There is no host fallback: without a device the call raises ``HipUnavailable``.
+(``ConfigReader.forcing_settings``), and with ABCD the parameter table: ``abcd_pars``, an ndarray or .npy of the shape of the
+run's calib_file array -- the member then equals the single run with ``calib_file`` set to it.  When no member overrides a
+forcing setting the ensemble is *resident*: the forcing is uploaded once, PET is computed once, and a member is one ABCD and
+one routing pass.  With ``observed`` every member's Q is scored in HBM against observed basin runoff (``xh_basin_kge``, the
+reference's KGE): ``EnsembleResult.kge`` and ``<OutputFolder>/ensemble/member_kge.csv``.
+There is no host fallback: without a device the call raises ``HipUnavailable``.
 """
 import copy
 import csv
@@ -27,11 +32,15 @@ import numpy as np
 from . import _hip, launch, nc_header
 from .components import _FORCING_DATA, _FORCING_SETTINGS, Components, runs_device_resident
 from .configurations import ConfigRunner
+from .data_load import load_file
 from .ini_reader import ValidationException, parse_statistic
 from .pipeline import OUTPUTS, DevicePipeline
 
 MAX_MEMBERS_WITH_STATISTICS = 64        # xh_ens_stats' compiled limit
 STATISTICS_DIR = 'ensemble'
+PARS_KEY = 'abcd_pars'                  # a member's own [rows, 5] table of a, b, c, d, m (the shape of the run's calib_file array)
+KGE_TABLE = 'member_kge.csv'
+OBS_UNITS = ('km3_per_mth', 'mm_per_mth')
 # output variable -> result attribute (Components.output_simulation)
 _WRITTEN = ('pet', 'aet', 'q', 'soilmoisture', 'avgchflow')
 
@@ -44,7 +53,8 @@ def refuse(member, key, why):
 
 class EnsemblePlan(SimpleNamespace):
     """What validate() made of a request: names, overrides (one dict per member), statistics [(label, q or None)],
-    statistics_vars, member_outputs, ncols (columns of an array as written), bytes_needed."""
+    statistics_vars, member_outputs, ncols (columns of an array as written), bytes_needed, resident (no member overrides a
+    forcing setting: one upload, one PET), skill (None, or load_observed()'s basins / observations / cell lists)."""
 
 
 def read_members(config, path):
@@ -57,13 +67,19 @@ def read_members(config, path):
     if not rows or 'name' not in rows[0]:
         raise refuse(None, 'members', "{} needs a header row with a 'name' column".format(path))
     header, known = rows[0], config.forcing_settings()
+    pars_dir = getattr(config, 'ro_model_dir', None)      # abcd_pars resolves as calib_file does: against the runoff model directory
+
+    def resolve(k, v):
+        if k in known:
+            return config.resolve_forcing_setting(k, v)
+        if k == PARS_KEY and pars_dir is not None:
+            return os.path.join(pars_dir, v)
+        return v                                          # (kept as written: validate() refuses it with the member's name)
     members = []
     for r in rows[1:]:
         cells = dict(zip(header, r + [''] * (len(header) - len(r))))
         name = cells.pop('name')
-        # (a column that names no forcing setting is kept as written: validate() refuses it with the member's name)
-        members.append((name, {k: (config.resolve_forcing_setting(k, v) if k in known else v)
-                               for k, v in cells.items() if v != ''}))
+        members.append((name, {k: resolve(k, v) for k, v in cells.items() if v != ''}))
     return members
 
 
@@ -105,7 +121,80 @@ def written_vars(config):
     return [v for v in config.output_vars if v in _WRITTEN and (v != 'avgchflow' or config.routing_module == 'mrtm')]
 
 
-def validate(config, members, statistics=(), statistics_vars=None, member_outputs=1, gpus=None):
+def _table_header(value):
+    """(shape, dtype) of a parameter table: an ndarray, or a .npy by its header."""
+    if isinstance(value, np.ndarray):
+        return value.shape, value.dtype
+    mm = np.load(value, mmap_mode='r')
+    return mm.shape, mm.dtype
+
+
+def _check_pars(s, runs_runoff, name, value):
+    """The refusals of one member's ``abcd_pars``.  The values are not range-checked: the contract is the single run with
+    that table as calib_file."""
+    if s.runoff_module != 'abcd' or not runs_runoff:
+        raise refuse(name, PARS_KEY, 'the table of a, b, c, d, m belongs to runoff_module = abcd; the configuration {} runs '
+                     '{}'.format(s.mod_cfg, 'runoff_module = ' + s.runoff_module if runs_runoff else 'without runoff'))
+    if not isinstance(value, (str, np.ndarray)):
+        raise refuse(name, PARS_KEY, 'a path or an ndarray is expected, not {}'.format(type(value).__name__))
+    if isinstance(value, str) and not os.path.isfile(value):
+        raise refuse(name, PARS_KEY, 'file {} does not exist'.format(value))
+    try:
+        shape, dtype = _table_header(value)
+    except Exception as exc:
+        raise refuse(name, PARS_KEY, '{} is not a .npy array ({})'.format(value, exc))
+    try:
+        expected = tuple(_table_header(s.calib_file)[0])
+    except Exception:                  # (the run's own table cannot be read: the run itself says so)
+        expected = None
+    if expected is not None and tuple(shape) != expected:
+        raise refuse(name, PARS_KEY, "the table has shape {}, expected the shape of the run's calib_file, {}".format(
+            tuple(shape), expected))
+    if not np.can_cast(dtype, np.float64, 'same_kind'):
+        raise refuse(name, PARS_KEY, 'values of type {} do not cast to float64'.format(dtype))
+
+
+def load_observed(s, observed, obs_unit, runs_runoff=True):
+    """[Ensemble] observed / obs_unit -> what the skill of a member is formed against: the basins with a record
+    (ascending), their first nmonths observations [basins, nmonths] and their cells as xh_basin_kge takes them (``start``
+    into ``cells``, ascending per basin).  ``observed``: a file in the format of [Calibrate] observed -- rows [basin id, *,
+    *, value], months in order -- or such an ndarray [rows, 4]."""
+    if obs_unit not in OBS_UNITS:
+        raise refuse(None, 'obs_unit', "{} is not one of {}".format(
+            'it is required with observed' if obs_unit is None else "'{}'".format(obs_unit), ' / '.join(OBS_UNITS)))
+    if not runs_runoff or s.runoff_module not in ('abcd', 'gwam'):
+        raise refuse(None, 'observed', 'the skill is formed on the runoff Q, which the configuration {} does not compute'
+                     .format(s.mod_cfg))
+    if isinstance(observed, str):
+        if not os.path.isfile(observed):
+            raise refuse(None, 'observed', 'file {} does not exist'.format(observed))
+        table = np.asarray(load_file(observed, 0))
+    else:
+        table = np.asarray(observed)
+    if table.ndim != 2 or table.shape[1] < 4:
+        raise refuse(None, 'observed', 'rows of [basin id, *, *, value] are expected, not an array of shape {}'.format(table.shape))
+    table = np.asarray(table[:, [0, 3]], dtype=np.float64)         # (data_load.py:243)
+    if not np.isfinite(table[:, 0]).all():
+        raise refuse(None, 'observed', 'a basin id is NaN or infinite')
+    basin_of = np.asarray(load_file(s.BasinIDs, 1)).reshape(-1).astype(int)
+    basins = sorted({int(b) for b in table[:, 0]})
+    obs, start, cells = np.empty((len(basins), s.nmonths)), [0], []
+    for j, b in enumerate(basins):
+        mine = np.flatnonzero(basin_of == b)
+        if mine.size == 0:
+            raise refuse(None, 'observed', 'basin {} has a record but no cells on the grid'.format(b))
+        record = table[table[:, 0] == b, 1]
+        if record.size < s.nmonths:
+            raise refuse(None, 'observed', 'basin {} has {} months of observations, the run has nmonths = {}'.format(
+                b, record.size, s.nmonths))
+        obs[j] = record[:s.nmonths]
+        cells.append(mine)
+        start.append(start[-1] + mine.size)
+    return SimpleNamespace(basins=basins, obs=obs, unit=obs_unit, start=np.asarray(start, dtype=np.int64),
+                           cells=np.concatenate(cells).astype(np.int32))
+
+
+def validate(config, members, statistics=(), statistics_vars=None, member_outputs=1, gpus=None, observed=None, obs_unit=None):
     """Every refusal of an ensemble request, before any GPU work; returns the EnsemblePlan."""
     s = config
     if getattr(s, 'calibrate', 0):
@@ -139,9 +228,13 @@ def validate(config, members, statistics=(), statistics_vars=None, member_output
             raise refuse(name, 'name', 'duplicate member name')
         seen.add(name)
         for key, value in overrides.items():
+            if key == PARS_KEY:
+                _check_pars(s, runner.run_runoff, name, value)
+                continue
             if key not in allowed:
+                hint = " (a member's own ABCD parameter table goes in as {})".format(PARS_KEY) if key == 'calib_file' else ''
                 raise refuse(name, key, 'may not vary per member: only the forcing arrays of pet_module = {} / runoff_module = {} '
-                             'may ({})'.format(s.pet_module, s.runoff_module, ', '.join(sorted(allowed))))
+                             'may ({}){}'.format(s.pet_module, s.runoff_module, ', '.join(sorted(allowed)), hint))
             if getattr(s, key, None) is None:
                 raise refuse(name, key, 'the configuration runs without it (no {} in the ini): a member cannot switch it on'.format(key))
             if not isinstance(value, (str, np.ndarray)):
@@ -173,19 +266,25 @@ def validate(config, members, statistics=(), statistics_vars=None, member_output
     member_outputs = int(member_outputs)
     if member_outputs not in (0, 1):
         raise refuse(None, 'member_outputs', 'must be 0 or 1')
-    if not member_outputs and not (stats and statistics_vars):
+    skill = None if observed is None else load_observed(s, observed, obs_unit, runner.run_runoff)
+    if not member_outputs and not (stats and statistics_vars) and skill is None:      # (with observed: the table of KGE)
         raise refuse(None, 'member_outputs', 'member_outputs = 0 without statistics writes nothing')
     if stats and len(members) > MAX_MEMBERS_WITH_STATISTICS:
         raise refuse(None, 'statistics', '{} members exceed the {} the statistics kernel takes'.format(
             len(members), MAX_MEMBERS_WITH_STATISTICS))
     ncols = s.nmonths // 12 if s.OutputInYear else s.nmonths
     nforcing = sum(len(_FORCING_DATA[m]) for m in (s.pet_module, s.runoff_module))
-    # the member stack of every statistics variable, one variable's statistics, and the two buffer sets
-    need = 8 * s.ncell * (ncols * (len(members) * len(statistics_vars) + len(stats)) + 2 * s.nmonths * (nforcing + len(OUTPUTS)))
+    # resident: no member overrides a forcing setting -- the run's forcing goes up once and PET is computed once
+    resident = not any(key in allowed for _, overrides in members for key in overrides)
+    # the member stack of every statistics variable, one variable's statistics, and the two buffer sets (resident: one
+    # forcing set, and the two output sets share the one PET array)
+    arrays = nforcing + 2 * len(OUTPUTS) - 1 if resident else 2 * (nforcing + len(OUTPUTS))
+    need = 8 * s.ncell * (ncols * (len(members) * len(statistics_vars) + len(stats)) + s.nmonths * arrays)
     if single:                         # the uploading context's scratch of one array as stored (pipeline._upload_stored)
         need += 4 * s.ncell * s.nmonths
     return EnsemblePlan(names=[n for n, _ in members], overrides=[o for _, o in members], statistics=stats,
-                        statistics_vars=statistics_vars, member_outputs=member_outputs, ncols=ncols, bytes_needed=need)
+                        statistics_vars=statistics_vars, member_outputs=member_outputs, ncols=ncols, bytes_needed=need,
+                        resident=resident, skill=skill)
 
 
 def check_fits(plan, free_bytes):
@@ -289,14 +388,18 @@ class _Lazy(dict):
 class EnsembleResult:
     """names, member_dirs, statistics[var][stat] (host arrays, fetched from HBM on first read), timings (seconds per
     member: 'upload', 'kernels', 'post', 'write'; 'statistics' and 'total' for the run), forcing_upload (per member, what
-    DevicePipeline.set_forcing sent: {forcing name: (kind, bytes host -> device)})."""
+    DevicePipeline.set_forcing sent: {forcing name: (kind, bytes host -> device)}; a resident ensemble uploads once, the
+    other members' entries are empty), kge [members, basins] and kge_basins (ascending basin ids) with ``observed``: each
+    member's Kling-Gupta efficiency against the observed basin runoff, also in ensemble/member_kge.csv; None without."""
 
-    def __init__(self, names, member_dirs, statistics, timings, forcing_upload=None):
+    def __init__(self, names, member_dirs, statistics, timings, forcing_upload=None, kge=None, kge_basins=None):
         self.names, self.member_dirs, self.statistics, self.timings = names, member_dirs, statistics, timings
         self.forcing_upload = forcing_upload
+        self.kge, self.kge_basins = kge, kge_basins
 
 
-def run(config, members=None, statistics=None, statistics_vars=None, member_outputs=None, overlap=True):
+def run(config, members=None, statistics=None, statistics_vars=None, member_outputs=None, overlap=True, observed=None,
+        obs_unit=None):
     """The driver behind run_ensemble / Xanthos.execute_ensemble; ``config``: a staged ConfigReader."""
     s = config
     ens = getattr(s, 'ensemble', None) or {}
@@ -307,7 +410,9 @@ def run(config, members=None, statistics=None, statistics_vars=None, member_outp
     statistics = ens.get('statistics', ()) if statistics is None else statistics
     statistics_vars = ens.get('statistics_vars') if statistics_vars is None else statistics_vars
     member_outputs = ens.get('member_outputs', 1) if member_outputs is None else member_outputs
-    plan = validate(s, members, statistics, statistics_vars, member_outputs)
+    observed = ens.get('observed') if observed is None else observed
+    obs_unit = ens.get('obs_unit') if obs_unit is None else obs_unit
+    plan = validate(s, members, statistics, statistics_vars, member_outputs, observed=observed, obs_unit=obs_unit)
     ctx = _hip.get_context(s.device)                      # HipUnavailable without a device: there is no host fallback
     check_fits(plan, ctx.mem_info()[0])
     return _Driver(s, plan, ctx, overlap).run()
@@ -323,12 +428,14 @@ class _Driver:
         self.settings = []
         for k in range(n):
             cfg = copy.copy(s)
-            for key, value in plan.overrides[k].items():
-                setattr(cfg, key, value)
+            for key, value in plan.overrides[k].items():      # (a member's table is its run's calib_file)
+                setattr(cfg, 'calib_file' if key == PARS_KEY else key, value)
             cfg.OutputFolder = self.member_dirs[k]
             self.settings.append(cfg)
         self.stack = {v: [] for v in plan.statistics_vars}
         self.up = self.wr = None
+        self.member_pars = [None] * n                     # DeviceArray of a member's own parameter table
+        self.run_pars = self.skill = self.kge = None
 
     # ---- set-up: everything static, once
     def setup(self):
@@ -341,9 +448,18 @@ class _Driver:
         self.pipe = pipe = DevicePipeline(ctx, **c._pipeline_args(self.runoff, um))
         pipe.plan                                         # the one routing plan of all members (waits for the partition)
         shape = (pipe.ncell, pipe.nmonths)
+        if self.runoff == 'abcd':                         # the tables of all members, a few KB each
+            self.run_pars = pipe.d_pars
+            for k, overrides in enumerate(self.plan.overrides):
+                table = overrides.get(PARS_KEY)
+                if table is not None:
+                    table = table if isinstance(table, np.ndarray) else np.load(table)
+                    self.member_pars[k] = ctx.upload(np.asarray(table, dtype=np.float64))
+        resident = self.plan.resident
         if not self.overlap:
             self.up = self.wr = ctx
             self.sets = [(pipe.forcing, pipe.out)]
+            self.setup_skill()
             return
         # two buffer sets: the forcing belongs to the uploading context, the outputs to the writing one (a DeviceArray's
         # copies run on the context that made it, and a context serves one host thread); the kernels only take pointers
@@ -351,14 +467,30 @@ class _Driver:
         for a in pipe.out.values():
             a.free()
         self.sets = []
+        forcing = {}                                      # resident: both sets read the one forcing ...
         for _ in range(2):
-            out = {k: self.wr.empty(shape) for k in OUTPUTS}
+            out = {k: self.wr.empty(shape) for k in OUTPUTS if not (resident and self.sets and k == 'pet')}
+            if resident and self.sets:                    # ... and refer to the one PET (owned by the first set's entry)
+                out['pet'] = self.sets[0][1]['pet']
             if self.runoff == 'none':
                 for k in ('aet', 'q', 'sav'):
                     out[k].zero()
-            self.sets.append(({}, out))
+            self.sets.append((forcing if resident else {}, out))
         self.wr.sync()
         pipe.forcing, pipe.out = self.sets[0]
+        self.setup_skill()
+
+    def setup_skill(self):
+        """The tables of xh_basin_kge, once per ensemble, on the writing context: the skill is formed in the write stage."""
+        sk = self.plan.skill
+        if sk is None:
+            return
+        wr, n, nb = self.wr, len(self.plan.names), len(sk.basins)
+        self.skill = SimpleNamespace(
+            nbasins=nb, start=wr.upload(sk.start, dtype=np.int64), cells=wr.upload(sk.cells, dtype=np.int32),
+            obs=wr.upload(sk.obs), area=wr.upload(self.c.data.area) if sk.unit == 'km3_per_mth' else None,
+            series=wr.empty((nb, self.pipe.nmonths)), ed=wr.empty((n, nb)))
+        wr.sync()
 
     def member_forcing(self, k):
         """Host forcing of member k by DevicePipeline name: the member's own arrays / memory maps where it overrides a
@@ -382,6 +514,8 @@ class _Driver:
 
     # ---- the three stages of a member
     def upload(self, k, i):
+        if self.plan.resident and k > 0:                  # the forcing is up: nothing crosses PCIe for this member
+            return
         t = time.time()
         self.pipe.set_forcing(self.member_forcing(k), ctx=self.up, into=self.sets[i][0])
         self.up.sync()
@@ -392,7 +526,14 @@ class _Driver:
         t = time.time()
         pipe = self.pipe
         pipe.forcing, pipe.out = self.sets[i]
-        pipe.run(fed=False, fused=False)                  # the stages strictly in order, as Components.simulation
+        if self.run_pars is not None:                     # the member's own table, or the run's
+            pipe.d_pars = self.member_pars[k] if self.member_pars[k] is not None else self.run_pars
+        if self.plan.resident:                            # PET does not depend on the parameters: once, before the first member
+            if k == 0:
+                pipe.run_pet()
+            pipe.run(stages=(self.runoff,) + (('mrtm',) if pipe.um is not None else ()), fed=False, fused=False)
+        else:
+            pipe.run(fed=False, fused=False)              # the stages strictly in order, as Components.simulation
         self.ctx.sync()
         self.timings['kernels'][k] = time.time() - t
 
@@ -409,6 +550,10 @@ class _Driver:
         c = self.c.member_view(cfg, view)
         logging.info("---ensemble member '{}' ({} of {})".format(plan.names[k], k + 1, len(plan.names)))
         t = time.time()
+        sk = self.skill
+        if sk is not None:                                # ED of this member's Q, mm per month, into row k (asynchronous)
+            self.wr.basin_kge(pipe.ncell, pipe.nmonths, sk.nbasins, sk.start, sk.cells, self.sets[i][1]['q'], sk.area, sk.obs,
+                              sk.ed.ptr + 8 * k * sk.nbasins, series=sk.series)
         if plan.member_outputs:                           # the phases of ConfigRunner.run() after the simulation, in its order
             os.makedirs(cfg.OutputFolder, exist_ok=True)
             c.accessible_water()
@@ -418,6 +563,10 @@ class _Driver:
             c.diagnostics()
         self.timings['post'][k] = time.time() - t
         t = time.time()
+        if not (plan.member_outputs or plan.statistics_vars):      # (member_outputs = 0 with observed alone: only the skill)
+            self.wr.sync()
+            self.timings['write'][k] = time.time() - t
+            return
         c.output_simulation(keep_device=bool(plan.statistics_vars), write_files=bool(plan.member_outputs))
         if plan.member_outputs and cfg.CreateTimeSeriesPlot:
             c.plots()
@@ -431,6 +580,8 @@ class _Driver:
             a.free()
         w.device_outputs = {}
         w.ctx.sync()
+        if sk is not None and w.ctx is not self.wr:
+            self.wr.sync()
         self.timings['write'][k] = time.time() - t
 
     # ---- the across-member statistics
@@ -461,6 +612,19 @@ class _Driver:
                 dict.__setitem__(result[var], label, arr)
         return result
 
+    def member_skill(self):
+        """KGE = 1 - ED [members, basins] from HBM, and the table ensemble/member_kge.csv (written on the host)."""
+        sk, plan = self.skill, self.plan
+        if sk is None:
+            return
+        self.kge = 1.0 - sk.ed.download()
+        folder = os.path.join(self.s.OutputFolder, STATISTICS_DIR)
+        os.makedirs(folder, exist_ok=True)
+        with open(os.path.join(folder, KGE_TABLE), 'w') as fh:
+            fh.write('name,' + ','.join(str(b) for b in plan.skill.basins) + '\n')
+            for name, row in zip(plan.names, self.kge):
+                fh.write(name + ',' + ','.join(repr(float(v)) for v in row) + '\n')
+
     def run(self):
         plan = self.plan
         t0 = time.time()
@@ -469,12 +633,17 @@ class _Driver:
         try:
             self.setup()
             run_schedule(len(plan.names), self.upload, self.compute, self.write, overlap=self.overlap)
+            self.member_skill()
             t = time.time()
             stats = self.statistics()
             self.timings['statistics'] = time.time() - t
         finally:
             for owned in self.stack.values():
                 for a in owned:
+                    a.free()
+            for a in self.member_pars + [v for v in vars(self.skill or SimpleNamespace()).values()
+                                         if isinstance(v, _hip.DeviceArray)]:
+                if a is not None:
                     a.free()
             if getattr(self, 'pipe', None) is not None:
                 self.pipe.close()
@@ -487,4 +656,4 @@ class _Driver:
             '{} {:.3f}'.format(k, sum(self.timings[k]) / n) for k in ('upload', 'kernels', 'post', 'write')) +
             '; statistics {:.3f} s, total {:.3f} s'.format(self.timings['statistics'], self.timings['total']))
         return EnsembleResult(list(plan.names), list(self.member_dirs) if plan.member_outputs else [], stats, self.timings,
-                              self.forcing_upload)
+                              self.forcing_upload, kge=self.kge, kge_basins=list(plan.skill.basins) if plan.skill else None)

@@ -586,8 +586,11 @@ class ConfigReader:
     def configure_ensemble(self, cfg):
         """[Ensemble] (not a section of the reference): members = <csv> (header ``name`` + forcing settings, one row per
         member, an empty cell keeps the ini's value), statistics = mean, std, min, max, qNN (default: none),
-        statistics_vars (default: output_vars), member_outputs = 1 | 0.  Kept as ``self.ensemble``; model.run_model hands
-        a configuration that has it to ensemble.run_ensemble."""
+        statistics_vars (default: output_vars), member_outputs = 1 | 0.  The table may have a column ``abcd_pars``: a
+        member's own ABCD parameter table (.npy, resolved as calib_file is).  observed = <file> (the format of [Calibrate]
+        observed: rows [basin id, *, *, value], months in order) with obs_unit = km3_per_mth | mm_per_mth: every member's
+        KGE against it is written to ensemble/member_kge.csv (ensemble.load_observed checks both).  Kept as
+        ``self.ensemble``; model.run_model hands a configuration that has it to ensemble.run_ensemble."""
         if self.calibrate:
             raise ValidationException('[Ensemble] and Calibrate = 1 ([Calibrate]) exclude each other: a calibration is '
                                       'not a member run.')
@@ -609,6 +612,12 @@ class ConfigReader:
             raise ValidationException('[Ensemble] member_outputs = {!r} must be 0 or 1.'.format(cfg.get('member_outputs')))
         self.ensemble = {'members': path, 'statistics': stats,
                          'statistics_vars': as_list(cfg.get('statistics_vars')) or None, 'member_outputs': member_outputs}
+        if 'observed' in cfg or 'obs_unit' in cfg:
+            if 'observed' not in cfg:
+                raise ValidationException('[Ensemble] obs_unit is given without observed.')
+            obs = cfg['observed'] if isinstance(cfg['observed'], str) else ','.join(cfg['observed'])
+            self.ensemble['observed'] = obs if os.path.isabs(obs) else os.path.join(self.root, obs)
+            self.ensemble['obs_unit'] = cfg.get('obs_unit')
 
     @staticmethod
     def ck_obs_unit(set_calib, unit):

@@ -40,14 +40,16 @@ class Xanthos:
         finally:
             self.cleanup()
 
-    def execute_ensemble(self, members=None, statistics=None, statistics_vars=None, member_outputs=None, overlap=True):
+    def execute_ensemble(self, members=None, statistics=None, statistics_vars=None, member_outputs=None, overlap=True,
+                         observed=None, obs_unit=None):
         """Run ``members`` (a list of (name, overrides) pairs or of dicts with a ``name`` key; overrides as ``execute``
-        takes them; None: the [Ensemble] section's table) through one device-resident pass; see ``ensemble.py``.
-        Returns the EnsembleResult."""
+        takes them, ``abcd_pars`` for a member's own parameter table; None: the [Ensemble] section's table) through one
+        device-resident pass; ``observed`` / ``obs_unit``: score every member against observed basin runoff; see
+        ``ensemble.py``.  Returns the EnsembleResult."""
         from . import ensemble
         self.stage({})
         try:
-            return ensemble.run(self.config, members, statistics, statistics_vars, member_outputs, overlap)
+            return ensemble.run(self.config, members, statistics, statistics_vars, member_outputs, overlap, observed, obs_unit)
         finally:
             self.cleanup()
 
@@ -68,14 +70,20 @@ def check_single_device(config):
                                   'implemented.'.format(config.mod_cfg, config.pet_module, config.runoff_module))
 
 
-def run_ensemble(config_file, members=None, statistics=None, statistics_vars=None, member_outputs=None, overlap=True):
+def run_ensemble(config_file, members=None, statistics=None, statistics_vars=None, member_outputs=None, overlap=True,
+                 observed=None, obs_unit=None):
     """An ensemble of forcing scenarios through the configuration's grid in one device-resident pass: static data stays
     in HBM, the members stream through with their transfers and write-out overlapped, the across-member statistics are
     formed on the device.  ``members`` / ``statistics`` / ``statistics_vars`` / ``member_outputs`` default to the ini's
     [Ensemble] section; ``overlap=False`` runs the members strictly one after the other (same bits).  Member ``name`` is
-    written to <OutputFolder>/<name>/, the statistics to <OutputFolder>/ensemble/.  Returns an EnsembleResult."""
+    written to <OutputFolder>/<name>/, the statistics to <OutputFolder>/ensemble/.  A member may also (or only) carry
+    ``abcd_pars``, its own ABCD parameter table: when no member overrides a forcing setting the run's forcing is uploaded
+    once and PET is computed once, and a member costs one ABCD and one routing pass.  ``observed`` (a file or ndarray of
+    rows [basin id, *, *, value]) with ``obs_unit`` ('km3_per_mth' | 'mm_per_mth') scores every member's runoff against
+    it: ``result.kge`` [members, basins] and ensemble/member_kge.csv.  Returns an EnsembleResult."""
     try:
-        return Xanthos(config_file).execute_ensemble(members, statistics, statistics_vars, member_outputs, overlap)
+        return Xanthos(config_file).execute_ensemble(members, statistics, statistics_vars, member_outputs, overlap,
+                                                     observed, obs_unit)
     finally:
         launch.close_group()
 
