@@ -104,6 +104,18 @@ int xh_csv_write_many(xh_ctx *ctx, int n, const double *const *d_arrs, const int
  * aligned (XH_ERR_ARG otherwise); enqueued on the context's stream, timer "pack_f32_be".  The caller writes the header
  * and sends the 4 n bytes out with xh_download_files.  (MATLAB's column-major body is xh_transpose.) */
 int xh_pack_f32_be(xh_ctx *ctx, const double *d_src, int64_t n, void *d_dst);
+/* The body of a gridded 'f4' variable [time, lat, lon] from HBM (data_writer/gridded.py, GriddedOutput = 1).  The reference
+ * has no gridded output: this replaces the host-side scatter a user writes behind it -- download the [ncell, ncols] array,
+ * fancy-index it into a [ncols, nslots] cube of fill values, narrow and swap.  d_src is the array as written, [ncell, ncols]
+ * row-major; d_cell_of_slot [nslots], nslots = ngridrow * ngridcol in row-major grid order, holds the 0-based cell lying
+ * in each slot or -1 for none (trusted: the host validates it, GridMap); d_dst receives [ncols, nslots] IEEE binary32
+ * values, most significant byte first: with c = cell_of_slot[s], dst[t * nslots + s] is fill_bits when c < 0 or
+ * src[c * ncols + t] is NaN, otherwise the value narrowed exactly as by xh_pack_f32_be (nearest even, overflow to +/-inf,
+ * binary32 subnormals and the sign of zero kept).  Nothing is uploaded; enqueued on the context's stream, timer
+ * "grid_pack"; offsets are 64-bit.  XH_ERR_ARG: a NULL array, ncell < 1, nslots < 1, ncols < 0, d_src not 8-byte or d_dst
+ * not 16-byte aligned.  ncols == 0 is XH_OK and launches nothing. */
+int xh_grid_pack_f32_be(xh_ctx *ctx, const double *d_src, int64_t ncell, int64_t ncols, const int32_t *d_cell_of_slot,
+                        int64_t nslots, uint32_t fill_bits, void *d_dst);
 /* The reader's side of the same: forcing as it is stored -> native doubles, in HBM (the loader of data_load.py:342-390
  * byte-swaps NetCDF variables and widens single precision on the host; here the stored bytes cross PCIe and are widened
  * behind it).  d_dst receives numpy's a.astype(np.float64) of the n stored values at d_src: every non-NaN value exactly
@@ -130,7 +142,7 @@ int xh_transpose(xh_ctx *ctx, const double *d_src, int64_t rows, int64_t cols, d
 /* HIP-event timing of the kernels each entry point launches, accumulated per kernel name on the context's stream.
  * Names: "pm_pet", "abcd_spinup", "abcd_basin_mean", "abcd_sim", "mrtm_route", "calib_abcd", "calib_kge", "calib_de",
  * "agg_time", "agg_spatial", "drought_thresh", "drought_stats", "hargreaves_pet", "gwam_spinup", "gwam_sim",
- * "hs_pet", "trn_daylight", "trn_pet", "diag_cell_total", "diag_group_sum", "ens_stats", "pack_f32_be", "widen".  xh_timing_get waits for the stream, then
+ * "hs_pet", "trn_daylight", "trn_pet", "diag_cell_total", "diag_group_sum", "ens_stats", "pack_f32_be", "widen", "grid_pack".  xh_timing_get waits for the stream, then
  * returns total milliseconds and launch count. */
 int xh_timing_reset(xh_ctx *ctx);
 /* a caller-named span on the context's stream, read back with xh_timing_get like the library's own timers (one open

@@ -124,6 +124,7 @@ SIGNATURES = {
     'xh_csv_write_many': (c_int, [_P, c_int, POINTER(c_void_p), POINTER(c_int64), POINTER(c_int64), POINTER(c_int64),
                                   POINTER(c_char_p), POINTER(ctypes.c_uint64), c_size_t, POINTER(ctypes.c_uint64)]),
     'xh_pack_f32_be': (c_int, [_P, _P, c_int64, _P]),
+    'xh_grid_pack_f32_be': (c_int, [_P, _P, c_int64, c_int64, _P, c_int64, ctypes.c_uint32, _P]),
     'xh_widen': (c_int, [_P, _P, c_int, c_int64, _P]),
     'xh_memset': (c_int, [_P, _P, c_int, c_size_t]),
     'xh_sync': (c_int, [_P]),
@@ -447,26 +448,27 @@ class Context:
         self._check(lib().xh_widen(self.handle, _dptr(src), int(kind), int(n), _dptr(dst)))
 
     def _save_bodies(self, items, nbytes_of, form):
-        """[(path, header bytes, DeviceArray [nrows, ncols]), ...] -> files of header + body, <= 16 at a time: the headers
-        are written here, ``form(src, scratch)`` enqueues the body of ``nbytes_of(src)`` bytes into a scratch DeviceArray,
-        and the bodies leave side by side behind their headers (xh_download_files).  The scratch is freed after the flush."""
+        """[(path, header bytes, DeviceArray [nrows, ncols], ...), ...] -> files of header + body, <= 16 at a time: the
+        headers are written here, ``form(src, scratch, ...)`` enqueues the body of ``nbytes_of(src, ...)`` bytes into a
+        scratch DeviceArray (``...``: what an item holds behind its array, e.g. the grid map of save_grid_nc_many), and the
+        bodies leave side by side behind their headers (xh_download_files).  The scratch is freed after the flush."""
         items = list(items)
         for k in range(0, len(items), 16):
             part, bodies = items[k:k + 16], []
             try:
-                for path, header, src in part:
+                for path, header, src, *more in part:
                     if src.dtype != np.float64 or len(src.shape) != 2:
                         raise ValueError('{}: a [nrows, ncols] float64 DeviceArray is expected'.format(path))
                     with open(path, 'wb') as fh:
                         fh.write(header)
-                    bodies.append(self.empty((max(nbytes_of(src), 1),), dtype=np.uint8))
+                    bodies.append(self.empty((max(nbytes_of(src, *more), 1),), dtype=np.uint8))
                     if src.size:
-                        form(src, bodies[-1])
+                        form(src, bodies[-1], *more)
                 n = len(part)
                 srcs = (c_void_p * n)(*[_dptr(b) for b in bodies])
-                paths = (c_char_p * n)(*[os.fsencode(path) for path, _, _ in part])
-                offs = (ctypes.c_uint64 * n)(*[len(header) for _, header, _ in part])
-                sizes = (c_size_t * n)(*[nbytes_of(src) for _, _, src in part])
+                paths = (c_char_p * n)(*[os.fsencode(item[0]) for item in part])
+                offs = (ctypes.c_uint64 * n)(*[len(item[1]) for item in part])
+                sizes = (c_size_t * n)(*[nbytes_of(*item[2:]) for item in part])
                 self._check(lib().xh_download_files(self.handle, n, srcs, paths, offs, sizes))
             finally:
                 for b in bodies:
@@ -482,6 +484,22 @@ class Context:
         array's name and shape, the body its doubles column-major (xh_transpose in HBM)."""
         self._save_bodies(items, lambda src: src.nbytes,
                           lambda src, body: self.transpose(src, src.shape[0], src.shape[1], body))
+
+    def grid_pack_f32_be(self, src, cell_of_slot, nslots, fill_bits, dst):
+        """DeviceArray ``src`` [ncell, ncols] -> ``dst`` [ncols, nslots] big-endian binary32 (xh_grid_pack_f32_be), enqueued:
+        slot s takes the row of cell ``cell_of_slot[s]`` (int32 in HBM, 0-based), narrowed as by pack_f32_be; a slot
+        without a cell (-1) and every NaN take ``fill_bits``.  ``dst`` 16-byte aligned."""
+        ncell, ncols = src.shape
+        self._check(lib().xh_grid_pack_f32_be(self.handle, _dptr(src), ncell, ncols, _dptr(cell_of_slot), int(nslots),
+                                              int(fill_bits), _dptr(dst)))
+
+    def save_grid_nc_many(self, items):
+        """[(path, header, DeviceArray [ncell, ncols], grid map), ...] -> gridded NetCDF-classic files: ``header`` is
+        data_writer.gridded.grid_nc_header(...), the body [ncols, nslots] big-endian binary32 with the map's fill value
+        where no cell lies, gathered and packed in HBM (xh_grid_pack_f32_be)."""
+        self._save_bodies(items, lambda src, grid: src.shape[1] * grid.nslots * 4,
+                          lambda src, body, grid: self.grid_pack_f32_be(src, grid.device_table(self), grid.nslots,
+                                                                        grid.fill_bits, body))
 
     def csv_format(self, src, first_id=1, cap=None):
         """The csv lines of DeviceArray ``src`` [nrows, ncols] formatted in HBM (xh_csv_format), downloaded for inspection:

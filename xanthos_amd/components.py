@@ -102,6 +102,12 @@ class Components:
         self.group = launch.current_group()
         self.is_root = self.group is None or self.group.rank == 0
         self.gather = None
+        # GriddedOutput = 1: the one map of cells to grid slots that every writer of this run takes (validated here, before
+        # anything is computed)
+        self.grid = None
+        if getattr(config, 'GriddedOutput', 0) and self.is_root:
+            from .data_writer.gridded import GridMap
+            self.grid = GridMap(self.data.coords, config.ngridrow, config.ngridcol)
 
     @property
     def q(self):
@@ -475,7 +481,7 @@ class Components:
         all_outputs = {k: (self.pipe.out[_RESULTS[a]] if self.pipe is not None and a not in self._host
                            and (a != 'Avg_ChFlow' or self.pipe.plan is not None) else getattr(self, a))
                        for k, a in names.items() if k in self.s.output_vars or k in ('q', 'avgchflow')}
-        writer = OutWriter(self.s, self.data.area, all_outputs)
+        writer = OutWriter(self.s, self.data.area, all_outputs, grid=self.grid)
         writer.keep_device, writer.write_files = keep_device, write_files
         writer.write()
         self._writer, self._q, self._ac = writer, None, None

@@ -15,6 +15,10 @@ the names alone (formats.py, made here) and a body formed in HBM (csrc/xh_pack.h
 column-major doubles) that leaves through the npy writer's path; the tables with names are cell arrays under MATLAB
 (``savemat`` on the host), and NetCDF cannot hold them -- the reference fails there, this writer refuses the combination
 when it is constructed.
+
+With a ``grid`` (gridded.GridMap; [Project] GriddedOutput = 1) every per-cell table is written a second time as
+``<same stem>_grid.nc``: a CF NetCDF map [time, lat, lon] of the array as written, its header made by gridded.py, its body
+gathered, transposed and narrowed in HBM (csrc/xh_grid.hip).  The per-cell files are what they are without it.
 """
 import logging
 import os
@@ -23,7 +27,7 @@ import numpy as np
 
 from .. import _hip
 from ..ini_reader import ValidationException
-from . import formats
+from . import formats, gridded
 
 FORMAT_NETCDF, FORMAT_CSV, FORMAT_MAT, FORMAT_PARQUET, FORMAT_NPY = 0, 1, 2, 3, 4
 UNIT_MM_MTH, UNIT_KM3_MTH = 0, 1
@@ -32,7 +36,7 @@ NMONTHS = 12
 
 class OutWriter:
 
-    def __init__(self, settings, grid_areas, all_outputs, device=None):
+    def __init__(self, settings, grid_areas, all_outputs, device=None, grid=None):
         # the reference's agg_spatial tables have a name column, which its save_netcdf cannot index (InvalidIndexError
         # after the whole run): refused before anything is computed for the writer
         aggregates = [k for k in ('AggregateRunoffBasin', 'AggregateRunoffCountry', 'AggregateRunoffGCAMRegion')
@@ -51,7 +55,8 @@ class OutWriter:
         self.keep_device, self.write_files = False, True
         self.device_outputs = {}
         # lists while write() collects the files it flushes together
-        self._npy_from_device = self._csv_from_device = self._bodies_from_device = None
+        self._npy_from_device = self._csv_from_device = self._bodies_from_device = self._grids_from_device = None
+        self.grid = grid                                # gridded.GridMap: every per-cell table also as <stem>_grid.nc
         self.grid_areas = np.asarray(grid_areas, dtype=np.float64)
         self.conversion_mm_km3 = self.grid_areas / 1e6
         self.proj_name = settings.ProjectName
@@ -63,6 +68,7 @@ class OutWriter:
         years = range(settings.StartYear, settings.EndYear + 1)
         self.time_steps = ([str(y) for y in years] if self.output_in_year else
                            ['{}{:02}'.format(y, m) for y in years for m in range(1, NMONTHS + 1)])
+        self.grid_time = gridded.time_axis(settings.StartYear, len(self.time_steps), self.output_in_year)
         if self.out_format not in (FORMAT_NETCDF, FORMAT_CSV, FORMAT_MAT, FORMAT_PARQUET, FORMAT_NPY):
             logging.warning('Output format {} is invalid; writing output as .csv'.format(self.out_format))
             self.out_format = FORMAT_CSV
@@ -144,6 +150,7 @@ class OutWriter:
         self._npy_from_device = []                      # monthly, unconverted npy outputs still in HBM: saved side by side
         self._csv_from_device = []                      # csv outputs: formatted in HBM and written side by side
         self._bodies_from_device = []                   # NetCDF / MATLAB outputs: bodies formed in HBM, written side by side
+        self._grids_from_device = []                    # the maps next to them (grid): the same
         # csv: an aggregated / converted array stays in HBM for the formatter (get() fetches it on demand); with keep_device
         # that array goes to the caller afterwards, so the host copy is made here as before
         # (NetCDF / MATLAB: the same, for the kernels that form the file's body)
@@ -183,7 +190,12 @@ class OutWriter:
             for (_, _, dev), mine in self._bodies_from_device:
                 if mine:
                     dev.free()
-        self._npy_from_device = self._csv_from_device = self._bodies_from_device = None
+        if self._grids_from_device:
+            self.ctx.save_grid_nc_many([item for item, _ in self._grids_from_device])
+            for (_, _, dev, _), mine in self._grids_from_device:
+                if mine:
+                    dev.free()
+        self._npy_from_device = self._csv_from_device = self._bodies_from_device = self._grids_from_device = None
 
     def write_aggregates(self, ref, values, basin, country, region):
         """Spatial sums of ``values`` (the written runoff) by basin / country / GCAM region (:126-158).
@@ -216,6 +228,28 @@ class OutWriter:
         return out
 
     def write_data(self, filename, var, data, col_names, first_id=1, names=None):
+        self._write_table(filename, var, data, col_names, first_id, names)
+        if self.grid is not None and names is None and data.shape[0] == self.grid.ncell and self.write_files:
+            self._write_grid(filename, var, data)
+
+    def _write_grid(self, filename, var, data):
+        """``<filename>_grid.nc``: the per-cell table ``data`` as a map [time, lat, lon] (gridded.py), from its copy in HBM
+        where there is one."""
+        collect = self._grids_from_device is not None and var in self.output_names
+        if collect:                                     # (write() under keep_device: the array as written is in HBM as well)
+            data = self.device_outputs.get(var, data)
+        days, units = self.grid_time
+        header = gridded.grid_nc_header(var, self.unit_of(var), days[:data.shape[1]], units, self.grid, title=self.proj_name)
+        dev, mine = self._on_device(data)
+        item = (filename + '_grid.nc', header, dev, self.grid)
+        if collect:
+            self._grids_from_device.append((item, mine))                         # flushed at the end of write()
+        else:
+            self.ctx.save_grid_nc_many([item])
+            if mine:
+                dev.free()
+
+    def _write_table(self, filename, var, data, col_names, first_id, names):
         os.makedirs(self.out_folder, exist_ok=True)
         if self.out_format == FORMAT_NPY:
             if isinstance(data, _hip.DeviceArray):

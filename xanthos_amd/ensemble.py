@@ -9,7 +9,8 @@ and write-out proceed on a third -- and the mean / spread / quantiles over the m
 
 Member ``name`` is written to ``<OutputFolder>/<name>/`` with exactly the files
 ``Xanthos(ini).execute({**overrides, 'OutputFolder': ...})`` writes (the log stays in ``<OutputFolder>``); the statistics
-go to ``<OutputFolder>/ensemble/<var>_<unit>_<ProjectName>_<stat>.<ext>`` through ``OutWriter.write_data``.
+go to ``<OutputFolder>/ensemble/<var>_<unit>_<ProjectName>_<stat>.<ext>`` through ``OutWriter.write_data``
+(with ``GriddedOutput = 1`` the members' maps and ``..._<stat>_grid.nc`` next to them, from the run's one ``GridMap``).
 
 Only the settings that name the forcing arrays of the configured PET / runoff modules may vary per member
 (``ConfigReader.forcing_settings``), and with ABCD the parameter table: ``abcd_pars``, an ndarray or .npy of the shape of the
@@ -455,6 +456,8 @@ class _Driver:
                 if table is not None:
                     table = table if isinstance(table, np.ndarray) else np.load(table)
                     self.member_pars[k] = ctx.upload(np.asarray(table, dtype=np.float64))
+        if c.grid is not None:                            # GriddedOutput = 1: the table of the maps, up before any writer asks
+            c.grid.device_table(ctx)
         resident = self.plan.resident
         if not self.overlap:
             self.up = self.wr = ctx
@@ -593,7 +596,7 @@ class _Driver:
             return result
         cfg = copy.copy(s)
         cfg.OutputFolder = os.path.join(s.OutputFolder, STATISTICS_DIR)
-        w = OutWriter(cfg, self.c.data.area, {})
+        w = OutWriter(cfg, self.c.data.area, {}, grid=self.c.grid)
         plain = [label for label in _hip.ENS_STAT_BITS if any(label == l for l, _ in plan.statistics)]      # the library's order
         quant = [(label, q) for label, q in plan.statistics if q is not None]
         for var in plan.statistics_vars:

@@ -174,6 +174,11 @@ class ConfigReader:
                     'AggregateRunoffGCAMRegion', 'PerformDiagnostics', 'CreateTimeSeriesPlot', 'CalculateDroughtStats',
                     'CalculateAccessibleWater', 'CalculateHydropowerPotential', 'CalculateHydropowerActual'):
             setattr(self, key, int(p.get(key, 0)))
+        # every per-cell output also as a CF NetCDF map <same stem>_grid.nc (data_writer/gridded.py); not in the reference
+        raw_grid = str(p.get('GriddedOutput', 0)).strip()
+        if raw_grid not in ('0', '1'):
+            raise ValidationException("GriddedOutput must be 0 or 1, not '{}'".format(raw_grid))
+        self.GriddedOutput = int(raw_grid)
         self.calibrate = int(p.get('Calibrate', 0))
         self.nmonths = (self.EndYear - self.StartYear + 1) * 12
         self.device = int(p.get('device', 0))

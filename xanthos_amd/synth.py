@@ -218,7 +218,7 @@ def write_example(root, world, forcing, start_year, end_year, project='pm_abcd_m
                   routing_spinup=None, output_vars=('q', 'avgchflow'), obs=None, post=False, aggregates=False,
                   hist_flag=True, ch_storage=None, output_format=1, output_in_year=0, set_calibrate=0,
                   calibration_basins='1-2', gauges=None, gauge_obs=None, gauge_missing=None, calibrate_velocity=0,
-                  velocity_scale_bounds=None, velocity_scale=None):
+                  velocity_scale_bounds=None, velocity_scale=None, gridded=False):
     """Write ``world`` + ``forcing`` as a Xanthos-style input tree under ``root`` and return the .ini path.
 
     Layout and file names follow the reference's example (ini_reader.py:254-279, 353-381, 399-416, 425-437):
@@ -239,6 +239,7 @@ def write_example(root, world, forcing, start_year, end_year, project='pm_abcd_m
     ``calibrate_velocity`` = 1 (with ``set_calibrate = 1`` or gauges) and ``velocity_scale_bounds`` = (lo, hi) go to
     [Calibrate] as given; ``velocity_scale`` (rows [basin_id, scale], or a dict) is written as routing/mrtm/
     velocity_scale.csv and named in [[mrtm]].
+    ``gridded=True`` adds ``GriddedOutput = 1`` to [Project]: every per-cell output also as a CF NetCDF map.
     """
     import os
     inp = os.path.join(root, 'input')
@@ -352,7 +353,7 @@ EndYear = {y1}
 output_vars = {ov}
 OutputFormat = {ofmt}
 OutputUnit = 0
-OutputInYear = {oyear}
+OutputInYear = {oyear}{grid}
 Calibrate = {cal}
 {post_project}
 [PET]
@@ -389,7 +390,7 @@ routing_spinup = {rtsp}
 channel_velocity = velocity.npy
 flow_distance = flow_dist.npy
 flow_direction = flow_dir.npy
-{vs}{calib}{post_sections}'''.format(vs=vs_line, ofmt=int(output_format), oyear=int(output_in_year), chs=chs_lines, hist='True' if hist_flag else 'False', post_project=post_project, post_sections=post_sections, project=project, root=root, nb=world.n_basins, ncell=world.ncell, nrow=world.nrow, ncol=world.ncol,
+{vs}{calib}{post_sections}'''.format(vs=vs_line, grid='\nGriddedOutput = 1' if gridded else '', ofmt=int(output_format), oyear=int(output_in_year), chs=chs_lines, hist='True' if hist_flag else 'False', post_project=post_project, post_sections=post_sections, project=project, root=root, nb=world.n_basins, ncell=world.ncell, nrow=world.nrow, ncol=world.ncol,
                   y0=start_year, y1=end_year, ov=', '.join(output_vars), cal=int(obs is not None or gauges is not None), nlcs=world.nlcs,
                   lcy=', '.join(str(y) for y in world.lc_years), rsp=runoff_spinup,
                   rtsp=nmonths if routing_spinup is None else routing_spinup,
