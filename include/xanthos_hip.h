@@ -526,6 +526,33 @@ int xh_basin_kge(xh_ctx *ctx, int64_t ncell, int32_t nmonths, int32_t nbasins, c
                  const int32_t *d_cells, const double *d_q, const double *d_area, const double *d_obs, double *d_series,
                  double *d_ed);
 
+/* ------------------------------------------------------------------ skill at stream gauges
+ * xh_gauge_skill: the routed streamflow of a run scored at stream gauges, on the Avg_ChFlow the run left in HBM.  The
+ * reference scores streamflow inside its calibration only (calibrate_abcd.py:196-213); a forward run's flow is compared
+ * with a measured discharge, if at all, from the files.  d_gauge_cell [ngauge]: 0-based grid cell of each gauge (two gauges
+ * may share a cell); d_flow [ncell, nmonths] m3/s; d_obs [ngauge, nmonths] m3/s, NaN (or an infinity) = no observation;
+ * d_series [ngauge, nmonths] optional out (NULL: not written): d_flow[cell_g, :], the same bits; d_metrics [ngauge, 8] out.
+ * Per gauge, with V the months whose observation is finite, n = |V|, s = flow[cell_g, V], o = obs[g, V]:
+ *   col 0  n (as a double)
+ *   col 1  ED = sqrt((r - 1)^2 + (alpha - 1)^2 + (beta - 1)^2); KGE = 1 - ED is the caller's to form
+ *   col 2  r: np.corrcoef through np.cov with n - 1, clipped to [-1, 1]
+ *   col 3  alpha = std(s) / std(o), population standard deviations
+ *   col 4  beta = mean(s) / mean(o)
+ *   col 5  NSE = 1 - sum (s - o)^2 / sum (o - mean(o))^2
+ *   col 6  PBIAS = 100 sum (s - o) / sum o
+ *   col 7  RMSE = sqrt(sum (s - o)^2 / n)
+ * Columns 1-4 are formed as the gauge form of the streamflow objective forms them (xh_calib_gauge_objective_multi): every
+ * sum over V is 256 strided partial sums joined by one tree in shared memory, a skipped month adds nothing, no contraction --
+ * so ED has the bits of that objective's per-gauge ED on the same series and record, and of the outlet form's for a
+ * complete record.  The sums of columns 5-7 have the same order.  A NaN flow at a month of V makes columns 1-7 NaN, one at a
+ * month outside V changes nothing; n < 2 gives NaN in columns 1-7; a record or a series of zero variance gives the NaN or
+ * infinity numpy gives.  A gauge cell outside [0, ncell) reads no flow: columns 1-7 and its row of d_series are NaN (col 0
+ * still counts the record).  One workgroup per gauge, fixed summation order, no atomics: two calls give the same bits.
+ * XH_ERR_ARG: a NULL array other than d_series, ngauge < 1 or > 65535, nmonths < 2, ncell < 1.  Asynchronous on the
+ * context's stream; nothing is uploaded (the tables are the caller's, made once, in HBM).                            */
+int xh_gauge_skill(xh_ctx *ctx, int64_t ncell, int32_t nmonths, int32_t ngauge, const int32_t *d_gauge_cell,
+                   const double *d_flow, const double *d_obs, double *d_series, double *d_metrics);
+
 /* The same objective for SEVERAL basins in one launch, each basin with its own population: one basin alone is only
  * months x ~1.7 us of dependent chain, far too little to fill the chip.  h_ncell [nbasins]; h_pars [nbasins, nmembers,
  * npar]; h_pet_t / h_precip_t / h_tmin_t / h_area: host arrays of nbasins DEVICE pointers ([nmonths, ncell_b] each;

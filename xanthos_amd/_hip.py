@@ -204,6 +204,7 @@ SIGNATURES = {
     'xh_diag_group_sum': (c_int, [_P, c_int64, c_int32, c_int32, _P, _P, _P, _P]),
     'xh_ens_stats': (c_int, [_P, c_int64, c_int32, POINTER(c_void_p), ctypes.c_uint32, c_int32, _P, POINTER(c_void_p)]),
     'xh_basin_kge': (c_int, [_P, c_int64, c_int32, c_int32, _P, _P, _P, _P, _P, _P, _P]),
+    'xh_gauge_skill': (c_int, [_P, c_int64, c_int32, c_int32, _P, _P, _P, _P, _P]),
     'xh_synth_forcing': (c_int, [_P, c_uint64, c_double, c_int64, c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
 }
 
@@ -854,6 +855,15 @@ class Context:
         an optional [nbasins, nmonths] output.  Asynchronous."""
         self._check(lib().xh_basin_kge(self.handle, int(ncell), int(nmonths), int(nbasins), _dptr(start), _dptr(cells),
                                        _dptr(q), _dptr(area), _dptr(obs), _dptr(series), _dptr(ed)))
+
+    # ---- skill at stream gauges (csrc/xh_gauge_skill.hip)
+    def gauge_skill(self, ncell, nmonths, ngauge, gauge_cell, flow, obs, metrics, series=None):
+        """The eight columns of xh_gauge_skill per gauge -- n, ED, r, alpha, beta, NSE, PBIAS, RMSE -- of ``flow``
+        [ncell, nmonths] (Avg_ChFlow, m3/s) at the cells ``gauge_cell`` (int32 [ngauge], 0-based) against ``obs`` [ngauge,
+        nmonths] (NaN = no observation) into ``metrics`` [ngauge, 8]; ``series``: an optional [ngauge, nmonths] output, the
+        flow rows of the gauge cells.  All DeviceArrays or raw device addresses (a member's slice).  Asynchronous."""
+        self._check(lib().xh_gauge_skill(self.handle, int(ncell), int(nmonths), int(ngauge), _dptr(gauge_cell), _dptr(flow),
+                                         _dptr(obs), _dptr(series), _dptr(metrics)))
 
     # ---- bench support
     def synth_forcing(self, seed, ncell, nmonths, lat, out, nan_frac=0.001, cell_ids=None):

@@ -81,7 +81,8 @@ class Components:
     PET, AET, Q, Sav = _result('PET'), _result('AET'), _result('Q'), _result('Sav')
     ChStorage, Avg_ChFlow = _result('ChStorage'), _result('Avg_ChFlow')
 
-    def __init__(self, config):
+    def __init__(self, config, gauges=None):
+        """``gauges``: the checked gauge set of [Evaluate] when the caller has loaded it already (the ensemble driver)."""
         self.s = config
         self.import_core()
         self.timings = {}                  # seconds per phase of run_model(): load, topology, plan, upload, kernels, download, ...
@@ -108,6 +109,13 @@ class Components:
         if getattr(config, 'GriddedOutput', 0) and self.is_root:
             from .data_writer.gridded import GridMap
             self.grid = GridMap(self.data.coords, config.ngridrow, config.ngridcol)
+        # [Evaluate]: the stream gauges the routed flow is scored at (loaded and checked here, before anything is computed),
+        # and what evaluate() leaves: gauge_skill {column: ndarray [ngauge]} and gauge_flow [ngauge, nmonths]
+        self.gauges = gauges
+        self.gauge_skill = self.gauge_flow = None
+        if gauges is None and getattr(config, 'evaluate', None) and self.is_root:
+            from .evaluate import load_gauge_set
+            self.gauges = load_gauge_set(config)
 
     @property
     def q(self):
@@ -319,6 +327,7 @@ class Components:
         c.s, c.pipe = settings, pipe
         c.timings, c._host = {}, {}
         c._writer = c._q = c._ac = None
+        c.gauge_skill = c.gauge_flow = None
         return c
 
     def _pipeline_args(self, runoff, um, cells=None):
@@ -426,6 +435,17 @@ class Components:
             t0 = time.time()
             HydropowerActual(self.s, self._routed_flow())
             logging.info('---Hydropower Actual has finished successfully: %s seconds ------' % (time.time() - t0))
+
+    def evaluate(self):
+        """Skill of the routed flow at the stream gauges of [Evaluate] (not in the reference): gauge_skill.csv and
+        gauge_flow.csv, and the attributes gauge_skill / gauge_flow."""
+        if self.gauges is not None and self.is_root:
+            from .evaluate import GaugeSkill
+            logging.info('---Start Gauge Skill:')
+            t0 = time.time()
+            res = GaugeSkill(self.s, self.gauges, self._routed_flow())
+            self.gauge_skill, self.gauge_flow = res.skill, res.flow
+            logging.info('---Gauge Skill has finished successfully: %s seconds ------' % (time.time() - t0))
 
     def _runoff(self):
         """Q for a post-processor: the DeviceArray in HBM after a device-resident simulation (on a sharded run the root's

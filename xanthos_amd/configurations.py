@@ -33,6 +33,7 @@ class ConfigRunner:
         c.drought()
         c.hydropower_potential()
         c.hydropower_actual()
+        c.evaluate()                  # ([Evaluate], not in the reference: the routed flow scored at stream gauges)
         c.diagnostics()
         c.timings['post'] = time.time() - t
         t = time.time()

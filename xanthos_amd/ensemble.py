@@ -17,7 +17,10 @@ Only the settings that name the forcing arrays of the configured PET / runoff mo
 run's calib_file array -- the member then equals the single run with ``calib_file`` set to it.  When no member overrides a
 forcing setting the ensemble is *resident*: the forcing is uploaded once, PET is computed once, and a member is one ABCD and
 one routing pass.  With ``observed`` every member's Q is scored in HBM against observed basin runoff (``xh_basin_kge``, the
-reference's KGE): ``EnsembleResult.kge`` and ``<OutputFolder>/ensemble/member_kge.csv``.
+reference's KGE): ``EnsembleResult.kge`` and ``<OutputFolder>/ensemble/member_kge.csv``.  With stream gauges ([Evaluate],
+or ``gauges`` / ``gauge_observed``) every member's Avg_ChFlow is scored at the gauge cells in HBM (``xh_gauge_skill``,
+DESIGN.md 4.17): ``EnsembleResult.gauge_kge`` / ``gauge_skill`` / ``gauge_flow``, ``ensemble/member_gauge_kge.csv`` and
+``member_gauge_skill.csv``, and with ``statistics`` the across-member statistics of the gauge hydrographs.
 There is no host fallback: without a device the call raises ``HipUnavailable``.
 """
 import copy
@@ -34,6 +37,7 @@ from . import _hip, launch, nc_header
 from .components import _FORCING_DATA, _FORCING_SETTINGS, Components, runs_device_resident
 from .configurations import ConfigRunner
 from .data_load import load_file
+from .evaluate import gauge_skill as gskill
 from .ini_reader import ValidationException, parse_statistic
 from .pipeline import OUTPUTS, DevicePipeline
 
@@ -41,6 +45,8 @@ MAX_MEMBERS_WITH_STATISTICS = 64        # xh_ens_stats' compiled limit
 STATISTICS_DIR = 'ensemble'
 PARS_KEY = 'abcd_pars'                  # a member's own [rows, 5] table of a, b, c, d, m (the shape of the run's calib_file array)
 KGE_TABLE = 'member_kge.csv'
+GAUGE_KGE_TABLE, GAUGE_SKILL_TABLE = 'member_gauge_kge.csv', 'member_gauge_skill.csv'
+GAUGE_STAT_FILE = 'gauge_flow_{}.csv'
 OBS_UNITS = ('km3_per_mth', 'mm_per_mth')
 # output variable -> result attribute (Components.output_simulation)
 _WRITTEN = ('pet', 'aet', 'q', 'soilmoisture', 'avgchflow')
@@ -55,7 +61,8 @@ def refuse(member, key, why):
 class EnsemblePlan(SimpleNamespace):
     """What validate() made of a request: names, overrides (one dict per member), statistics [(label, q or None)],
     statistics_vars, member_outputs, ncols (columns of an array as written), bytes_needed, resident (no member overrides a
-    forcing setting: one upload, one PET), skill (None, or load_observed()'s basins / observations / cell lists)."""
+    forcing setting: one upload, one PET), skill (None, or load_observed()'s basins / observations / cell lists), gauge_skill
+    (None, or evaluate.load_gauge_set()'s ids / cells / basins / records)."""
 
 
 def read_members(config, path):
@@ -195,7 +202,8 @@ def load_observed(s, observed, obs_unit, runs_runoff=True):
                            cells=np.concatenate(cells).astype(np.int32))
 
 
-def validate(config, members, statistics=(), statistics_vars=None, member_outputs=1, gpus=None, observed=None, obs_unit=None):
+def validate(config, members, statistics=(), statistics_vars=None, member_outputs=1, gpus=None, observed=None, obs_unit=None,
+             gauges=None, gauge_observed=None, gauge_missing=None):
     """Every refusal of an ensemble request, before any GPU work; returns the EnsemblePlan."""
     s = config
     if getattr(s, 'calibrate', 0):
@@ -268,7 +276,12 @@ def validate(config, members, statistics=(), statistics_vars=None, member_output
     if member_outputs not in (0, 1):
         raise refuse(None, 'member_outputs', 'must be 0 or 1')
     skill = None if observed is None else load_observed(s, observed, obs_unit, runner.run_runoff)
-    if not member_outputs and not (stats and statistics_vars) and skill is None:      # (with observed: the table of KGE)
+    # stream gauges: the arguments, or the ini's [Evaluate]; loaded and checked once for all members
+    gauge_skill = None
+    if gauges is not None or gauge_observed is not None or getattr(s, 'evaluate', None):
+        gauge_skill = gskill.load_gauge_set(s, gauges, gauge_observed, gauge_missing)
+    if not member_outputs and not (stats and statistics_vars) and skill is None and gauge_skill is None:
+        # (with observed or gauges: the tables of the members' skill)
         raise refuse(None, 'member_outputs', 'member_outputs = 0 without statistics writes nothing')
     if stats and len(members) > MAX_MEMBERS_WITH_STATISTICS:
         raise refuse(None, 'statistics', '{} members exceed the {} the statistics kernel takes'.format(
@@ -283,15 +296,20 @@ def validate(config, members, statistics=(), statistics_vars=None, member_output
     need = 8 * s.ncell * (ncols * (len(members) * len(statistics_vars) + len(stats)) + s.nmonths * arrays)
     if single:                         # the uploading context's scratch of one array as stored (pipeline._upload_stored)
         need += 4 * s.ncell * s.nmonths
+    if gauge_skill is not None:        # cells, records, the members' hydrographs and metrics, the hydrographs' statistics
+        ng = gauge_skill.ids.size
+        need += 4 * ng + 8 * ng * (s.nmonths + len(members) * (s.nmonths + gskill.NCOLS) + len(stats) * s.nmonths)
     return EnsemblePlan(names=[n for n, _ in members], overrides=[o for _, o in members], statistics=stats,
                         statistics_vars=statistics_vars, member_outputs=member_outputs, ncols=ncols, bytes_needed=need,
-                        resident=resident, skill=skill)
+                        resident=resident, skill=skill, gauge_skill=gauge_skill)
 
 
 def check_fits(plan, free_bytes):
-    """The member stack against the free HBM."""
-    if plan.statistics and plan.bytes_needed > free_bytes:
-        raise refuse(None, 'statistics', 'the stack of {} members x {} variables and the buffer sets need {} bytes of HBM, {} '
+    """The member stack (and the gauge hydrographs of all members) against the free HBM."""
+    gauges = getattr(plan, 'gauge_skill', None) is not None
+    if (plan.statistics or gauges) and plan.bytes_needed > free_bytes:
+        key = 'statistics' if plan.statistics else 'gauges'
+        raise refuse(None, key, 'the stack of {} members x {} variables and the buffer sets need {} bytes of HBM, {} '
                      'bytes are free'.format(len(plan.names), len(plan.statistics_vars), plan.bytes_needed, free_bytes))
 
 
@@ -393,14 +411,21 @@ class EnsembleResult:
     other members' entries are empty), kge [members, basins] and kge_basins (ascending basin ids) with ``observed``: each
     member's Kling-Gupta efficiency against the observed basin runoff, also in ensemble/member_kge.csv; None without."""
 
-    def __init__(self, names, member_dirs, statistics, timings, forcing_upload=None, kge=None, kge_basins=None):
+    def __init__(self, names, member_dirs, statistics, timings, forcing_upload=None, kge=None, kge_basins=None, gauges=None):
         self.names, self.member_dirs, self.statistics, self.timings = names, member_dirs, statistics, timings
         self.forcing_upload = forcing_upload
         self.kge, self.kge_basins = kge, kge_basins
+        # with stream gauges: gauge_ids (the order of the gauges file), gauge_kge [members, gauges], gauge_skill {column:
+        # [members, gauges]} (evaluate.COLUMNS), gauge_flow [members, gauges, nmonths] and, with statistics,
+        # gauge_flow_statistics {stat: [gauges, nmonths]}; None without
+        g = gauges or {}
+        self.gauge_ids, self.gauge_skill, self.gauge_flow = g.get('ids'), g.get('skill'), g.get('flow')
+        self.gauge_kge = None if self.gauge_skill is None else self.gauge_skill['kge']
+        self.gauge_flow_statistics = g.get('statistics')
 
 
 def run(config, members=None, statistics=None, statistics_vars=None, member_outputs=None, overlap=True, observed=None,
-        obs_unit=None):
+        obs_unit=None, gauges=None, gauge_observed=None, gauge_missing=None):
     """The driver behind run_ensemble / Xanthos.execute_ensemble; ``config``: a staged ConfigReader."""
     s = config
     ens = getattr(s, 'ensemble', None) or {}
@@ -413,7 +438,8 @@ def run(config, members=None, statistics=None, statistics_vars=None, member_outp
     member_outputs = ens.get('member_outputs', 1) if member_outputs is None else member_outputs
     observed = ens.get('observed') if observed is None else observed
     obs_unit = ens.get('obs_unit') if obs_unit is None else obs_unit
-    plan = validate(s, members, statistics, statistics_vars, member_outputs, observed=observed, obs_unit=obs_unit)
+    plan = validate(s, members, statistics, statistics_vars, member_outputs, observed=observed, obs_unit=obs_unit,
+                    gauges=gauges, gauge_observed=gauge_observed, gauge_missing=gauge_missing)
     ctx = _hip.get_context(s.device)                      # HipUnavailable without a device: there is no host fallback
     check_fits(plan, ctx.mem_info()[0])
     return _Driver(s, plan, ctx, overlap).run()
@@ -437,12 +463,13 @@ class _Driver:
         self.up = self.wr = None
         self.member_pars = [None] * n                     # DeviceArray of a member's own parameter table
         self.run_pars = self.skill = self.kge = None
+        self.gauges = self.gauge_result = None            # the device tables of xh_gauge_skill; what member_gauge_skill() made
 
     # ---- set-up: everything static, once
     def setup(self):
         s, ctx = self.s, self.ctx
         runner = ConfigRunner(s)
-        self.c = c = Components(s)
+        self.c = c = Components(s, gauges=self.plan.gauge_skill)
         self.runoff = s.runoff_module if runner.run_runoff else 'none'
         c.check_resident(self.runoff)
         um = c.topology() if (runner.run_routing and s.routing_module == 'mrtm') else None
@@ -485,6 +512,13 @@ class _Driver:
 
     def setup_skill(self):
         """The tables of xh_basin_kge, once per ensemble, on the writing context: the skill is formed in the write stage."""
+        gs = self.plan.gauge_skill
+        if gs is not None:             # xh_gauge_skill: cells and records once, every member's hydrographs and metrics
+            wr, n, ng = self.wr, len(self.plan.names), gs.ids.size
+            self.gauges = SimpleNamespace(
+                ngauge=ng, cells=wr.upload(gs.cells, dtype=np.int32), obs=wr.upload(gs.obs),
+                series=wr.empty((n, ng, self.pipe.nmonths)), metrics=wr.empty((n, ng, gskill.NCOLS)))
+            wr.sync()
         sk = self.plan.skill
         if sk is None:
             return
@@ -557,16 +591,29 @@ class _Driver:
         if sk is not None:                                # ED of this member's Q, mm per month, into row k (asynchronous)
             self.wr.basin_kge(pipe.ncell, pipe.nmonths, sk.nbasins, sk.start, sk.cells, self.sets[i][1]['q'], sk.area, sk.obs,
                               sk.ed.ptr + 8 * k * sk.nbasins, series=sk.series)
+        gd = self.gauges
+        if gd is not None:                                # this member's Avg_ChFlow at the gauges, into slice k (asynchronous)
+            series = gd.series.ptr + 8 * k * gd.ngauge * pipe.nmonths
+            metrics = gd.metrics.ptr + 8 * k * gd.ngauge * gskill.NCOLS
+            self.wr.gauge_skill(pipe.ncell, pipe.nmonths, gd.ngauge, gd.cells, self.sets[i][1]['avg'], gd.obs, metrics, series=series)
         if plan.member_outputs:                           # the phases of ConfigRunner.run() after the simulation, in its order
             os.makedirs(cfg.OutputFolder, exist_ok=True)
             c.accessible_water()
             c.drought()
             c.hydropower_potential()
             c.hydropower_actual()
+            if gd is not None:                            # Components.evaluate()'s two files, from slice k
+                gs = plan.gauge_skill
+                raw, flow = np.empty((gd.ngauge, gskill.NCOLS)), np.empty((gd.ngauge, pipe.nmonths))
+                self.wr.d2h_async(raw, metrics)
+                self.wr.d2h_async(flow, series)
+                self.wr.sync()
+                gskill.write_skill(os.path.join(cfg.OutputFolder, gskill.SKILL_FILE), gs, gskill.skill_table(raw))
+                gskill.write_flow(os.path.join(cfg.OutputFolder, gskill.FLOW_FILE), gs, flow, gskill.month_labels(cfg))
             c.diagnostics()
         self.timings['post'][k] = time.time() - t
         t = time.time()
-        if not (plan.member_outputs or plan.statistics_vars):      # (member_outputs = 0 with observed alone: only the skill)
+        if not (plan.member_outputs or plan.statistics_vars):      # (member_outputs = 0 with observed or gauges alone: only the skill)
             self.wr.sync()
             self.timings['write'][k] = time.time() - t
             return
@@ -583,7 +630,7 @@ class _Driver:
             a.free()
         w.device_outputs = {}
         w.ctx.sync()
-        if sk is not None and w.ctx is not self.wr:
+        if (sk is not None or gd is not None) and w.ctx is not self.wr:
             self.wr.sync()
         self.timings['write'][k] = time.time() - t
 
@@ -628,6 +675,46 @@ class _Driver:
             for name, row in zip(plan.names, self.kge):
                 fh.write(name + ',' + ','.join(repr(float(v)) for v in row) + '\n')
 
+    def member_gauge_skill(self):
+        """The members' skill at the stream gauges from HBM -- {column: [members, gauges]}, the hydrographs [members,
+        gauges, nmonths] --, the tables ensemble/member_gauge_kge.csv (one column per gauge, the format of member_kge.csv)
+        and member_gauge_skill.csv (long form), and with statistics the across-member statistics of the hydrographs
+        (xh_ens_stats on the members' slices in HBM) as ensemble/gauge_flow_<stat>.csv."""
+        gd, plan, gs = self.gauges, self.plan, self.plan.gauge_skill
+        if gd is None:
+            return
+        wr = self.wr
+        skill = gskill.skill_table(gd.metrics.download())
+        flow = gd.series.download()
+        folder = os.path.join(self.s.OutputFolder, STATISTICS_DIR)
+        os.makedirs(folder, exist_ok=True)
+        with open(os.path.join(folder, GAUGE_KGE_TABLE), 'w') as fh:
+            fh.write('name,' + ','.join(str(int(g)) for g in gs.ids) + '\n')
+            for name, row in zip(plan.names, skill['kge']):
+                fh.write(name + ',' + ','.join(repr(float(v)) for v in row) + '\n')
+        with open(os.path.join(folder, GAUGE_SKILL_TABLE), 'w') as fh:
+            fh.write('name,gauge_id,' + ','.join(gskill.COLUMNS) + '\n')
+            for k, name in enumerate(plan.names):
+                member = {col: v[k] for col, v in skill.items()}
+                for g in range(gd.ngauge):
+                    fh.write(','.join([name, str(int(gs.ids[g]))] + gskill.skill_fields(member, g)) + '\n')
+        stats = None
+        if plan.statistics:
+            plain = [label for label in _hip.ENS_STAT_BITS if any(label == l for l, _ in plan.statistics)]      # the library's order
+            quant = [(label, q) for label, q in plan.statistics if q is not None]
+            n = gd.ngauge * self.pipe.nmonths
+            outs = [wr.empty((gd.ngauge, self.pipe.nmonths)) for _ in range(len(plain) + len(quant))]
+            try:
+                wr.ens_stats(n, [gd.series.ptr + 8 * k * n for k in range(len(plan.names))], plain, [q for _, q in quant], outs)
+                stats = {label: arr.download() for label, arr in zip(plain + [label for label, _ in quant], outs)}
+            finally:
+                for a in outs:
+                    a.free()
+            labels = gskill.month_labels(self.s)
+            for label, arr in stats.items():
+                gskill.write_flow(os.path.join(folder, GAUGE_STAT_FILE.format(label)), gs, arr, labels)
+        self.gauge_result = {'ids': [int(g) for g in gs.ids], 'skill': skill, 'flow': flow, 'statistics': stats}
+
     def run(self):
         plan = self.plan
         t0 = time.time()
@@ -638,13 +725,14 @@ class _Driver:
             run_schedule(len(plan.names), self.upload, self.compute, self.write, overlap=self.overlap)
             self.member_skill()
             t = time.time()
+            self.member_gauge_skill()
             stats = self.statistics()
             self.timings['statistics'] = time.time() - t
         finally:
             for owned in self.stack.values():
                 for a in owned:
                     a.free()
-            for a in self.member_pars + [v for v in vars(self.skill or SimpleNamespace()).values()
+            for a in self.member_pars + [v for tables in (self.skill, self.gauges) for v in vars(tables or SimpleNamespace()).values()
                                          if isinstance(v, _hip.DeviceArray)]:
                 if a is not None:
                     a.free()
@@ -659,4 +747,5 @@ class _Driver:
             '{} {:.3f}'.format(k, sum(self.timings[k]) / n) for k in ('upload', 'kernels', 'post', 'write')) +
             '; statistics {:.3f} s, total {:.3f} s'.format(self.timings['statistics'], self.timings['total']))
         return EnsembleResult(list(plan.names), list(self.member_dirs) if plan.member_outputs else [], stats, self.timings,
-                              self.forcing_upload, kge=self.kge, kge_basins=list(plan.skill.basins) if plan.skill else None)
+                              self.forcing_upload, kge=self.kge, kge_basins=list(plan.skill.basins) if plan.skill else None,
+                              gauges=self.gauge_result)

@@ -213,6 +213,9 @@ class ConfigReader:
         self.ensemble = None
         if isinstance(c.get('Ensemble'), dict):
             self.configure_ensemble(c['Ensemble'])
+        self.evaluate = None
+        if isinstance(c.get('Evaluate'), dict):
+            self.configure_evaluate(c['Evaluate'])
 
     # ------------------------------------------------------------------ modules
     def configure_pet(self, cfg):
@@ -623,6 +626,28 @@ class ConfigReader:
             obs = cfg['observed'] if isinstance(cfg['observed'], str) else ','.join(cfg['observed'])
             self.ensemble['observed'] = obs if os.path.isabs(obs) else os.path.join(self.root, obs)
             self.ensemble['obs_unit'] = cfg.get('obs_unit')
+
+    def configure_evaluate(self, cfg):
+        """[Evaluate] (not a section of the reference): gauges / gauge_observed / gauge_missing, the file formats, path
+        resolution and meaning of the [Calibrate] keys of the same names (the weight column is read and ignored).  A
+        forward run, or every member of an ensemble, is scored at these stream gauges on its routed flow
+        (evaluate/gauge_skill.py).  Kept as ``self.evaluate``."""
+        if self.calibrate:
+            raise ValidationException('[Evaluate] gauges and Calibrate = 1 exclude each other: the calibration scores its own '
+                                      'gauges and writes its own gauge_kge.csv.')
+        if self.routing_module != 'mrtm':
+            raise ValidationException("[Evaluate] gauges are scored on the routed channel flow (Avg_ChFlow): the run needs "
+                                      "routing_module = mrtm, not '{}'.".format(self.routing_module))
+        if (cfg.get('gauges') is None) != (cfg.get('gauge_observed') is None):
+            raise ValidationException('[Evaluate] {} is missing: gauges and gauge_observed go together, the stations and their '
+                                      'records.'.format('gauges' if cfg.get('gauges') is None else 'gauge_observed'))
+        if cfg.get('gauges') is None:
+            raise ValidationException('[Evaluate] needs gauges and gauge_observed.')
+        try:
+            missing = None if cfg.get('gauge_missing') is None else float(cfg['gauge_missing'])
+        except (TypeError, ValueError):
+            raise ValidationException('[Evaluate] gauge_missing = {!r} is not a number.'.format(cfg.get('gauge_missing')))
+        self.evaluate = {'gauges': cfg['gauges'], 'gauge_observed': cfg['gauge_observed'], 'gauge_missing': missing}
 
     @staticmethod
     def ck_obs_unit(set_calib, unit):

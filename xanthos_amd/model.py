@@ -41,15 +41,17 @@ class Xanthos:
             self.cleanup()
 
     def execute_ensemble(self, members=None, statistics=None, statistics_vars=None, member_outputs=None, overlap=True,
-                         observed=None, obs_unit=None):
+                         observed=None, obs_unit=None, gauges=None, gauge_observed=None, gauge_missing=None):
         """Run ``members`` (a list of (name, overrides) pairs or of dicts with a ``name`` key; overrides as ``execute``
         takes them, ``abcd_pars`` for a member's own parameter table; None: the [Ensemble] section's table) through one
-        device-resident pass; ``observed`` / ``obs_unit``: score every member against observed basin runoff; see
-        ``ensemble.py``.  Returns the EnsembleResult."""
+        device-resident pass; ``observed`` / ``obs_unit``: score every member against observed basin runoff; ``gauges`` /
+        ``gauge_observed`` / ``gauge_missing`` (default: the ini's [Evaluate]): score every member's routed flow at stream
+        gauges; see ``ensemble.py``.  Returns the EnsembleResult."""
         from . import ensemble
         self.stage({})
         try:
-            return ensemble.run(self.config, members, statistics, statistics_vars, member_outputs, overlap, observed, obs_unit)
+            return ensemble.run(self.config, members, statistics, statistics_vars, member_outputs, overlap, observed, obs_unit,
+                                gauges, gauge_observed, gauge_missing)
         finally:
             self.cleanup()
 
@@ -71,7 +73,7 @@ def check_single_device(config):
 
 
 def run_ensemble(config_file, members=None, statistics=None, statistics_vars=None, member_outputs=None, overlap=True,
-                 observed=None, obs_unit=None):
+                 observed=None, obs_unit=None, gauges=None, gauge_observed=None, gauge_missing=None):
     """An ensemble of forcing scenarios through the configuration's grid in one device-resident pass: static data stays
     in HBM, the members stream through with their transfers and write-out overlapped, the across-member statistics are
     formed on the device.  ``members`` / ``statistics`` / ``statistics_vars`` / ``member_outputs`` default to the ini's
@@ -80,10 +82,13 @@ def run_ensemble(config_file, members=None, statistics=None, statistics_vars=Non
     ``abcd_pars``, its own ABCD parameter table: when no member overrides a forcing setting the run's forcing is uploaded
     once and PET is computed once, and a member costs one ABCD and one routing pass.  ``observed`` (a file or ndarray of
     rows [basin id, *, *, value]) with ``obs_unit`` ('km3_per_mth' | 'mm_per_mth') scores every member's runoff against
-    it: ``result.kge`` [members, basins] and ensemble/member_kge.csv.  Returns an EnsembleResult."""
+    it: ``result.kge`` [members, basins] and ensemble/member_kge.csv.  ``gauges`` / ``gauge_observed`` (files in the format of
+    the [Evaluate] keys, which are the default; ``gauge_missing``: a sentinel) score every member's routed flow at stream
+    gauges: ``result.gauge_kge`` [members, gauges], ``result.gauge_skill``, ``result.gauge_flow`` and
+    ensemble/member_gauge_kge.csv, member_gauge_skill.csv.  Returns an EnsembleResult."""
     try:
         return Xanthos(config_file).execute_ensemble(members, statistics, statistics_vars, member_outputs, overlap,
-                                                     observed, obs_unit)
+                                                     observed, obs_unit, gauges, gauge_observed, gauge_missing)
     finally:
         launch.close_group()
 

@@ -674,6 +674,25 @@ def enable_hydro(ini, hpot_start_date='1/1971', hact_start_date='1/1971', q_ex=0
     return ini
 
 
+def enable_evaluate(ini, gauges, gauge_obs, gauge_missing=None):
+    """Switch the scoring at stream gauges on in an .ini written by ``write_example`` / ``write_hgm_example``: ``gauges``
+    (rows [gauge_id, cell_id (1-based)[, weight]]) and ``gauge_obs`` (rows [gauge_id, 0, 0, value], NaN = missing) are
+    written next to the ini's input tree as eval_gauges.csv / eval_gauge_obs.csv and named in an [Evaluate] section;
+    ``gauge_missing``: a sentinel written to the section."""
+    import os
+    text = open(ini).read()
+    inp = os.path.join(os.path.dirname(os.path.abspath(ini)), 'input')
+    os.makedirs(inp, exist_ok=True)
+    paths = os.path.join(inp, 'eval_gauges.csv'), os.path.join(inp, 'eval_gauge_obs.csv')
+    np.savetxt(paths[0], np.atleast_2d(gauges), delimiter=',', fmt='%.17g')
+    np.savetxt(paths[1], gauge_obs, delimiter=',', fmt='%.17g')
+    text += '\n[Evaluate]\ngauges = {}\ngauge_observed = {}\n'.format(*paths)
+    if gauge_missing is not None:
+        text += 'gauge_missing = {!r}\n'.format(float(gauge_missing))
+    open(ini, 'w').write(text)
+    return ini
+
+
 def write_diag_inputs(root, world, seed=17, nvic=30, dir_name='diagnostics'):
     """Write the four comparison tables of the diagnostics (the reference's DiagDir, ini_reader.py:439-445) matched to
     ``world`` under ``root``/input/``dir_name`` and return its path.
