@@ -553,6 +553,39 @@ int xh_basin_kge(xh_ctx *ctx, int64_t ncell, int32_t nmonths, int32_t nbasins, c
 int xh_gauge_skill(xh_ctx *ctx, int64_t ncell, int32_t nmonths, int32_t ngauge, const int32_t *d_gauge_cell,
                    const double *d_flow, const double *d_obs, double *d_series, double *d_metrics);
 
+/* ------------------------------------------------------------------ standardized drought indices
+ * xh_std_index replaces NO function of the reference: xanthos/drought/drought_stats.py knows a fixed threshold and Sheffield
+ * & Wood's severity / intensity / duration only (xh_drought_*).  It forms the standardized runoff index SRI (Shukla & Wood
+ * 2008) -- or, on soil moisture or routed flow, SSI / SSFI -- of d_x [ncell, nmonths] (month 0 a January, nmonths whole
+ * years, <= 4096) in the SPI construction of McKee et al. (1993) at nscale (1..8) accumulation scales h_scale[s] (1..48
+ * months) in one pass over d_x: h_d_index[s] [ncell, nmonths] out, one array per scale.
+ *   Accumulated series  X[c, t] = ((x[c, t-k+1] + x[c, t-k+2]) + ...) + x[c, t], left to right, no contraction; NaN for
+ *     t < k - 1; a NaN term makes X NaN.
+ *   Reference sample    the period of ref_nyear whole years from month ref_month0 (a multiple of 12); for calendar month
+ *     m = t mod 12: R(c, m) = {X[c, u] : u in the period, u mod 12 = m, u >= k - 1} in ascending u, n = |R|.
+ *   dist = 0, gamma (Thom's closed-form approximation of the maximum-likelihood fit, as NCAR climate_indices): an element of
+ *     R NaN or negative -> NaN parameters; n0 = #{s == 0}, q0 = n0 / n; P the positive elements, np = |P| < 4 -> NaN; mu =
+ *     (sum of P from 0.0, ascending) / np; ml = (sum of log P from 0.0, ascending) / np; A = log(mu) - ml, not A > 0 -> NaN;
+ *     alpha = (1 + sqrt(1 + 4 A / 3)) / (4 A), alpha > max_shape -> NaN; beta = mu / alpha.  X NaN or negative or NaN
+ *     parameters -> index NaN; X == 0 -> H = q0; else H = q0 + (1 - q0) P(alpha, X / beta), P the regularized lower incomplete
+ *     gamma function; index = min(max(ndtri(H), -3.09), 3.09).  The parameters are [ncell, 12, 4] tables of (q0, alpha, beta,
+ *     n), an unusable entry four NaNs: h_d_par_out (NULL, or one per scale) receives the fit; h_d_par_in (NULL, or one per
+ *     scale) is used INSTEAD of fitting (a future run indexed against a historic run's fit).
+ *   dist = 1, empirical (Gringorten; Farahmand & AghaKouchak 2015): X NaN, an element of R NaN or n < 4 -> NaN; in = 1 when
+ *     t lies in the reference period; L = #{s < X}, E = #{s == X}, N = n + 1 - in, rank = L + (E + 2 - in) / 2, p = (rank -
+ *     0.44) / (N + 0.12); index = clip(ndtri(p), +-3.09).  h_d_par_out is ignored.
+ * P(a, x) (series / continued fraction, at most 512 iterations, NaN when not converged: none for a <= 1000) and ndtri
+ * (Wichura's AS 241) are csrc/xh_sindex_dev.h.  Fixed operation order, no atomics: two calls give the same bits.
+ * XH_ERR_ARG: a NULL array (other than the two parameter lists), nmonths not a positive multiple of 12, a reference period
+ * that is not whole years inside the series, dist not 0 / 1, h_d_par_in with dist = 1, max_shape <= 0 (or NaN).
+ * XH_ERR_LIMIT: nmonths > 4096, nscale outside 1..8, a scale outside 1..48.  Nothing is launched then.  Asynchronous on the
+ * context's stream, timer "std_index"; nothing is uploaded.                                                          */
+#define XH_STD_INDEX_GAMMA 0
+#define XH_STD_INDEX_EMPIRICAL 1
+int xh_std_index(xh_ctx *ctx, int64_t ncell, int32_t nmonths, int32_t nscale, const int32_t *h_scale, int32_t ref_month0,
+                 int32_t ref_nyear, int32_t dist, double max_shape, const double *d_x, const double *const *h_d_par_in,
+                 double *const *h_d_par_out, double *const *h_d_index);
+
 /* The same objective for SEVERAL basins in one launch, each basin with its own population: one basin alone is only
  * months x ~1.7 us of dependent chain, far too little to fill the chip.  h_ncell [nbasins]; h_pars [nbasins, nmembers,
  * npar]; h_pet_t / h_precip_t / h_tmin_t / h_area: host arrays of nbasins DEVICE pointers ([nmonths, ncell_b] each;

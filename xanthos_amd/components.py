@@ -328,6 +328,7 @@ class Components:
         c.timings, c._host = {}, {}
         c._writer = c._q = c._ac = None
         c.gauge_skill = c.gauge_flow = None
+        c.__dict__.pop('drought_index', None)          # (the result of drought_index() stands in the method's place)
         return c
 
     def _pipeline_args(self, runoff, um, cells=None):
@@ -401,6 +402,26 @@ class Components:
             t0 = time.time()
             DroughtStats(self.s, self.Q, self.Sav)
             logging.info('---Drought Statistics has finished successfully: %s seconds ------' % (time.time() - t0))
+
+    def drought_index(self, keep_on_device=False, write_files=True):
+        """Standardized drought indices of [DroughtIndex] (not in the reference): SRI / SSI / SSFI of the run's runoff, soil
+        moisture or routed flow, from the array in HBM.  Leaves the result as the ATTRIBUTE ``drought_index`` of this
+        object, {scale: ndarray [ncell, nmonths]} (or DeviceArrays with ``keep_on_device``), in place of this method, and
+        the fitted tables as ``drought_index_parameters`` ({scale: [ncell, 12, 4]} or None)."""
+        if getattr(self.s, 'CalculateDroughtIndex', 0) and self.is_root:
+            from .drought.standardized import StandardizedIndex
+            logging.info('---Start Drought Index:')
+            t0 = time.time()
+            var = self.s.drought_index['var']
+            if var == 'q':
+                rows = self._runoff()
+            elif var == 'avgchflow':
+                rows = self._routed_flow()
+            else:
+                rows = self.pipe.out[_RESULTS['Sav']] if self.pipe is not None and 'Sav' not in self._host else self.Sav
+            res = StandardizedIndex(self.s, rows, keep_on_device=keep_on_device, write_files=write_files, grid=self.grid)
+            self.drought_index, self.drought_index_parameters = res.index, res.parameters
+            logging.info('---Drought Index has finished successfully: %s seconds ------' % (time.time() - t0))
 
     def accessible_water(self):
         """Accessible water per basin (components.py:401-409)."""

@@ -31,6 +31,7 @@ class ConfigRunner:
         t = time.time()
         c.accessible_water()          # post-processors, the outputs, the plots: the reference's order (configurations.py:117-139)
         c.drought()
+        c.drought_index()             # ([DroughtIndex], not in the reference: standardized drought indices)
         c.hydropower_potential()
         c.hydropower_actual()
         c.evaluate()                  # ([Evaluate], not in the reference: the routed flow scored at stream gauges)

@@ -93,6 +93,8 @@ class OutWriter:
         return (a, False) if isinstance(a, _hip.DeviceArray) else (self.ctx.upload(np.asarray(a, dtype=np.float64)), True)
 
     def unit_of(self, var):
+        if var == 'drought_index':                      # (drought/standardized.py: a standard normal deviate)
+            return '1'
         return 'm3persec' if var == 'avgchflow' else self.out_unit_str
 
     # ---- device helpers

@@ -269,9 +269,12 @@ def validate(config, members, statistics=(), statistics_vars=None, member_output
     if statistics_vars is None:
         statistics_vars = list(outputs)
     statistics_vars = list(statistics_vars) if stats else []
+    # index<k>: the standardized drought index of [DroughtIndex] at one of its scales (monthly, like the variable it indexes)
+    index_names = ['index{}'.format(k) for k in s.drought_index['scales']] if getattr(s, 'CalculateDroughtIndex', 0) else []
     for v in statistics_vars:
-        if v not in outputs:
-            raise refuse(None, 'statistics_vars', "'{}' is not among the variables the run writes ({})".format(v, ', '.join(outputs)))
+        if v not in outputs and v not in index_names:
+            raise refuse(None, 'statistics_vars', "'{}' is not among the variables the run writes ({})".format(
+                v, ', '.join(list(outputs) + index_names)))
     member_outputs = int(member_outputs)
     if member_outputs not in (0, 1):
         raise refuse(None, 'member_outputs', 'must be 0 or 1')
@@ -302,6 +305,12 @@ def validate(config, members, statistics=(), statistics_vars=None, member_output
     return EnsemblePlan(names=[n for n, _ in members], overrides=[o for _, o in members], statistics=stats,
                         statistics_vars=statistics_vars, member_outputs=member_outputs, ncols=ncols, bytes_needed=need,
                         resident=resident, skill=skill, gauge_skill=gauge_skill)
+
+
+def index_scale(var):
+    """The scale k of a statistics variable 'index<k>' (a standardized drought index), or None."""
+    t = str(var)
+    return int(t[5:]) if t.startswith('index') and t[5:].isdigit() else None
 
 
 def check_fits(plan, free_bytes):
@@ -600,6 +609,7 @@ class _Driver:
             os.makedirs(cfg.OutputFolder, exist_ok=True)
             c.accessible_water()
             c.drought()
+            self._drought_index(c)
             c.hydropower_potential()
             c.hydropower_actual()
             if gd is not None:                            # Components.evaluate()'s two files, from slice k
@@ -611,6 +621,8 @@ class _Driver:
                 gskill.write_skill(os.path.join(cfg.OutputFolder, gskill.SKILL_FILE), gs, gskill.skill_table(raw))
                 gskill.write_flow(os.path.join(cfg.OutputFolder, gskill.FLOW_FILE), gs, flow, gskill.month_labels(cfg))
             c.diagnostics()
+        elif any(index_scale(v) is not None for v in plan.statistics_vars):
+            self._drought_index(c)                        # member_outputs = 0: no files, the arrays for the statistics
         self.timings['post'][k] = time.time() - t
         t = time.time()
         if not (plan.member_outputs or plan.statistics_vars):      # (member_outputs = 0 with observed or gauges alone: only the skill)
@@ -622,6 +634,8 @@ class _Driver:
             c.plots()
         w = c._writer
         for var in plan.statistics_vars:                  # the array as written joins the member stack in HBM
+            if index_scale(var) is not None:              # (the member's index array: _drought_index put it there)
+                continue
             arr, owned = w.get_device(var)
             if not owned:                                 # the run's own array: the next member of this set overwrites it
                 arr = w.ctx.d2d(w.ctx.empty(arr.shape), arr)
@@ -633,6 +647,19 @@ class _Driver:
         if (sk is not None or gd is not None) and w.ctx is not self.wr:
             self.wr.sync()
         self.timings['write'][k] = time.time() - t
+
+    def _drought_index(self, c):
+        """Components.drought_index() of one member: its files with member_outputs = 1, and the arrays of the scales named
+        in statistics_vars onto the member stack (they are the member's own: nothing overwrites them)."""
+        if not getattr(c.s, 'CalculateDroughtIndex', 0):
+            return
+        wanted = {index_scale(v): v for v in self.plan.statistics_vars if index_scale(v) is not None}
+        c.drought_index(keep_on_device=True, write_files=bool(self.plan.member_outputs))      # (no download: files leave from HBM)
+        for k, arr in c.drought_index.items():
+            if k in wanted:
+                self.stack[wanted[k]].append(arr)
+            else:
+                arr.free()
 
     # ---- the across-member statistics
     def statistics(self):
@@ -657,6 +684,12 @@ class _Driver:
             self.stack[var] = []
             result[var] = _Lazy()
             for label, arr in zip(plain + [label for label, _ in quant], outs):
+                if index_scale(var) is not None:
+                    from .drought.standardized import output_stem
+                    w.write_data('{}_{}'.format(output_stem(cfg, s.drought_index['var'], index_scale(var)), label),
+                                 'drought_index', arr, w.time_steps)
+                    dict.__setitem__(result[var], label, arr)
+                    continue
                 filename = os.path.join(cfg.OutputFolder, '{}_{}_{}_{}'.format(var, w.unit_of(var), s.ProjectName, label))
                 w.write_data(filename, var, arr, w.time_steps)      # npy and csv are written from HBM
                 dict.__setitem__(result[var], label, arr)

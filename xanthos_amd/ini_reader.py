@@ -216,6 +216,16 @@ class ConfigReader:
         self.evaluate = None
         if isinstance(c.get('Evaluate'), dict):
             self.configure_evaluate(c['Evaluate'])
+        # [DroughtIndex] (not in the reference): standardized drought indices of the run's runoff, soil moisture or routed flow
+        raw_di = str(p.get('CalculateDroughtIndex', 0)).strip()
+        if raw_di not in ('0', '1'):
+            raise ValidationException("CalculateDroughtIndex must be 0 or 1, not '{}'".format(raw_di))
+        self.CalculateDroughtIndex = int(raw_di)
+        self.drought_index = None
+        if self.CalculateDroughtIndex:
+            if not isinstance(c.get('DroughtIndex'), dict):
+                raise ValidationException('CalculateDroughtIndex = 1 but the config file has no [DroughtIndex] section.')
+            self.configure_drought_index(c['DroughtIndex'])
 
     # ------------------------------------------------------------------ modules
     def configure_pet(self, cfg):
@@ -648,6 +658,81 @@ class ConfigReader:
         except (TypeError, ValueError):
             raise ValidationException('[Evaluate] gauge_missing = {!r} is not a number.'.format(cfg.get('gauge_missing')))
         self.evaluate = {'gauges': cfg['gauges'], 'gauge_observed': cfg['gauge_observed'], 'gauge_missing': missing}
+
+    DROUGHT_INDEX_VARS = ('q', 'soilmoisture', 'avgchflow')
+    DROUGHT_INDEX_DISTRIBUTIONS = ('gamma', 'empirical')
+
+    def configure_drought_index(self, cfg):
+        """[DroughtIndex] (not a section of the reference; drought/standardized.py): index_var = q | soilmoisture | avgchflow
+        (SRI / SSI / SSFI), scales = up to 8 accumulation scales of 1 - 48 months, distribution = gamma (default) |
+        empirical, reference_start_year / reference_end_year (default: the run's years), parameters = <stem> (gamma
+        only: index against the fit of an earlier run instead of fitting; <stem> = <that run's OutputFolder>/<its
+        OutputNameStr>, the table of scale k being <folder>/drought_index_<var>_<k>m_parameters_<name>.npy as that run wrote
+        it -- or any file name with ``{k}`` standing for the scale; relative to RootDir unless absolute), max_shape (default
+        1000).  Kept as ``self.drought_index``; 'parameters' there is {k: file} or None."""
+        def refuse(key, why):
+            raise ValidationException('[DroughtIndex] {} {}'.format(key, why))
+        var = str(cfg.get('index_var', '')).strip().lower()
+        if var not in self.DROUGHT_INDEX_VARS:
+            refuse('index_var', "= '{}' must be one of {}.".format(cfg.get('index_var'), ', '.join(self.DROUGHT_INDEX_VARS)))
+        if var == 'avgchflow' and self.routing_module != 'mrtm':
+            refuse('index_var', "= avgchflow is the routed channel flow: the run needs routing_module = mrtm, not '{}'.".format(
+                self.routing_module))
+        if self.OutputInYear:
+            refuse('needs OutputInYear = 0:', 'the index is monthly and is written with the monthly column labels.')
+        if self.calibrate:
+            refuse('and Calibrate = 1', 'exclude each other: a calibration writes no outputs to index.')
+        raw = cfg.get('scales')
+        raw = [] if raw in (None, '') else (raw if isinstance(raw, list) else [raw])
+        try:
+            scales = [int(x) for x in raw]
+        except (TypeError, ValueError):
+            refuse('scales', '= {!r} are not integers.'.format(cfg.get('scales')))
+        if not 1 <= len(scales) <= 8 or any(k < 1 or k > 48 for k in scales) or len(set(scales)) != len(scales):
+            refuse('scales', '= {!r}: 1 to 8 different accumulation scales of 1 to 48 months.'.format(cfg.get('scales')))
+        dist = str(cfg.get('distribution', 'gamma')).strip().lower()
+        if dist not in self.DROUGHT_INDEX_DISTRIBUTIONS:
+            refuse('distribution', "= '{}' must be gamma or empirical.".format(cfg.get('distribution')))
+        years = {}
+        for key, default in (('reference_start_year', self.StartYear), ('reference_end_year', self.EndYear)):
+            try:
+                years[key] = int(cfg.get(key, default))
+            except (TypeError, ValueError):
+                refuse(key, '= {!r} is not a year.'.format(cfg.get(key)))
+            if not self.StartYear <= years[key] <= self.EndYear:
+                refuse(key, '= {} lies outside the years of the run, {} - {}.'.format(years[key], self.StartYear, self.EndYear))
+        if years['reference_end_year'] < years['reference_start_year']:
+            refuse('reference_end_year', '= {} lies before reference_start_year = {}.'.format(
+                years['reference_end_year'], years['reference_start_year']))
+        try:
+            max_shape = float(cfg.get('max_shape', 1000.0))
+        except (TypeError, ValueError):
+            max_shape = float('nan')
+        if not max_shape > 0:
+            refuse('max_shape', '= {!r} must be a positive number.'.format(cfg.get('max_shape')))
+        stem = cfg.get('parameters')
+        files = None
+        if stem is not None:
+            if dist == 'empirical':
+                refuse('parameters', 'has no meaning with distribution = empirical: nothing is fitted there.')
+            import numpy as np
+            stem = stem if isinstance(stem, str) else ','.join(stem)
+            stem = stem if os.path.isabs(stem) else os.path.join(self.root, stem)
+            files = {}
+            for k in scales:
+                path = stem.replace('{k}', str(k)) if '{k}' in stem else os.path.join(
+                    os.path.dirname(stem), 'drought_index_{}_{}m_parameters_{}.npy'.format(var, k, os.path.basename(stem)))
+                try:
+                    shape = np.load(path, mmap_mode='r').shape
+                except (OSError, ValueError) as exc:
+                    refuse('parameters', '= {}: cannot read {} for scale {}: {}'.format(cfg.get('parameters'), path, k, exc))
+                if tuple(shape) != (self.ncell, 12, 4):
+                    refuse('parameters', '= {}: {} has shape {}, the run needs [{}, 12, 4] (cells, calendar months, q0 / alpha '
+                           '/ beta / n).'.format(cfg.get('parameters'), path, tuple(shape), self.ncell))
+                files[k] = path
+        self.drought_index = {'var': var, 'scales': scales, 'distribution': dist,
+                              'reference_start_year': years['reference_start_year'],
+                              'reference_end_year': years['reference_end_year'], 'max_shape': max_shape, 'parameters': files}
 
     @staticmethod
     def ck_obs_unit(set_calib, unit):

@@ -218,7 +218,7 @@ def write_example(root, world, forcing, start_year, end_year, project='pm_abcd_m
                   routing_spinup=None, output_vars=('q', 'avgchflow'), obs=None, post=False, aggregates=False,
                   hist_flag=True, ch_storage=None, output_format=1, output_in_year=0, set_calibrate=0,
                   calibration_basins='1-2', gauges=None, gauge_obs=None, gauge_missing=None, calibrate_velocity=0,
-                  velocity_scale_bounds=None, velocity_scale=None, gridded=False):
+                  velocity_scale_bounds=None, velocity_scale=None, gridded=False, drought_index=None):
     """Write ``world`` + ``forcing`` as a Xanthos-style input tree under ``root`` and return the .ini path.
 
     Layout and file names follow the reference's example (ini_reader.py:254-279, 353-381, 399-416, 425-437):
@@ -240,6 +240,8 @@ def write_example(root, world, forcing, start_year, end_year, project='pm_abcd_m
     [Calibrate] as given; ``velocity_scale`` (rows [basin_id, scale], or a dict) is written as routing/mrtm/
     velocity_scale.csv and named in [[mrtm]].
     ``gridded=True`` adds ``GriddedOutput = 1`` to [Project]: every per-cell output also as a CF NetCDF map.
+    ``drought_index`` (a dict of ``enable_drought_index``'s arguments, {} for its defaults) appends
+    ``CalculateDroughtIndex = 1`` and a [DroughtIndex] section.
     """
     import os
     inp = os.path.join(root, 'input')
@@ -395,6 +397,8 @@ flow_direction = flow_dir.npy
                   lcy=', '.join(str(y) for y in world.lc_years), rsp=runoff_spinup,
                   rtsp=nmonths if routing_spinup is None else routing_spinup,
                   pr=os.path.join(dirs['ro'], 'pr.npy'), tn=os.path.join(dirs['ro'], 'tmin.npy'), calib=calib))
+    if drought_index is not None:
+        enable_drought_index(ini, **drought_index)
     return ini
 
 
@@ -461,7 +465,7 @@ def hgm_soil(world, seed=7):
 def write_hgm_example(root, world, forcing, start_year, end_year, project='hargreaves_gwam_mrtm_synth', runoff='gwam',
                       runoff_spinup=12, routing_spinup=12, output_vars=('q', 'avgchflow'), hist_flag=True, sav=None,
                       ch_storage=None, precipitation=None, soil=None, routing=True, pet='hargreaves', daylight=None,
-                      obs=None):
+                      obs=None, drought_index=None):
     """Write a hargreaves_gwam_mrtm (``runoff='abcd'``: hargreaves_abcd_mrtm) input tree under ``root``; returns the .ini.
 
     Keys and layout follow the reference's test configuration (xanthos/test/configs/hargreaves_gwam_mrtm.ini; ini_reader.py
@@ -583,6 +587,8 @@ runoff_module = {runoff}
                         nb=world.n_basins, ncell=world.ncell, nrow=world.nrow, ncol=world.ncol, y0=start_year,
                         y1=end_year, ov=', '.join(output_vars), runoff_sec=runoff_sec, future=future,
                         routing_sec=routing_sec))
+    if drought_index is not None:          # (as in write_example)
+        enable_drought_index(ini, **drought_index)
     return ini
 
 
@@ -689,6 +695,18 @@ def enable_evaluate(ini, gauges, gauge_obs, gauge_missing=None):
     text += '\n[Evaluate]\ngauges = {}\ngauge_observed = {}\n'.format(*paths)
     if gauge_missing is not None:
         text += 'gauge_missing = {!r}\n'.format(float(gauge_missing))
+    open(ini, 'w').write(text)
+    return ini
+
+
+def enable_drought_index(ini, index_var='q', scales=(1, 3, 12), **keys):
+    """Switch the standardized drought indices on in an .ini written by one of the example writers: ``CalculateDroughtIndex
+    = 1`` in [Project] and a [DroughtIndex] section with ``index_var``, ``scales`` and whatever else is given
+    (``distribution``, ``reference_start_year``, ``reference_end_year``, ``parameters``, ``max_shape``) as written."""
+    text = open(ini).read()
+    text = text.replace('\n[PET]', '\nCalculateDroughtIndex = 1\n\n[PET]', 1)
+    text += '\n[DroughtIndex]\nindex_var = {}\nscales = {}\n'.format(index_var, ', '.join(str(k) for k in scales))
+    text += ''.join('{} = {}\n'.format(k, v) for k, v in keys.items())
     open(ini, 'w').write(text)
     return ini
 
