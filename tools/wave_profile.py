@@ -1,5 +1,8 @@
-"""Where the cycles of the time-skewed routing kernel go, per unit (library built with `make PROFILE=1`):
-ordinary groups of 16 sub-steps, groups with a month boundary, checks + month bookkeeping.  Run on the GPU box."""
+"""Where the cycles of the time-skewed routing kernel go, per unit (library built with -DXH_WAVE_PROFILE, below):
+ordinary groups of 16 sub-steps, groups with a month boundary, checks + month bookkeeping -- and, per class of unit, the
+split of the last: checks without their waits, the waits, finalize(), the zone exit, what else lies between the runs of
+groups.  The accounting reads a timer at every mark, which the buckets include: indicative, a few per cent slower than the
+shipped build.  Run on the GPU box."""
 import os, sys
 import numpy as np
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
@@ -22,8 +25,17 @@ for rep in range(2):
 st = pipe.plan.stats()
 raw3 = st[:, 3]
 shape = (raw3 & np.uint64(255)).astype(int)
-zg = (raw3 >> np.uint64(44)).astype(np.float64)
+zg = ((raw3 >> np.uint64(44)) & np.uint64(0x7ffff)).astype(np.float64)
+# the diagnostic build packs 32-bit halves (wave_unit(), XH_WAVE_PROFILE): st[1] the run | the waits inside the checks << 32,
+# st[2] housekeeping | checks with their waits << 32, st[5] zone exits | finalize() << 32
+lo32 = np.uint64(0xffffffff)
+raw = st
+waits, total_c = (raw[:, 1] >> np.uint64(32)).astype(np.float64), (raw[:, 1] & lo32).astype(np.float64)
+p_check, p_hk = (raw[:, 2] >> np.uint64(32)).astype(np.float64), (raw[:, 2] & lo32).astype(np.float64)
+p_fin, p_zx = (raw[:, 5] >> np.uint64(32)).astype(np.float64), (raw[:, 5] & lo32).astype(np.float64)
 st = st.astype(np.float64)
+st[:, 1] = total_c
+st[:, 5] = p_check + p_hk + p_fin + p_zx      # "checks + months", as before the split
 nsub = sum(int(d) * 8 for d in pipe.ndays)
 groups = nsub / 16.0
 print('route ms', ms / n, 'reassociated', pipe.plan.rsum_info())
@@ -42,6 +54,27 @@ if pipe.plan.info()['last_tree_kernel'] == 4:      # k_mrtm_rsum: by streams and
                       np.median(zone[sel] / zg[sel] / 16), np.percentile(zone[sel] / zg[sel] / 16, 90),
                       np.median(plain[sel] / nsub), np.median(zone[sel] / nsub), np.median(fin[sel] / nsub), np.median(total[sel] / nsub),
                       (total[sel] / nsub).max()))
+    # the split of "checks + months", per class of unit: cycles per sub-step of the run and, for the three parts that run once a
+    # month, cycles per month
+    nmon = float(len(pipe.ndays))
+    print('split of checks+months (median per class): checks without waits | waits | finalize | zone exit | housekeeping + transitions, '
+          'cycles per sub-step of the run; in brackets cycles per month')
+    classes = [(name, pl, ((shape & 48) == flag) & ((shape & 64) == pl)) for flag, name in ((0, 'no streams'), (16, 'imports'), (32, 'exports'), (48, 'both'))
+               for pl in (0, 64)]
+    slow = np.argsort(-(total - waits))[:40]
+    pace = np.zeros(len(shape), dtype=bool)
+    pace[slow] = True
+    classes.append(('slowest 40', 64, pace))
+    fold = (raw3 >> np.uint64(63)) != 0      # the unit carries folded leaves
+    classes.append(('no str fold', 64, fold & ((shape & 48) == 0)))
+    classes.append(('export fold', 64, fold & ((shape & 48) == 32)))
+    for name, pl, sel in classes:
+        if not sel.any():
+            continue
+        med = lambda x: np.median(x[sel])
+        print('%-11s %-6s n=%4d | %5.1f | %5.1f | %5.1f (%4.0f) | %5.1f (%4.0f) | %5.1f (%4.0f) | outside waits %.0f' % (
+            name, 'single' if pl else 'pair', sel.sum(), med((p_check - waits) / nsub), med(waits / nsub), med(p_fin / nsub), med(p_fin / nmon),
+            med(p_zx / nsub), med(p_zx / nmon), med(p_hk / nsub), med(p_hk / nmon), med((total - waits) / nsub)))
     pu = np.nonzero((shape & 64) == 0)[0] if pipe.plan.rsum_info()['pair_cells'] >= 0 else []
     for u in pu:
         og = groups - zg[u]

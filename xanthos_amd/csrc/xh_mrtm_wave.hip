@@ -14,7 +14,7 @@
 //     Here (a) is branch-free (one compare against an inline constant and five selects on the even sub-steps of a
 //     boundary group), (b) has no exec masks at all (idle block lanes write unused ghost entries and access the rings
 //     out of range, which the buffer resource drops) and one transfer round unless a unit really has more than 8 imports
-//     / outlets, (c) reads one 32-byte record per month.
+//     / outlets, (c) reads one record per month (xh_mrtm_rec.h).
 //
 //   (Rounds 3-5 also had PLAIN units here -- one 8-byte value per term where no upstream neighbour can fire, with a guard, a
 //   learning pass and per-box caches of the cells seen firing: the bit-exact kernel's way to 22.5 ms.  Since round 5 the

@@ -90,36 +90,16 @@ int wave_launch(xh_ctx *ctx, FlowPlan *fp, const FlowSched &s, const FlowIO &io,
         rec_key = xh_fnv1a(rec_key, s.h_g, sizeof(int) * (size_t)(s.nit + 1));
         rec_key = xh_fnv1a(rec_key, s.h_wr, (size_t)s.nit);
         rec_key = xh_fnv1a(rec_key, s.h_secs, sizeof(double) * (size_t)s.nit);
+        rec_key = xh_fnv1a(rec_key, &s.dt, sizeof(double));      // (the records hold 1000 dt / seconds)
         if (rec_key == 0) rec_key = 1;
     }
     if (rec_key != fp->rec_key) {   // the schedule as one record per iteration (+ three zero records: the month bookkeeping looks two ahead)
         fp->rec_key = 0;
         fp->h_rec.assign((size_t)(s.nit + 3) * sizeof(MonthRec), 0);
         MonthRec *h = reinterpret_cast<MonthRec *>(fp->h_rec.data());
-        for (int it = 0; it < s.nit; ++it) {
-            h[it].m = s.h_m[it];
-            h[it].nt = s.h_nt[it];
-            h[it].g = s.h_g[it];
-            h[it].write = s.h_wr[it];
-            h[it].secs = s.h_secs[it];
-            h[it].q_off = q_off(s.h_m[it]);
-        }
-        h[s.nit].g = s.total;
         fp->h_fin.assign((size_t)(s.nit + 2) * sizeof(FinRec), 0);
         FinRec *hf = reinterpret_cast<FinRec *>(fp->h_fin.data());
-        for (int it = 0; it <= s.nit; ++it) {
-            if (it >= 1) {
-                hf[it].m_prev_w = h[it - 1].m | (h[it - 1].write ? FIN_WRITE : 0);
-                hf[it].nt_prev = h[it - 1].nt;
-            }
-            hf[it].nt_prev = std::max(hf[it].nt_prev, 1);
-            hf[it].secs_next1 = it + 1 < s.nit ? h[it + 1].secs : 1.0;
-            hf[it].m_next2 = it + 2 < s.nit ? h[it + 2].m : 0;
-            hf[it].q_off_next2 = q_off(hf[it].m_next2);
-            hf[it].g_next1 = it + 1 <= s.nit ? h[it + 1].g : s.total;
-        }
-        hf[s.nit + 1].nt_prev = 1;
-        hf[s.nit + 1].secs_next1 = 1.0;
+        wave_fill_records(s.nit, s.total, s.dt, s.h_m, s.h_nt, s.h_g, s.h_wr, s.h_secs, q_off, h, hf);
         // pageable source: the copy is staged before the call returns, so h_rec may be rewritten by the next launch
         XH_HIP(ctx, hipMemcpyAsync(d_rec, h, fp->h_rec.size(), hipMemcpyHostToDevice, st));
         XH_HIP(ctx, hipMemcpyAsync(d_fin, hf, fp->h_fin.size(), hipMemcpyHostToDevice, st));

@@ -12,6 +12,7 @@
 #include <type_traits>
 
 #include "xh_mrtm_flow.h"
+#include "xh_mrtm_rec.h"
 
 namespace {
 
@@ -39,25 +40,6 @@ constexpr unsigned FAULT_TEST = 99;
 constexpr int PLACE_KEYS = 16 * 8 * 2 * 16 * 4;      // (xcc, se, sh, cu, simd) of HW_ID / XCC_ID
 
 constexpr int PLACE_WORDS = 16 + PLACE_KEYS + PLACE_KEYS / 4;      // counters, one word per SIMD, one per CU
-
-struct MonthRec {                             // one iteration of the schedule (spin-up months, then every month)
-    int m, nt, g, write;                      // month index, sub-steps, first global sub-step, 1 = simulation pass
-    double secs;
-    long long q_off;                          // byte offset of month m inside a cell's row of the runoff source
-};
-static_assert(sizeof(MonthRec) == 32, "MonthRec is read with one s_load_dwordx8");
-
-// What the month bookkeeping of iteration `it` needs, gathered in one record that is loaded a whole month before it is
-// used (round 3 profile: three dependent loads of month records, each waited for, cost every unit ~30 cycles per sub-step)
-struct FinRec {
-    int m_prev_w, nt_prev;                    // month index (bit 30: write flag) and sub-steps of iteration it - 1
-    int m_next2;                              // month index of iteration it + 2 (its runoff is loaded now)
-    int g_next1;                              // first global sub-step of iteration it + 1
-    double secs_next1;                        // seconds of iteration it + 1
-    long long q_off_next2;                    // byte offset of month m_next2 inside a cell's row of the runoff source
-};
-constexpr int FIN_WRITE = 1 << 30;
-static_assert(sizeof(FinRec) == 32, "FinRec is read with one s_load_dwordx8");
 
 struct WaveArgs {
     const int *cell_of_slot, *lag, *ghost_lag, *export_edge, *ghost_edge, *edge_cons_unit;
@@ -331,14 +313,20 @@ __device__ __forceinline__ void wave_unit(WaveArgsK *ap, char *lds_generic, uint
     MonthRecK *p_rec = (MonthRecK *)A(rec);
     typedef __attribute__((address_space(4))) const FinRec FinRecK;
     FinRecK *p_fin = (FinRecK *)A(fin);
-    auto ld_fin = [&](int i) {
-        FinRec r;
+    auto ld_fin = [&](int i) {           // the fields this kernel uses: the record stays in scalar registers for a month
+        FinRec r = {};
         r.m_prev_w = p_fin[i].m_prev_w;
-        r.nt_prev = p_fin[i].nt_prev;
         r.m_next2 = p_fin[i].m_next2;
         r.g_next1 = p_fin[i].g_next1;
-        r.secs_next1 = p_fin[i].secs_next1;
         r.q_off_next2 = p_fin[i].q_off_next2;
+        r.nt_cur = p_fin[i].nt_cur;
+        if constexpr (RSUM) {            // multiplies by what the host divided once
+            r.erl_scale_next1 = p_fin[i].erl_scale_next1;
+            r.inv_nt_prev = p_fin[i].inv_nt_prev;
+        } else {                         // divides as the reference does
+            r.nt_prev = p_fin[i].nt_prev;
+            r.secs_next1 = p_fin[i].secs_next1;
+        }
         return r;
     };
     FinRec fc = ld_fin(0);               // record of the next month bookkeeping, loaded one month ahead
@@ -392,13 +380,17 @@ __device__ __forceinline__ void wave_unit(WaveArgsK *ap, char *lds_generic, uint
             return *reinterpret_cast<const double *>(reinterpret_cast<const char *>(p_runoff) + q_off + (size_t)row_off);
         };
         const double q0 = ld_q(r0.q_off);
-        erl_n = ((valid ? q0 : 0.0) * area) * 1000.0 / r0.secs;                  // mrtm.py:45
-        if (RSUM) erl_n *= A(dt);
-        if (SGL != 0) gsgl |= (erl_n < -SGL_EPS) ? 2u : 0u;
-        if (FOLD) {
-            const double q0L = *reinterpret_cast<const double *>(reinterpret_cast<const char *>(p_runoff) + r0.q_off + (size_t)row_offL);
-            erlL_n = (((validL ? q0L : 0.0) * areaL) * 1000.0 / r0.secs) * A(dt);
+        if constexpr (RSUM) {      // the factor the later months find in their records (FinRec::erl_scale_next1), same rounding
+            const double scale0 = 1000.0 * A(dt) / r0.secs;
+            erl_n = ((valid ? q0 : 0.0) * area) * scale0;
+            if (FOLD) {
+                const double q0L = *reinterpret_cast<const double *>(reinterpret_cast<const char *>(p_runoff) + r0.q_off + (size_t)row_offL);
+                erlL_n = ((validL ? q0L : 0.0) * areaL) * scale0;
+            }
+        } else {
+            erl_n = ((valid ? q0 : 0.0) * area) * 1000.0 / r0.secs;              // mrtm.py:45
         }
+        if (SGL != 0) gsgl |= (erl_n < -SGL_EPS) ? 2u : 0u;
         if (nit > 1) runoff_fetch(r1.q_off);
     }
     // month outputs leave as groups of OB months per cell (32 bytes = one memory sector)
@@ -517,7 +509,7 @@ __device__ __forceinline__ void wave_unit(WaveArgsK *ap, char *lds_generic, uint
     };
 
     // ---- month bookkeeping for all lanes at once: outputs of iteration it - 1, lateral inflow of iteration it + 1.
-    //      One 32-byte record per month involved (rec has three zero records past the end: no bounds tests).
+    //      One 64-byte record per month (fin has a record past the last bookkeeping: no bounds tests).
     auto finalize = [&](int it) {
         const FinRec f = fc;
         fc = ld_fin(it + 1 <= nit ? it + 1 : nit + 1);      // used a month from now: nobody waits for it
@@ -526,13 +518,13 @@ __device__ __forceinline__ void wave_unit(WaveArgsK *ap, char *lds_generic, uint
         // per sub-step of every unit).
         if (it + 1 < nit) {
             const double qn = runoff_take();
-            erl_n = ((valid ? qn : 0.0) * area) * 1000.0 / f.secs_next1;
-            if (RSUM) erl_n *= dt;
+            if constexpr (RSUM) erl_n = ((valid ? qn : 0.0) * area) * f.erl_scale_next1;
+            else erl_n = ((valid ? qn : 0.0) * area) * 1000.0 / f.secs_next1;
             if (SGL != 0) gsgl |= (erl_n < -SGL_EPS) ? 2u : 0u;
             if (FOLD) {      // (runoff_take has waited for the loads of both staging areas: a unit without streams waits vmcnt(0))
                 const unsigned lo = qstage[2 * LANES + lane], hi = qstage[3 * LANES + lane];
                 const double qnL = __hiloint2double((int)hi, (int)lo);
-                erlL_n = (((validL ? qnL : 0.0) * areaL) * 1000.0 / f.secs_next1) * dt;
+                erlL_n = ((validL ? qnL : 0.0) * areaL) * f.erl_scale_next1;
             }
         }
         if (it >= 1) {
@@ -544,7 +536,8 @@ __device__ __forceinline__ void wave_unit(WaveArgsK *ap, char *lds_generic, uint
                 ob_a[j] = ob_a[j + 1];
             }
             ob_s[OB - 1] = snapS;
-            ob_a[OB - 1] = snapA / (double)f.nt_prev;                          // mrtm.py:80
+            if constexpr (RSUM) ob_a[OB - 1] = snapA * f.inv_nt_prev;
+            else ob_a[OB - 1] = snapA / (double)f.nt_prev;                     // mrtm.py:80
             if (FOLD) {
 #pragma unroll
                 for (int j = 0; j < OB - 1; ++j) {
@@ -552,7 +545,7 @@ __device__ __forceinline__ void wave_unit(WaveArgsK *ap, char *lds_generic, uint
                     ob_aL[j] = ob_aL[j + 1];
                 }
                 ob_sL[OB - 1] = snapSL;
-                ob_aL[OB - 1] = snapAL / (double)f.nt_prev;
+                ob_aL[OB - 1] = snapAL * f.inv_nt_prev;
                 gfold |= (snapSL < -FOLD_EPS) ? 2u : 0u;                       // (NaN storage: as the reference, not a firing)
                 if (write_prev && validL) {
                     if ((m & (OB - 1)) == OB - 1) {
@@ -600,7 +593,6 @@ __device__ __forceinline__ void wave_unit(WaveArgsK *ap, char *lds_generic, uint
             if ((unsigned)f.m_next2 >= mready) alive = wait_months((unsigned)f.m_next2 + 1u);
             if (alive) runoff_fetch(f.q_off_next2);
         }
-        return f.g_next1;
     };
 
     // gathered values of the current sub-step (issued one iteration ago); import blocks in flight (two ahead)
@@ -677,8 +669,7 @@ __device__ __forceinline__ void wave_unit(WaveArgsK *ap, char *lds_generic, uint
 
     const int N = (total + lmax + 1 + GROUP - 1) & ~(GROUP - 1);
     int itz = 0, gz = 0;                 // month whose start zone [gz, gz + lmax] is next (itz == nit: the end zone)
-    int itf = 0, nf = (lmax + 1 + GROUP - 1) & ~(GROUP - 1);     // next month bookkeeping and its iteration
-    int ntz = nit > 0 ? p_rec[0].nt : 0;
+    int nf = (lmax + 1 + GROUP - 1) & ~(GROUP - 1);      // the group behind that zone: the month bookkeeping of itz
 
     // zone: some lanes cross a month start in this group; first: it is the start of the series (the lanes pick up S0)
     // edge: 1 = the start of the series (the lanes pick up S0), 2 = its end (the lanes leave their last outflow for F_end in
@@ -807,8 +798,11 @@ __device__ __forceinline__ void wave_unit(WaveArgsK *ap, char *lds_generic, uint
         }
     };
 
-#ifdef XH_WAVE_PROFILE      // diagnostic build (make PROFILE=1): where a unit's cycles go; st[0] / st[4] / st[5] change meaning
-    unsigned long long prof_zone = 0, prof_fin = 0, prof_t = __builtin_amdgcn_s_memtime();
+#ifdef XH_WAVE_PROFILE      // diagnostic build (make prof / make exprsum EXPFLAGS=-DXH_WAVE_PROFILE): where a unit's cycles go; every
+                            // st[] but st[3] changes meaning (tools/wave_profile.py reads them)
+    // prof_check: check() with its waits; prof_fin: finalize(); prof_zx: the zone exit (the lanes' next crossing); prof_hk: what
+    // else lies between two runs of groups -- the tests, the run's limits, the moves in and out of the unrolled loops
+    unsigned long long prof_zone = 0, prof_fin = 0, prof_check = 0, prof_zx = 0, prof_hk = 0, prof_t = __builtin_amdgcn_s_memtime();
 #define PROF_MARK(acc)                                                  \
     {                                                                   \
         const unsigned long long now_ = __builtin_amdgcn_s_memtime();   \
@@ -823,30 +817,45 @@ __device__ __forceinline__ void wave_unit(WaveArgsK *ap, char *lds_generic, uint
     // per group: a loop with two unrolled bodies left the values in flight (gathered pairs, import blocks) in different
     // registers on its two paths and the compiler reconciled them at the back-edge with ~30 moves behind
     // s_waitcnt vmcnt(0), draining every import load a group had just issued.
-    auto housekeeping = [&](int n) {
-        if (n > 0 && (n & (CH - 1)) == 0) check(n);
-        if (alive && n == nf) {
-            const int g_next = finalize(itf);
-            ++itf;
-            nf = itf <= nit ? ((g_next + lmax + 1 + GROUP - 1) & ~(GROUP - 1)) : INT_MAX;
-        }
-        PROF_MARK(prof_fin)
-    };
+    // The inner loops hold nothing but groups.  A run ends where the kind of group changes or a check is due, and what happens
+    // once a month or once per CH iterations sits HERE, between the runs, in one copy per shape: the check, then -- at the
+    // group behind the zone of month itz, n == nf -- the lanes' next crossing and the month bookkeeping, both out of the
+    // record that has been in scalar registers for a month (no load that is waited for at once).  (With the check left inside
+    // the loops, at the end of the group in front of it, and only the month between the runs: 11.3 - 11.6 ms against
+    // 11.0 - 11.2 at the full grid, profiles/month_path.)  A month is longer than a zone by two groups at the least
+    // (wave_launch refuses the schedule otherwise), so the zones never touch and every zone ends in its own n == nf: the one
+    // after the end zone is n == N, the last bookkeeping.
     int n = 0;
-    while (n < N && alive) {
-        if (itz <= nit && n + GROUP > gz && n <= gz + lmax) {      // boundary groups of month itz
+    for (;;) {
+        PROF_MARK(prof_hk)
+        if (n > 0 && n < N && (n & (CH - 1)) == 0) {
+            check(n);
+            PROF_MARK(prof_check)
+        }
+        if (alive && n == nf) {      // every lane has crossed into month itz: next boundary
+            nx = itz < nit ? nx + fc.nt_cur : INT_MAX;
+            gz = itz < nit ? fc.g_next1 : INT_MAX;
+            PROF_MARK(prof_zx)
+            finalize(itz);
+            ++itz;
+            nf = itz <= nit ? ((gz + lmax + 1 + GROUP - 1) & ~(GROUP - 1)) : INT_MAX;
+            PROF_MARK(prof_fin)
+        }
+        if (n >= N || !alive) break;
+        const int stop = min(N, (n | (CH - 1)) + 1);               // the next check, or the end
+        PROF_MARK(prof_hk)
+        if (n + GROUP > gz) {                                      // boundary groups of month itz (up to n == nf)
             const int edge = itz == 0 ? 1 : (itz == nit ? 2 : 0);
+            const int n_end = min(nf, stop);
             auto zone_run = [&](auto mid_c) {
                 do {
-                    housekeeping(n);
-                    if (!alive) break;
                     ++zone_groups;
                     const int rel = nx - n;      // the sub-step of this group at which the lane crosses (outside 0..15: not in this group)
 #pragma unroll
                     for (int j = 0; j < GROUP; ++j) substep(std::true_type(), mid_c, n, j, edge, rel);
                     n += GROUP;
                     PROF_MARK(prof_zone)
-                } while (n <= gz + lmax && n < N);
+                } while (n < n_end);
             };
 #if XH_WAVE_MIDZONE
             if (edge == 0 && !odd_ok) zone_run(std::true_type());
@@ -854,18 +863,9 @@ __device__ __forceinline__ void wave_unit(WaveArgsK *ap, char *lds_generic, uint
 #else
             zone_run(std::false_type());
 #endif
-            if (alive) {      // every lane has crossed: next boundary
-                nx = itz < nit ? nx + ntz : INT_MAX;
-                ++itz;
-                gz = p_rec[itz <= nit ? itz : nit].g;
-                if (itz > nit) gz = INT_MAX;
-                ntz = p_rec[itz <= nit ? itz : nit].nt;
-            }
         } else {                                                   // ordinary groups up to the next boundary
-            const int n_end = itz <= nit ? min(N, gz & ~(GROUP - 1)) : N;
+            const int n_end = min(stop, gz & ~(GROUP - 1));
             do {
-                housekeeping(n);
-                if (!alive) break;
 #pragma unroll
                 for (int j = 0; j < GROUP; ++j) substep(std::false_type(), std::false_type(), n, j, 0, 0);
                 n += GROUP;
@@ -874,7 +874,6 @@ __device__ __forceinline__ void wave_unit(WaveArgsK *ap, char *lds_generic, uint
         }
     }
     if (alive) {
-        while (itf <= nit) finalize(itf++);
         if (SGL == 2) gsgl |= (xlane && fmin_seen < -SGL_XEPS) ? 4u : 0u;
         if ((FOLD && __any(gfold != 0)) || (SGL != 0 && __any(gsgl != 0))) {
             __hip_atomic_store(A(fault), FAULT_GUARD, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -918,7 +917,12 @@ __device__ __forceinline__ void wave_unit(WaveArgsK *ap, char *lds_generic, uint
 #ifdef XH_WAVE_PROFILE
         st[0] = prof_plain;      // cycles in groups without a month boundary
         st[4] = prof_zone;       // cycles in boundary groups (their number: st[3] >> 44)
-        st[5] = prof_fin;        // checks (with their waits) and month bookkeeping
+        // 32 bits each (a launch is some 3e7 cycles): the whole run and the waits inside the checks; the checks with their waits
+        // and the housekeeping; finalize() and the zone exits
+        st[1] = (cyc & 0xffffffffull) | ((cyc_wait_data + cyc_wait_ring) << 32);
+        st[2] = (prof_check << 32) | (prof_hk & 0xffffffffull);
+        st[5] = (prof_fin << 32) | (prof_zx & 0xffffffffull);
+        if (FOLD) st[3] |= 1ull << 63;      // the unit carries folded leaves (the boundary groups are fewer than 2^19)
 #endif
     }
 }
