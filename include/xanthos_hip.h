@@ -577,7 +577,7 @@ int xh_gauge_skill(xh_ctx *ctx, int64_t ncell, int32_t nmonths, int32_t ngauge, 
  * P(a, x) (series / continued fraction, at most 512 iterations, NaN when not converged: none for a <= 1000) and ndtri
  * (Wichura's AS 241) are csrc/xh_sindex_dev.h.  Fixed operation order, no atomics: two calls give the same bits.
  * XH_ERR_ARG: a NULL array (other than the two parameter lists), nmonths not a positive multiple of 12, a reference period
- * that is not whole years inside the series, dist not 0 / 1, h_d_par_in with dist = 1, max_shape <= 0 (or NaN).
+ * that is not whole years inside the series, dist not 0 / 1 / 2 (2: log-logistic, below), h_d_par_in with dist = 1, max_shape <= 0 (or NaN).
  * XH_ERR_LIMIT: nmonths > 4096, nscale outside 1..8, a scale outside 1..48.  Nothing is launched then.  Asynchronous on the
  * context's stream, timer "std_index"; nothing is uploaded.                                                          */
 #define XH_STD_INDEX_GAMMA 0
@@ -585,6 +585,30 @@ int xh_gauge_skill(xh_ctx *ctx, int64_t ncell, int32_t nmonths, int32_t ngauge, 
 int xh_std_index(xh_ctx *ctx, int64_t ncell, int32_t nmonths, int32_t nscale, const int32_t *h_scale, int32_t ref_month0,
                  int32_t ref_nyear, int32_t dist, double max_shape, const double *d_x, const double *const *h_d_par_in,
                  double *const *h_d_par_out, double *const *h_d_index);
+
+/* ------------------------------------------------------------------ SPI, SPEI and the log-logistic distribution
+ * xh_std_index2 replaces NO function of the reference either (xanthos has no standardized index): it is xh_std_index with an
+ * optional subtrahend, and both entries take a third distribution.  xh_std_index IS xh_std_index2 with d_minus = NULL.
+ *   d_minus (NULL: none) [ncell, nmonths]: the input element is d_x[c, t] - d_minus[c, t], one rounded subtraction (a NaN
+ *     propagates), formed when the row enters LDS; no [ncell, nmonths] scratch array is made.  SPI is the index of
+ *     precipitation, SPEI that of the climatic water balance D = precipitation - PET (Vicente-Serrano et al. 2010).
+ *   dist = 2, log-logistic (three parameters, fitted by unbiased probability-weighted moments, Begueria et al. 2014): an
+ *     element of R NaN or n < 4 -> NaN parameters.  Sort R ascending, s_1 <= ... <= s_n (the order among equal values does not
+ *     matter).  Every sum from 0.0 over ascending i, no contraction, every coefficient the quotient of two exactly converted
+ *     integers, multiplied into s_i:  w0 = (sum s_i) / n;  w1 = (sum s_i ((n - i) / (n - 1))) / n;  w2 = (sum s_i (((n - i)
+ *     (n - i - 1)) / ((n - 1)(n - 2)))) / n;  beta = (2 w1 - w0) / (6 w1 - w0 - 6 w2);  g = (pi / beta) / sin(pi / beta)
+ *     (Gamma(1 + 1/beta) Gamma(1 - 1/beta) in closed form);  alpha = (w0 - 2 w1) beta / g;  gamma = w0 - alpha g.  Usable when
+ *     all three are finite and 1 < |beta| <= max_shape; four NaNs otherwise, and for a constant sample (s_1 = s_n: 0 / 0).  A negatively skewed sample gives beta < 0 and
+ *     alpha < 0: the mirrored distribution with the upper bound gamma.  X NaN or NaN parameters -> index NaN;  z = (X -
+ *     gamma) / alpha;  z <= 0: H = 0 for alpha > 0, H = 1 for alpha < 0;  else H = 1 / (1 + exp(-beta log z));  index =
+ *     clip(ndtri(H), +-3.09), so H = 0 gives exactly -3.09 and H = 1 exactly +3.09.  The parameter tables are [ncell, 12, 4] =
+ *     (alpha, beta, gamma, n); h_d_par_out / h_d_par_in as with gamma, bit for bit.
+ * Errors as xh_std_index, with dist outside 0..2 an XH_ERR_ARG; h_d_par_in stays refused with dist = 1.  LDS: 24 B per month
+ * + 384 B with dist = 2 (98 KB at 4092 months), 16 B per month + 384 B otherwise.  Timer "std_index".                 */
+#define XH_STD_INDEX_LOGLOGISTIC 2
+int xh_std_index2(xh_ctx *ctx, int64_t ncell, int32_t nmonths, int32_t nscale, const int32_t *h_scale, int32_t ref_month0,
+                  int32_t ref_nyear, int32_t dist, double max_shape, const double *d_x, const double *d_minus,
+                  const double *const *h_d_par_in, double *const *h_d_par_out, double *const *h_d_index);
 
 /* The same objective for SEVERAL basins in one launch, each basin with its own population: one basin alone is only
  * months x ~1.7 us of dependent chain, far too little to fill the chip.  h_ncell [nbasins]; h_pars [nbasins, nmembers,

@@ -27,6 +27,7 @@ XH_SRC_F32_LE, XH_SRC_F32_BE, XH_SRC_F64_BE = 1, 2, 3          # xh_widen's kind
 NARROW_KINDS = {np.dtype('<f4'): (XH_SRC_F32_LE, 'f32'), np.dtype('>f4'): (XH_SRC_F32_BE, 'f32be'),
                 np.dtype('>f8'): (XH_SRC_F64_BE, 'f64be')}
 STD_INDEX_DIST = {'gamma': 0, 'empirical': 1}                        # XH_STD_INDEX_* of xh_std_index
+STD_INDEX_DIST2 = dict(STD_INDEX_DIST, loglogistic=2)                # ... and of xh_std_index2
 ENS_STAT_BITS = {'mean': 1, 'std': 2, 'min': 4, 'max': 8}       # XH_ENS_* of xh_ens_stats, in its output order
 
 
@@ -208,6 +209,8 @@ SIGNATURES = {
     'xh_gauge_skill': (c_int, [_P, c_int64, c_int32, c_int32, _P, _P, _P, _P, _P]),
     'xh_std_index': (c_int, [_P, c_int64, c_int32, c_int32, POINTER(c_int32), c_int32, c_int32, c_int32, c_double, _P,
                             POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p)]),
+    'xh_std_index2': (c_int, [_P, c_int64, c_int32, c_int32, POINTER(c_int32), c_int32, c_int32, c_int32, c_double, _P, _P,
+                             POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p)]),
     'xh_synth_forcing': (c_int, [_P, c_uint64, c_double, c_int64, c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
 }
 
@@ -869,13 +872,16 @@ class Context:
                                          _dptr(obs), _dptr(series), _dptr(metrics)))
 
     # ---- standardized drought indices (csrc/xh_sindex.hip)
-    def std_index(self, ncell, nmonths, scales, ref_month0, ref_nyear, dist, max_shape, x, index, par_in=None, par_out=None):
-        """SRI / SSI / SSFI of ``x`` [ncell, nmonths] at the accumulation ``scales`` (months) in one pass (xh_std_index):
-        ``index``: one [ncell, nmonths] array per scale; ``dist``: 'gamma' or 'empirical'; ``par_in`` / ``par_out``: None or
-        one [ncell, 12, 4] table (q0, alpha, beta, n) per scale -- used instead of fitting / receiving the fit.  All
-        DeviceArrays or raw device addresses.  Asynchronous."""
-        if dist not in STD_INDEX_DIST:
-            raise ValueError("unknown distribution '{}' (gamma or empirical)".format(dist))
+    def std_index(self, ncell, nmonths, scales, ref_month0, ref_nyear, dist, max_shape, x, index, par_in=None, par_out=None,
+                  minus=None):
+        """SRI / SSI / SSFI / SPI / SPEI of ``x`` [ncell, nmonths] -- of ``x - minus`` with a subtrahend ``minus`` [ncell,
+        nmonths], subtracted as the rows enter LDS -- at the accumulation ``scales`` (months) in one pass (xh_std_index2):
+        ``index``: one [ncell, nmonths] array per scale; ``dist``: 'gamma', 'empirical' or 'loglogistic'; ``par_in`` /
+        ``par_out``: None or one [ncell, 12, 4] table per scale ((q0, alpha, beta, n) of gamma, (alpha, beta, gamma, n) of
+        loglogistic) -- used instead of fitting / receiving the fit.  All DeviceArrays or raw device addresses.
+        Asynchronous."""
+        if dist not in STD_INDEX_DIST2:
+            raise ValueError("unknown distribution '{}' (gamma, empirical or loglogistic)".format(dist))
         k = np.ascontiguousarray(scales, dtype=np.int32).reshape(-1)
         for name, arrs in (('index', index), ('par_in', par_in), ('par_out', par_out)):
             if arrs is not None and len(arrs) != k.size:
@@ -883,9 +889,9 @@ class Context:
 
         def table(arrs):
             return None if arrs is None else (c_void_p * max(k.size, 1))(*[_dptr(a) for a in arrs])
-        self._check(lib().xh_std_index(self.handle, int(ncell), int(nmonths), int(k.size), k.ctypes.data_as(POINTER(c_int32)),
-                                       int(ref_month0), int(ref_nyear), STD_INDEX_DIST[dist], float(max_shape), _dptr(x),
-                                       table(par_in), table(par_out), table(index)))
+        self._check(lib().xh_std_index2(self.handle, int(ncell), int(nmonths), int(k.size), k.ctypes.data_as(POINTER(c_int32)),
+                                        int(ref_month0), int(ref_nyear), STD_INDEX_DIST2[dist], float(max_shape), _dptr(x),
+                                        _dptr(minus), table(par_in), table(par_out), table(index)))
 
     # ---- bench support
     def synth_forcing(self, seed, ncell, nmonths, lat, out, nan_frac=0.001, cell_ids=None):

@@ -405,7 +405,8 @@ class Components:
 
     def drought_index(self, keep_on_device=False, write_files=True):
         """Standardized drought indices of [DroughtIndex] (not in the reference): SRI / SSI / SSFI of the run's runoff, soil
-        moisture or routed flow, from the array in HBM.  Leaves the result as the ATTRIBUTE ``drought_index`` of this
+        moisture or routed flow, SPI of its precipitation or SPEI of precipitation minus PET (subtracted inside the kernel),
+        from the arrays in HBM.  Leaves the result as the ATTRIBUTE ``drought_index`` of this
         object, {scale: ndarray [ncell, nmonths]} (or DeviceArrays with ``keep_on_device``), in place of this method, and
         the fitted tables as ``drought_index_parameters`` ({scale: [ncell, 12, 4]} or None)."""
         if getattr(self.s, 'CalculateDroughtIndex', 0) and self.is_root:
@@ -413,15 +414,34 @@ class Components:
             logging.info('---Start Drought Index:')
             t0 = time.time()
             var = self.s.drought_index['var']
-            if var == 'q':
+            minus = None
+            if var in ('precip', 'balance'):
+                rows = self._precipitation(var)
+                if var == 'balance':
+                    minus = self.pipe.out[_RESULTS['PET']] if self.pipe is not None and 'PET' not in self._host else self.PET
+            elif var == 'q':
                 rows = self._runoff()
             elif var == 'avgchflow':
                 rows = self._routed_flow()
             else:
                 rows = self.pipe.out[_RESULTS['Sav']] if self.pipe is not None and 'Sav' not in self._host else self.Sav
-            res = StandardizedIndex(self.s, rows, keep_on_device=keep_on_device, write_files=write_files, grid=self.grid)
+            res = StandardizedIndex(self.s, rows, keep_on_device=keep_on_device, write_files=write_files, grid=self.grid,
+                                    minus=minus)
             self.drought_index, self.drought_index_parameters = res.index, res.parameters
             logging.info('---Drought Index has finished successfully: %s seconds ------' % (time.time() - t0))
+
+    def _precipitation(self, var):
+        """The run's precipitation [ncell, nmonths] for SPI / SPEI: the forcing array in HBM after a device-resident
+        simulation, the loader's host array after a run that went stage by stage.  On a sharded run every rank's pipeline
+        holds its own rows of the forcing only, and nothing gathers them: refused rather than indexed in part."""
+        if self.pipe is None:
+            return self.data.precip
+        forcing = getattr(self.pipe, 'forcing', None)
+        rows = forcing.get('precip') if forcing is not None else None
+        if rows is None or tuple(rows.shape) != (self.s.ncell, self.s.nmonths):
+            raise ValidationException("[DroughtIndex] index_var = {} needs the run's whole precipitation array on one GPU: in a run "
+                                      "sharded over several GPUs every rank holds its own cells' rows only.".format(var))
+        return rows
 
     def accessible_water(self):
         """Accessible water per basin (components.py:401-409)."""

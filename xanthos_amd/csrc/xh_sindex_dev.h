@@ -33,6 +33,31 @@
 // ndtri, the inverse of the standard normal distribution function: Wichura's algorithm AS 241, routine PPND16 (Applied
 // Statistics 37, 1988): |p - 1/2| <= 0.425 a rational function of 0.180625 - (p - 1/2)^2 (central region); otherwise of
 // r = sqrt(-log(min(p, 1 - p))) - 1.6 for r <= 5 and of r - 5 beyond (the two tail regions).  About 1e-16 relative.
+//
+// SPI / SPEI AND THE LOG-LOGISTIC DISTRIBUTION.  The definitions above hold unchanged (X at scale k, the sample
+// R(c, m) in ascending u, n = |R|, the clip).
+//   Input with a subtrahend: with a second array y the input element is x[c, t] - y[c, t], one rounded subtraction (a NaN
+//     propagates), formed when the row enters LDS: SPEI is the index of the climatic water balance D = P - PET.
+//   log-logistic fit (three parameters, unbiased probability-weighted moments; Vicente-Serrano et al. 2010, Begueria et al.
+//     2014 "ub-pwm"): an element of R NaN, or n < 4 -> NaN row.  Sort R ascending, s_1 <= ... <= s_n (the order among equal
+//     values does not matter).  Every sum runs from 0.0 over ascending i, no contraction; every coefficient is the quotient of
+//     two exactly converted integers, multiplied into s_i:
+//       w0 = (sum s_i) / n;   w1 = (sum s_i ((n - i) / (n - 1))) / n;   w2 = (sum s_i (((n - i)(n - i - 1)) / ((n - 1)(n - 2)))) / n
+//       beta = (2 w1 - w0) / (6 w1 - w0 - 6 w2);   g = (pi / beta) / sin(pi / beta)   [= Gamma(1 + 1/beta) Gamma(1 - 1/beta)]
+//       alpha = (w0 - 2 w1) beta / g;   gamma = w0 - alpha g.
+//     Usable when all three are finite and 1 < |beta| <= max_shape; otherwise four NaNs (a constant sample, s_1 = s_n: 0 / 0
+//     in exact arithmetic, tested for as such because the rounded sums leave noise over noise; |beta| beyond max_shape: a sample without measurable skew, alpha and gamma differences of huge numbers).  The sign is general:
+//     beta = 1 / (L-skewness), so a negatively skewed sample gives beta < 0 and alpha < 0, and the same formulas describe the
+//     mirrored distribution with the UPPER bound gamma.  The row is (alpha, beta, gamma, n).
+//   log-logistic evaluation: X NaN or a NaN row -> NaN;  z = (X - gamma) / alpha;  z <= 0 (outside the support): H = 0 for
+//     alpha > 0, H = 1 for alpha < 0;  else H = 1 / (1 + exp(-beta log z));  index = clip(ndtri(H), +-3.09): H = 0 gives
+//     exactly -3.09, H = 1 exactly +3.09.
+//   WHERE THE ERROR IS.  (1) the denominator 6 w1 - w0 - 6 w2 is a difference of three numbers of the size of the
+//     sample's mean that leaves a number of the size of its L-skewness times its L-scale: beta, and through it
+//     alpha and gamma, lose log2(|mean| |beta| / L-scale) bits -- the row shifted by 1e6 in the golden inputs is the worst
+//     case there.  (2) exp(beta log z) at large |beta|: the rounding of log z (and of z itself) is multiplied by |beta|, so H
+//     carries a relative error of ~ |beta log z| eps.  Both are shared by every float64 implementation of the definition;
+//     the 40-digit golden has neither.
 #pragma once
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
@@ -232,4 +257,70 @@ XH_SI_HD double xh_si_eval_empirical(double X, S s, int n, int in_ref) {
     const double N = (double)(n + 1 - in_ref);
     const double rank = (double)L + (double)(E + 2 - in_ref) / 2.0;
     return xh_si_clip(xh_si_ndtri((rank - 0.44) / (N + 0.12)));
+}
+
+// ---- log-logistic (SPEI)
+#define XH_SI_LOGLOGISTIC 2
+
+struct XhSiLogLogistic {
+    double alpha, beta, gamma, n;
+};
+
+// Rank by counting: the position of element j of the sample s(i), i in [0, n), in ascending order -- #{s < s_j} + #{s = s_j
+// at an earlier i}.  A NaN counts as larger than every number and equal to another NaN, so the ranks of a sample are always a
+// permutation of 0 .. n - 1 (a scatter by rank writes every slot once), with the NaNs last.
+template <typename S>
+XH_SI_HD int xh_si_rank(S s, int n, int j) {
+    const double x = s(j);
+    const bool xnan = x != x;
+    int r = 0;
+    for (int i = 0; i < n; ++i) {
+        const double v = s(i);
+        const bool less = xnan ? (v == v) : (v < x);
+        const bool same = xnan ? (v != v) : (v == x);
+        r += (less || (same && i < j)) ? 1 : 0;
+    }
+    return r;
+}
+
+// The log-logistic fit of one sample: s(i), i in [0, n), is the sample SORTED ascending (NaNs, if any, last).
+template <typename S>
+XH_SI_HD XhSiLogLogistic xh_si_fit_loglogistic(S s, int n, double max_shape) {
+    const double nan = xh_si_nan();
+    const XhSiLogLogistic bad = {nan, nan, nan, nan};
+    if (n < 4 || s(0) == s(n - 1)) return bad;              // (a constant sample: in exact arithmetic 0 / 0)
+    const double d1 = (double)(n - 1), d2 = (double)((n - 1) * (n - 2));
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+    for (int i = 1; i <= n; ++i) {                          // (i as in the definition: s_1 the smallest)
+        const double v = s(i - 1);
+        s0 += v;
+        s1 += v * ((double)(n - i) / d1);
+        s2 += v * ((double)((n - i) * (n - i - 1)) / d2);
+    }
+    if (s0 != s0) return bad;                               // an element NaN (an infinite one fails the test below)
+    const double w0 = s0 / (double)n, w1 = s1 / (double)n, w2 = s2 / (double)n;
+    const double pi = 3.141592653589793238463;
+    const double beta = (2.0 * w1 - w0) / (6.0 * w1 - w0 - 6.0 * w2);
+    const double pb = pi / beta;
+    const double g = pb / sin(pb);
+    const double alpha = (w0 - 2.0 * w1) * beta / g;
+    const double gamma = w0 - alpha * g;
+    const double inf = __builtin_inf();
+    const bool finite = fabs(alpha) < inf && fabs(beta) < inf && fabs(gamma) < inf;      // (false for a NaN)
+    if (!finite || !(fabs(beta) > 1.0) || !(fabs(beta) <= max_shape)) return bad;
+    const XhSiLogLogistic par = {alpha, beta, gamma, (double)n};
+    return par;
+}
+
+// H(X) of the fitted distribution; NaN for a NaN X or a NaN row.
+XH_SI_HD double xh_si_cdf_loglogistic(double X, const XhSiLogLogistic &par) {
+    if (X != X || par.alpha != par.alpha || par.beta != par.beta || par.gamma != par.gamma) return xh_si_nan();
+    const double z = (X - par.gamma) / par.alpha;
+    if (z != z) return xh_si_nan();                         // (inf - inf, 0 / 0: a table that no fit writes)
+    if (z <= 0.0) return par.alpha > 0.0 ? 0.0 : 1.0;       // outside the support
+    return 1.0 / (1.0 + exp(-par.beta * log(z)));
+}
+
+XH_SI_HD double xh_si_eval_loglogistic(double X, const XhSiLogLogistic &par) {
+    return xh_si_clip(xh_si_ndtri(xh_si_cdf_loglogistic(X, par)));
 }

@@ -326,12 +326,14 @@ class _Aborted(Exception):
     pass
 
 
-def run_schedule(n, upload, compute, write, overlap=True, nsets=2):
+def run_schedule(n, upload, compute, write, overlap=True, nsets=2, write_reads_forcing=False):
     """Members 0 .. n - 1 through ``upload(k, i)``, ``compute(k, i)``, ``write(k, i)`` (i: buffer set).  ``overlap``:
     uploads on one host thread, write-outs on another, computes on the caller's, over ``nsets`` buffer sets -- member k's
     compute starts only when its upload has completed, its write-out when its compute has; a set's forcing is
     uploaded anew only when the compute that read it has ended, its outputs are computed anew only when their write-out
-    has.  Otherwise strictly one after the other on set 0.  The first exception of any stage ends the run and is raised."""
+    has.  ``write_reads_forcing``: the write-out reads its set's forcing too (SPI / SPEI index the precipitation), so that
+    forcing is uploaded anew only when the write-out has ended as well.  Otherwise strictly one after the other on set 0.
+    The first exception of any stage ends the run and is raised."""
     if not overlap:
         for k in range(n):
             upload(k, 0)
@@ -363,6 +365,8 @@ def run_schedule(n, upload, compute, write, overlap=True, nsets=2):
         for k in range(n):
             if k >= nsets:
                 wait(computed[k - nsets])
+                if write_reads_forcing:
+                    wait(written[k - nsets])
             upload(k, k % nsets)
             uploaded[k].set()
 
@@ -592,7 +596,8 @@ class _Driver:
 
     def _write(self, k, i):
         plan, pipe, cfg = self.plan, self.pipe, self.settings[k]
-        view = SimpleNamespace(out=self.sets[i][1], plan=pipe.plan, ncell=pipe.ncell, nmonths=pipe.nmonths)
+        view = SimpleNamespace(out=self.sets[i][1], plan=pipe.plan, ncell=pipe.ncell, nmonths=pipe.nmonths,
+                               forcing=self.sets[i][0])        # (the member's own forcing: SPI / SPEI index it)
         c = self.c.member_view(cfg, view)
         logging.info("---ensemble member '{}' ({} of {})".format(plan.names[k], k + 1, len(plan.names)))
         t = time.time()
@@ -755,7 +760,9 @@ class _Driver:
             len(plan.names), 'overlapped' if self.overlap else 'one after the other'))
         try:
             self.setup()
-            run_schedule(len(plan.names), self.upload, self.compute, self.write, overlap=self.overlap)
+            di = self.c.s.drought_index if getattr(self.c.s, 'CalculateDroughtIndex', 0) else None
+            run_schedule(len(plan.names), self.upload, self.compute, self.write, overlap=self.overlap,
+                         write_reads_forcing=di is not None and di['var'] in ('precip', 'balance'))
             self.member_skill()
             t = time.time()
             self.member_gauge_skill()

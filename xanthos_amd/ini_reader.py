@@ -659,17 +659,20 @@ class ConfigReader:
             raise ValidationException('[Evaluate] gauge_missing = {!r} is not a number.'.format(cfg.get('gauge_missing')))
         self.evaluate = {'gauges': cfg['gauges'], 'gauge_observed': cfg['gauge_observed'], 'gauge_missing': missing}
 
-    DROUGHT_INDEX_VARS = ('q', 'soilmoisture', 'avgchflow')
-    DROUGHT_INDEX_DISTRIBUTIONS = ('gamma', 'empirical')
+    DROUGHT_INDEX_VARS = ('q', 'soilmoisture', 'avgchflow', 'precip', 'balance')
+    DROUGHT_INDEX_DISTRIBUTIONS = ('gamma', 'empirical', 'loglogistic')
 
     def configure_drought_index(self, cfg):
         """[DroughtIndex] (not a section of the reference; drought/standardized.py): index_var = q | soilmoisture | avgchflow
-        (SRI / SSI / SSFI), scales = up to 8 accumulation scales of 1 - 48 months, distribution = gamma (default) |
-        empirical, reference_start_year / reference_end_year (default: the run's years), parameters = <stem> (gamma
-        only: index against the fit of an earlier run instead of fitting; <stem> = <that run's OutputFolder>/<its
+        | precip | balance (SRI / SSI / SSFI of the run's results; SPI of its precipitation, SPEI of precipitation minus the
+        PET module's PET), scales = up to 8 accumulation scales of 1 - 48 months, distribution = gamma (default) |
+        empirical | loglogistic (SPEI's own: balance is negative half the time, where gamma fits nothing),
+        reference_start_year / reference_end_year (default: the run's years), parameters = <stem> (gamma and loglogistic:
+        index against the fit of an earlier run instead of fitting; <stem> = <that run's OutputFolder>/<its
         OutputNameStr>, the table of scale k being <folder>/drought_index_<var>_<k>m_parameters_<name>.npy as that run wrote
-        it -- or any file name with ``{k}`` standing for the scale; relative to RootDir unless absolute), max_shape (default
-        1000).  Kept as ``self.drought_index``; 'parameters' there is {k: file} or None."""
+        it, ..._llparameters_... with loglogistic, whose tables hold other columns -- or any file name with ``{k}`` standing
+        for the scale; relative to RootDir unless absolute), max_shape (default 1000).  Kept as ``self.drought_index``;
+        'parameters' there is {k: file} or None."""
         def refuse(key, why):
             raise ValidationException('[DroughtIndex] {} {}'.format(key, why))
         var = str(cfg.get('index_var', '')).strip().lower()
@@ -678,6 +681,11 @@ class ConfigReader:
         if var == 'avgchflow' and self.routing_module != 'mrtm':
             refuse('index_var', "= avgchflow is the routed channel flow: the run needs routing_module = mrtm, not '{}'.".format(
                 self.routing_module))
+        if var in ('precip', 'balance') and self.runoff_module == 'none':
+            refuse('index_var', "= {} is the index of the run's precipitation, which the runoff module loads: the run needs a "
+                   "runoff_module, not 'none'.".format(var))
+        if var == 'balance' and self.pet_module == 'none':
+            refuse('index_var', "= balance is precipitation minus PET: the run needs a pet_module, not 'none'.")
         if self.OutputInYear:
             refuse('needs OutputInYear = 0:', 'the index is monthly and is written with the monthly column labels.')
         if self.calibrate:
@@ -692,7 +700,7 @@ class ConfigReader:
             refuse('scales', '= {!r}: 1 to 8 different accumulation scales of 1 to 48 months.'.format(cfg.get('scales')))
         dist = str(cfg.get('distribution', 'gamma')).strip().lower()
         if dist not in self.DROUGHT_INDEX_DISTRIBUTIONS:
-            refuse('distribution', "= '{}' must be gamma or empirical.".format(cfg.get('distribution')))
+            refuse('distribution', "= '{}' must be gamma, empirical or loglogistic.".format(cfg.get('distribution')))
         years = {}
         for key, default in (('reference_start_year', self.StartYear), ('reference_end_year', self.EndYear)):
             try:
@@ -719,16 +727,19 @@ class ConfigReader:
             stem = stem if isinstance(stem, str) else ','.join(stem)
             stem = stem if os.path.isabs(stem) else os.path.join(self.root, stem)
             files = {}
+            # (a log-logistic table is (alpha, beta, gamma, n), a gamma table (q0, alpha, beta, n): each under its own name)
+            word = 'llparameters' if dist == 'loglogistic' else 'parameters'
             for k in scales:
                 path = stem.replace('{k}', str(k)) if '{k}' in stem else os.path.join(
-                    os.path.dirname(stem), 'drought_index_{}_{}m_parameters_{}.npy'.format(var, k, os.path.basename(stem)))
+                    os.path.dirname(stem), 'drought_index_{}_{}m_{}_{}.npy'.format(var, k, word, os.path.basename(stem)))
                 try:
                     shape = np.load(path, mmap_mode='r').shape
                 except (OSError, ValueError) as exc:
                     refuse('parameters', '= {}: cannot read {} for scale {}: {}'.format(cfg.get('parameters'), path, k, exc))
                 if tuple(shape) != (self.ncell, 12, 4):
-                    refuse('parameters', '= {}: {} has shape {}, the run needs [{}, 12, 4] (cells, calendar months, q0 / alpha '
-                           '/ beta / n).'.format(cfg.get('parameters'), path, tuple(shape), self.ncell))
+                    refuse('parameters', '= {}: {} has shape {}, the run needs [{}, 12, 4] (cells, calendar months, {}).'
+                           .format(cfg.get('parameters'), path, tuple(shape), self.ncell,
+                                   'alpha / beta / gamma / n' if dist == 'loglogistic' else 'q0 / alpha / beta / n'))
                 files[k] = path
         self.drought_index = {'var': var, 'scales': scales, 'distribution': dist,
                               'reference_start_year': years['reference_start_year'],
