@@ -354,6 +354,9 @@ int xh_mrtm_um_csr(int64_t ncell, const int64_t *h_upid, int64_t *h_indptr, int3
  * Both rest on which cells can fire; the kernel guards the assumptions (folded leaves' storage, lateral inflow and initial
  * storage >= 0, the outflow of the halos' exit cells >= 0) and a trip routes the call again on the plan of pairs.          */
 int xh_route_plan_rsum_info(const xh_route_plan *plan, int64_t info[8]);
+/* Single units of the plan the last call ran on that ran the step WITHOUT the clamp of mrtm.py:54-63 ("linear units": none of
+ * their cells may fire; guarded by the smallest storage each lane has seen).  0 with XH_RSUM_LINEAR=0 and on a plan of pairs. */
+int64_t xh_route_plan_linear_units(const xh_route_plan *plan);
 int xh_route_series(xh_ctx *ctx, xh_route_plan *plan, int32_t nmonths, int32_t spinup_months,
                     const int32_t *h_ndays, double dt,
                     const double *d_flow_dist, const double *d_velocity, const double *d_area,

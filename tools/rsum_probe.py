@@ -105,11 +105,39 @@ uniq, cnt = np.unique(key, return_counts=True)
 shared = np.isin(key, uniq[cnt > 1])
 print('SIMDs in use %d, with two units %d; units on shared SIMDs: cycles/sub-step of wall median %.0f max %.0f' % (
     len(uniq), int((cnt > 1).sum()), np.median(total[shared] / nsub) if shared.any() else 0, (total[shared] / nsub).max() if shared.any() else 0))
-zone = (raw3 >> np.uint64(44)).astype(int)
+zone = ((raw3 >> np.uint64(44)) & np.uint64(0x7ffff)).astype(int)
 print('boundary groups per unit: median %d max %d of %d groups' % (np.median(zone), zone.max(), nsub // 16))
+# the unit's form (bit 63: the kernel wrote it -- bits 24-28 imports, 29-33 outlets, 34 linear, 35 outlet rounds at compile time)
+has_form = bool(((raw3 >> np.uint64(63)) & np.uint64(1)).all())
+n_imp = ((raw3 >> np.uint64(24)) & np.uint64(31)).astype(int)
+n_out = ((raw3 >> np.uint64(29)) & np.uint64(31)).astype(int)
+linear = ((raw3 >> np.uint64(34)) & np.uint64(1)).astype(bool)
+nxr_ct = ((raw3 >> np.uint64(35)) & np.uint64(1)).astype(bool)
+
+
+def form(u):
+    if not has_form:
+        return 'form not recorded by this library'
+    kind = 'pair' if pairu[u] else ('linear' if linear[u] else 'clamping')
+    return '%-8s outlets %2d (%d round%s, %s) imports %2d (%d round%s)' % (
+        kind, n_out[u], (n_out[u] + 7) // 8, '' if n_out[u] in range(1, 9) else 's', 'compile time' if nxr_ct[u] else 'run time',
+        n_imp[u], (n_imp[u] + 7) // 8, '' if n_imp[u] in range(1, 9) else 's')
+
+
+if has_form:
+    single = ~pairu if single_plan else np.zeros(len(shape), dtype=bool)
+    for name, sel in (('linear', single & linear), ('clamping', single & ~linear), ('pair', pairu)):
+        for sname, ssel in (('no outlet', n_out == 0), ('outlets', n_out > 0)):
+            k = sel & ssel
+            if k.any():
+                print('  form %-8s %-9s n=%4d cycles/sub-step outside waits median %.0f max %.0f, of wall median %.0f max %.0f' % (
+                    name, sname, k.sum(), np.median(loop[k] / nsub), (loop[k] / nsub).max(), np.median(total[k] / nsub), (total[k] / nsub).max()))
 order = np.argsort(-loop)
-print('slowest units (cycles/sub-step outside waits, wall, streams, boundary groups, shared SIMD):')
+print('slowest units (cycles/sub-step outside waits, wall, streams, boundary groups, shared SIMD, form):')
 for u in order[:10]:
-    print('  unit %4d  %.0f  %.0f  %s  %d  %s' % (u, loop[u] / nsub, total[u] / nsub, {0: '-', 16: 'in', 32: 'out', 48: 'in+out'}[shape[u] & 48],
-                                               zone[u], 'shared' if shared[u] else ''))
+    print('  unit %4d  %.0f  %.0f  %s  %d  %s  %s' % (u, loop[u] / nsub, total[u] / nsub, {0: '-', 16: 'in', 32: 'out', 48: 'in+out'}[shape[u] & 48],
+                                                   zone[u], 'shared' if shared[u] else '', form(u)))
+print('slowest units of wall:')
+for u in np.argsort(-total)[:10]:
+    print('  unit %4d  %.0f  %.0f  %s  %s' % (u, loop[u] / nsub, total[u] / nsub, {0: '-', 16: 'in', 32: 'out', 48: 'in+out'}[shape[u] & 48], form(u)))
 sys.exit(0 if ok else 3)

@@ -148,6 +148,7 @@ SIGNATURES = {
     'xh_route_plan_info': (c_int, [_P, POINTER(c_int64)]),
     'xh_route_plan_stats': (c_int, [_P, c_int64, _P, POINTER(c_int64)]),
     'xh_route_plan_rsum_info': (c_int, [_P, POINTER(c_int64)]),
+    'xh_route_plan_linear_units': (c_int64, [_P]),
     'xh_route_plan_prepare': (c_int, [_P, _P, _P, _P, c_double]),
     'xh_mrtm_downstream': (c_int, [c_int64, c_int32, c_int32, _P, _P, _P, _P, _P]),
     'xh_mrtm_upstream': (c_int, [c_int64, c_int32, c_int32, _P, _P, _P, _P, _P]),
@@ -217,6 +218,9 @@ SIGNATURES = {
 _lib = None
 
 
+# Exports added without a change of any existing signature: a library from before them still loads (the parent's build beside
+# this package through XH_LIBRARY, for an A/B), and the caller sees None
+OPTIONAL_SYMBOLS = frozenset(['xh_route_plan_linear_units'])
 ABI_VERSION = 7        # xh_abi_version() of the library these signatures describe
 
 
@@ -236,6 +240,8 @@ def lib():
             try:
                 fn = getattr(handle, name)
             except AttributeError:          # a library built from older sources than these signatures
+                if name in OPTIONAL_SYMBOLS:
+                    continue
                 raise HipUnavailable('{} lacks {}: it was built from older sources; rebuild it (make -C xanthos_amd/csrc)'
                                      .format(LIB_PATH, name))
             fn.restype = res
@@ -941,8 +947,11 @@ class RoutePlan:
         """The reassociated plan the last call ran on (xh_route_plan_rsum_info)."""
         arr = (c_int64 * 8)()
         self.ctx._check(lib().xh_route_plan_rsum_info(self.handle, arr))
-        return dict(zip(('units', 'folded', 'fold_disabled', 'prepared_folded', 'pair_cells', 'prepared_pair_cells', 'guard_trips',
-                         'pair_units'), list(arr)))
+        out = dict(zip(('units', 'folded', 'fold_disabled', 'prepared_folded', 'pair_cells', 'prepared_pair_cells', 'guard_trips',
+                        'pair_units'), list(arr)))
+        fn = getattr(lib(), 'xh_route_plan_linear_units', None)      # (OPTIONAL_SYMBOLS: an older library has no such units)
+        out['linear_units'] = int(fn(self.handle)) if fn is not None else 0
+        return out
 
     def stats(self):
         """[units, 6] uint64 per-unit accounting of the last launch (needs XH_FLOW_STATS=1), or None."""

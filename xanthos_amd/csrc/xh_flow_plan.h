@@ -52,6 +52,7 @@ struct FlowTables {
     std::vector<int> fold_of_slot;                               // reassociated form: [units*64] the leaf cell folded into the lane's cell, or -1 (empty: none)
     int n_folded = 0;
     int n_special = -1;                                          // reassociated form: -1 = plan of pairs; >= 0 = single-sum plan with that many cells in pair units
+    int n_linear_units = 0;                                      // single-sum plan: single units none of whose cells may fire (unit_p bit 5)
     int n_pair_units = 0;                                        // single-sum plan: its pair units (the last ones of unit_order)
 };
 

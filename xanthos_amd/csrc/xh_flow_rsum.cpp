@@ -413,7 +413,7 @@ void rsum_partition(const Tree &t, const FlowPlanOptions &opt, int cap, RPart &P
 
 }  // namespace
 
-int flow_rsum_planner_version() { return 8; }
+int flow_rsum_planner_version() { return 9; }      // 9: linear units (unit_p bit 5)
 
 int flow_tables_build_rsum(int n, const int64_t *indptr, const int32_t *indices, const int8_t *sign, const int *comp,
                            int ncomp, const FlowPlanOptions &opt, std::vector<char> &handled, FlowTables &out,
@@ -612,6 +612,20 @@ int flow_tables_build_rsum(int n, const int64_t *indptr, const int32_t *indices,
             out.lane_flags[sl] = (unsigned char)((P.mayfire[c] ? 1 : 0) | ((P.special[c] && ds[c] >= 0 && !P.special[ds[c]]) ? 2 : 0));
         }
 
+    // bit 5: a LINEAR unit -- a single unit none of whose cells may fire (a folded leaf cannot, by what it is): the kernel runs
+    // the step without the clamp on it (wave_unit<LIN>)
+    out.n_linear_units = 0;
+    if (P.n_special >= 0)
+        for (int u = 0; u < nunit; ++u) {
+            if (out.unit_p[u] & 16) continue;
+            bool any = false;
+            for (int k = 0; k < LANES && !any; ++k) any = (out.lane_flags[(int64_t)u * LANES + k] & 1) != 0;
+            if (!any) {
+                out.unit_p[u] |= 32;
+                out.n_linear_units++;
+            }
+        }
+
     std::vector<int> unit_exp(nunit, 0);
     for (int ed = 0; ed < nedge; ++ed) unit_exp[unit_of_piece[piece[P.e_prod[ed]]]]++;
     {   // ---- the claim list (top of the kernel): units without streams by rising cost, then the others.  The SIMDs that hold
@@ -689,8 +703,8 @@ int flow_tables_build_rsum(int n, const int64_t *indptr, const int32_t *indices,
                 if (out.unit_p[u] & 16)
                     fprintf(stderr, "  pair unit %d: %d cells, %d imports, %d outlets, depth %d, lmax %d\n", u, P.unit_cells[u], P.unit_imp[u], unit_exp[u],
                             P.unit_depth[u], out.unit_lmax[u]);
-            fprintf(stderr, "  single-sum plan: %s, %d cells may fire, %d of them in pair form in %d units; %d single units hold no cell that may fire\n",
-                    P.n_special >= 0 ? "yes" : "no", nx, std::max(P.n_special, 0), nsu, quiet);
+            fprintf(stderr, "  single-sum plan: %s, %d cells may fire, %d of them in pair form in %d units; %d single units hold no cell that may fire (%d marked linear)\n",
+                    P.n_special >= 0 ? "yes" : "no", nx, std::max(P.n_special, 0), nsu, quiet, out.n_linear_units);
         }
         fprintf(stderr, "  units by reads (none, A, R, A+R): %d %d %d %d\n  units by lmax/16 (0..13+):", hs[0], hs[1], hs[2], hs[3]);
         for (int k = 0; k < 14; ++k) fprintf(stderr, " %d", hl[k]);
@@ -778,7 +792,8 @@ std::string flow_tables_check_rsum(int n, const int64_t *indptr, const int32_t *
             }
         if (g != imp[u]) return "ghost count";
         if (t.unit_lmax[u] & 15) return "unit lag not a multiple of 16";
-        if ((t.unit_p[u] & ~31) != 0x400) return "shape word of unit " + std::to_string(u);
+        if ((t.unit_p[u] & ~63) != 0x400) return "shape word of unit " + std::to_string(u);
+        if ((t.unit_p[u] & 32) && (t.unit_p[u] & 24) != 8) return "linear flag of unit " + std::to_string(u) + " that is not a single unit";
         if (t.n_special >= 0 ? !(t.unit_p[u] & 8) : (t.unit_p[u] & 24) != 0) return "single-sum flags of unit " + std::to_string(u);
     }
     // what a value stands for: the cells whose flows it sums.  expand(entry) appends them.
@@ -837,6 +852,7 @@ std::string flow_tables_check_rsum(int n, const int64_t *indptr, const int32_t *
             // sits in a pair unit, and so do those neighbours; along its chain no value of a single unit follows one of a pair unit
             if ((int64_t)t.lane_flags.size() != ts) return "lane flags";
             const bool pair_u = (t.unit_p[u] & 16) != 0;
+            if ((t.unit_p[u] & 32) && (t.lane_flags[s] & 1)) return "cell " + std::to_string(c) + " of a linear unit may fire";
             if (pair_u && !(t.lane_flags[s] & 1)) return "cell " + std::to_string(c) + " of a pair unit is not one that may fire";
             if (pair_u && !t.fold_of_slot.empty() && t.fold_of_slot[s] >= 0) return "folded leaf in a pair unit";
             int nx = 0;

@@ -882,6 +882,11 @@ extern "C" int xh_route_plan_rsum_info(const xh_route_plan *plan, int64_t info[8
     return XH_OK;
 }
 
+extern "C" int64_t xh_route_plan_linear_units(const xh_route_plan *plan) {
+    const FlowPlan *fp = plan ? last_reassoc(plan) : nullptr;
+    return fp && xh_env_on("XH_RSUM_LINEAR", true) ? fp->n_linear_units : 0;
+}
+
 RouteChoice route_choose(const xh_route_plan *plan, int flags, double dt, bool fed) {
     RouteChoice c;
     c.whole_graph = (flags & XH_ROUTE_FORCE_FALLBACK) != 0;

@@ -133,6 +133,11 @@ static std::string first_check_path(const xh_ctx *ctx, const xh_route_plan *plan
     uint64_t h = xh_fnv1a(XH_FNV_BASIS, ctx->prop.name);
     h = xh_fnv1a(h, ctx->prop.gcnArchName);
     h = xh_fnv1a(h, __DATE__ " " __TIME__);      // this translation unit's build: a new library build checks again
+    {   // ... and the planner's version, which moves with the shapes the kernels have: a marker left for older shapes does not
+        // vouch for the new ones even where this translation unit was not rebuilt
+        const int pv = flow_rsum_planner_version();
+        h = xh_fnv1a(h, &pv, sizeof(pv));
+    }
     {   // the HIP runtime and the driver the pass was recorded under: the ordering the streams rely on is theirs as much as
         // the silicon's (XH_TEST_RUNTIME_TAG: appended, so that a test can stand in for "another runtime")
         int rt = 0, drv = 0;

@@ -33,6 +33,7 @@ struct FlowPlan {
     FlowBuf d_fold_cell;                 // reassociated form with folded leaves: [units*64] the leaf a lane carries, or -1 (NULL: none)
     int n_folded = 0;
     int n_special = -1;      // reassociated form: -1 = pairs of sums, >= 0 = single-sum plan with that many cells in pair units
+    int n_linear_units = 0;  // single-sum plan: its linear units (unit_p bit 5: the clamp-free step of k_mrtm_rsum)
     int n_pair_units = 0;    // single-sum plan: its pair units (the tail of the claim list; the kernel gives them CUs of their own)
     FlowBuf d_lane_flags;    // single-sum plans: [units*64] bit 0 the cell may fire, bit 1 an exit lane (xh_flow_rsum.cpp)
 };

@@ -423,6 +423,7 @@ int flow_plan_upload(xh_ctx *ctx, const FlowTables &t, FlowPlan **out) {
     fp->n_folded = t.n_folded;
     fp->n_special = t.n_special;
     fp->n_pair_units = t.n_pair_units;
+    fp->n_linear_units = t.n_linear_units;
     if (rc) {
         flow_plan_destroy(fp);
         return XH_ERR_HIP;

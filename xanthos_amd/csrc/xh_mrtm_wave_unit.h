@@ -77,6 +77,7 @@ struct WaveArgs {
     unsigned *fault;
     unsigned long long *stats;
     const int *fold_cell;             // (at the end: k_mrtm_rsum only) [units*64] the leaf cell a lane carries besides its own, or -1; NULL: none
+    int linear;                       // k_mrtm_rsum: 1 = units marked linear (unit_p bit 5) run the clamp-free step; 0 (XH_RSUM_LINEAR=0): they clamp
 };
 
 __device__ __forceinline__ unsigned ld_relaxed(const unsigned *p) {
@@ -185,8 +186,19 @@ template <> struct Val<true> {
 // the outflow of every exit lane (lane_flags bit 1: a cell in pair form whose downstream cell is not) stays >= -SGL_XEPS:
 // then every flow a single unit receives is >= 0, and its cells outside the marked set cannot fire.
 // NXR (pair units): rounds of 8 outlets known at compile time (0, 1; -1: looked up at run time, as every other shape does):
-// the run-time form branches four times per block around the outlet's LDS read and its store.
-template <int PRE, int POST, int NG, bool CHAIN, bool RSUM = false, bool FOLD = false, int SGL = 0, int NXR = -1>
+// the run-time form branches four times per block around the outlet's LDS read and its store.  The single units have it too.
+// LIN (single units, SGL = 1): a LINEAR unit -- none of its cells may fire (lane_flags bit 0 of no lane: unit_p bit 5,
+// xh_flow_rsum.cpp), so min(S1, 0) = 0 in every sub-step and the step is the recurrence itself,
+//     own = fma(S, tauinv, rc)      S = fma(sum F2, dt, fma(S, a, erl dt))      (a folded leaf still adds FL dt to the inner fma)
+// with the month's mean flow kept as the sum of the storages and multiplied by tauinv once a month (finalize()): four fp64
+// operations where the clamping step has nine.  NaN storage propagates as it does there (min(NaN, 0) = 0 leaves S1 - 0).
+// Its guard: the guards of the single-sum plan (gsgl) already imply S1 >= 0; on top of them the unit keeps the smallest
+// storage it has seen (one v_min_f64 per sub-step, NaN ignored) and check() / the end of the run compare it with -SGL_EPS:
+// below that the unit gives up like on every other guard (FAULT_GUARD, the call is routed again on the plan of pairs).
+// The bound and not the bare sign, for the reason FOLD_EPS has: runoff of -1e-17 mm on a dry cell takes an empty storage
+// to about -1e-11 m3, which the reference passes on at once and the recurrence over 1 / (tauinv dt) sub-steps; what the
+// bound lets through is 1e-6 m3 and 1e-10 m3/s, below this form's bar (1e-3 m3, 1e-9 m3/s).
+template <int PRE, int POST, int NG, bool CHAIN, bool RSUM = false, bool FOLD = false, int SGL = 0, int NXR = -1, bool LIN = false>
 __device__ __forceinline__ void wave_unit(WaveArgsK *ap, char *lds_generic, uint2 *xtab,
                                           __attribute__((address_space(3))) unsigned *qstage,
                                           __attribute__((address_space(3))) double *fend, const int unit) {
@@ -218,6 +230,7 @@ __device__ __forceinline__ void wave_unit(WaveArgsK *ap, char *lds_generic, uint
     static_assert(!RSUM || (PRE <= 1 && POST == 0), "reassociated form: one inflow entry");
     static_assert(!FOLD || (RSUM && NG == 0), "folded leaves: reassociated form, units without imports");
     static_assert(SGL == 0 || RSUM, "single-sum plans: reassociated form");
+    static_assert(!LIN || SGL == 1, "linear units: single units of a single-sum plan");
     // the folded leaf of this lane
     const int gcL = FOLD ? A(fold_cell)[slot] : -1;
     const bool validL = FOLD && valid && gcL >= 0;
@@ -237,6 +250,7 @@ __device__ __forceinline__ void wave_unit(WaveArgsK *ap, char *lds_generic, uint
     unsigned gsgl = 0;
     bool xlane = false;
     double fmin_seen = 0.0;                // SGL = 2: smallest outflow of this lane so far
+    double smin_seen = 0.0, Sp = 0.0;      // LIN: smallest storage of this lane so far; its storage one sub-step ago (F_end)
     if (SGL != 0) {
         const unsigned lf = A(lane_flags)[slot];
         xlane = valid && (lf & 2u) != 0;
@@ -448,29 +462,36 @@ __device__ __forceinline__ void wave_unit(WaveArgsK *ap, char *lds_generic, uint
     //      XCD's L2.  No release / acquire fences.  Evidence: every full-size launch of the test suite bit-identical to
     //      the oracle, XH_ROUTE_VALIDATE (the same call routed by the barrier-only kernel and compared on the device),
     //      two contexts routing concurrently, the fuzzers; a violation would show as a wrong bit, a lost wake-up as a
-    //      bounded-wait fault.  Each check asks for the counters the NEXT check will look at (pend_*, loaded by inline
-    //      asm so that no wait is attached to them) and first looks at the values asked for 128 iterations ago; only if
-    //      those do not cover its needs does it poll.  Counters only grow, so a stale value is merely conservative.
-    unsigned seen_ready = 0, seen_done = 0, pend_ready = 0, pend_done = 0;
-    auto load_async = [&](const unsigned *q) {
-        unsigned v;
-        asm volatile("global_load_dword %0, %1, off sc1" : "=v"(v) : "v"(q) : "memory");
-        return v;
-    };
+    //      bounded-wait fault.  Each check asks for both counters FIRST, in front of the wait for the wave's memory operations
+    //      that it begins with anyway, and first looks at those values; only if they do not cover its needs does it poll.
+    //      The two loads and the wait are ONE asm statement: its outputs are defined when it ends, so no register of a load
+    //      in flight exists outside it and nothing the register allocator does around a loop header can read one early.
+    //      (Until the linear units: the counters were asked for at the END of a check for the next one, CH sub-steps ahead,
+    //      in registers that stayed in flight across the unrolled loops -- 31 sites in the ISA where such a register was
+    //      copied at a loop header with no wait between the load and the copy: profiles/pace/ab.txt, profiles/linear_units.)
+    //      Counters only grow, so a value read before the wait is merely conservative.
+    unsigned seen_ready = 0, seen_done = 0;
     auto check = [&](int n) {
         const unsigned long long w0 = __builtin_amdgcn_s_memtime();
+        unsigned now_ready = 0, now_done = 0;
         // Round 5, the default since: EVERY memory operation of the wave has been acknowledged before the counter
         // store -- `s_waitcnt vmcnt(0)` in front of the flag, the guide's measured `sc1` hand-off form, without the L2 write-back
         // of a release fence; the import loads two blocks ahead are simply waited for.  Priced on both kernels, same box,
         // alternating (profiles/round5/fence_mid_ab.txt): 15.08 - 15.38 against 15.16 - 15.36 ms (reassociated), 22.0 - 22.9
         // against 22.3 - 23.0 (bit-exact) -- nothing; the full release / acquire pair costs +76 % / +40 % (XH_ROUTE_FENCED=1).
         // (Until round 4: all but the 8 youngest operations + a publication lag of 64 sub-steps.)
-        // (The second wait is a statement of its own BEHIND the counted one, without register operands: pend_* are registers
-        // of loads in flight until that wait, and anything that makes the compiler copy them first -- a branch around the wait
-        // did, and every stream-linked unit then read counters that had not arrived -- reads garbage.)
-        asm volatile("s_waitcnt vmcnt(8)" : "+v"(pend_ready), "+v"(pend_done) : : "memory");   // older stores acknowledged, pend_* in
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        // The counters ride under that wait (a unit without streams asks for none).  Both loads, whichever the unit needs:
+        // done_p / ready_p of a unit without outlets / imports point at word 0 of their arrays, which lie in one block with
+        // the placement words behind them (wave_launch), so the address is always inside it.
+        if (any_x || any_g)
+            asm volatile("global_load_dword %0, %2, off sc1\n\tglobal_load_dword %1, %3, off sc1\n\ts_waitcnt vmcnt(0)"
+                         : "=&v"(now_done), "=&v"(now_ready)
+                         : "v"(done_p), "v"(ready_p)
+                         : "memory");
+        else
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         if (SGL == 2) gsgl |= (xlane && fmin_seen < -SGL_XEPS) ? 4u : 0u;
+        if (LIN) gsgl |= (smin_seen < -SGL_EPS) ? 8u : 0u;
         if ((FOLD && __any(gfold != 0)) || (SGL != 0 && __any(gsgl != 0))) {      // a folded leaf that can fire after all, a single-sum plan made for other data: the host routes again on the plan of pairs
             __hip_atomic_store(A(fault), FAULT_GUARD, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             alive = false;
@@ -487,7 +508,7 @@ __device__ __forceinline__ void wave_unit(WaveArgsK *ap, char *lds_generic, uint
             if (fenced) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
             if (has_x) __hip_atomic_store(A(ready) + xedge, (unsigned)pub, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             const int need = n + CH - lmax - A(rs);
-            seen_done = max(seen_done, pend_done);
+            seen_done = max(seen_done, now_done);
             if (need > 0 && alive)
                 alive = wave_wait_ge(has_x, done_p, (unsigned)min(need, total), seen_done, A(fault), FAULT_RING_WAIT);
         }
@@ -497,13 +518,11 @@ __device__ __forceinline__ void wave_unit(WaveArgsK *ap, char *lds_generic, uint
                 __hip_atomic_store(A(done) + unit, (unsigned)min(max(n - glmax, 0), total), __ATOMIC_RELAXED,
                                    __HIP_MEMORY_SCOPE_AGENT);
             const int need = min(total, n + CH + GROUP - lag_g);
-            seen_ready = max(seen_ready, pend_ready);
+            seen_ready = max(seen_ready, now_ready);
             alive = wave_wait_ge(has_g && need > 0, ready_p, (unsigned)max(need, 0), seen_ready, A(fault), FAULT_DATA_WAIT);
             if (fenced) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
             asm volatile("" ::: "memory");      // the stream loads stay behind the poll
         }
-        if (any_x) pend_done = load_async(done_p);
-        if (any_g) pend_ready = load_async(ready_p);
         cyc_wait_ring += w1 - w0;
         cyc_wait_data += __builtin_amdgcn_s_memtime() - w1;
     };
@@ -536,7 +555,8 @@ __device__ __forceinline__ void wave_unit(WaveArgsK *ap, char *lds_generic, uint
                 ob_a[j] = ob_a[j + 1];
             }
             ob_s[OB - 1] = snapS;
-            if constexpr (RSUM) ob_a[OB - 1] = snapA * f.inv_nt_prev;
+            if constexpr (LIN) ob_a[OB - 1] = (snapA * tauinv) * f.inv_nt_prev;      // the month's sum of storages -> mean flow
+            else if constexpr (RSUM) ob_a[OB - 1] = snapA * f.inv_nt_prev;
             else ob_a[OB - 1] = snapA / (double)f.nt_prev;                     // mrtm.py:80
             if (FOLD) {
 #pragma unroll
@@ -715,7 +735,7 @@ __device__ __forceinline__ void wave_unit(WaveArgsK *ap, char *lds_generic, uint
                 if (edge == 1) S = c ? S0v : S;
                 if (FOLD && edge == 1) SL = c ? S0L : SL;
                 if (edge == 2) {
-                    if (c) fend[lane] = F;
+                    if (c) fend[lane] = LIN ? Sp * tauinv : F;
                     if (FOLD && c) fend[LANES + lane] = FL;
                 }
             }
@@ -747,7 +767,13 @@ __device__ __forceinline__ void wave_unit(WaveArgsK *ap, char *lds_generic, uint
                 favgL += FL;                                                   // mrtm.py:78
                 base = __builtin_fma(FL, dt, base);
             }
-            if constexpr (SGL == 1) {      // single unit (the template's comment): one running sum, 8-byte entries
+            if constexpr (LIN) {           // linear unit (the template's comment): no cell of it can fire
+                own[(j & (RING - 1)) * NSLOT] = CHAIN ? __builtin_fma(S, tauinv, rc) : F0;
+                favg += S;                                                     // mrtm.py:78, times tauinv in finalize()
+                Sp = S;
+                S = PRE ? __builtin_fma(ac[0], dt, base) : base;               // mrtm.py:51, 69: the branch of :54 is never taken
+                smin_seen = __builtin_fmin(smin_seen, S);                      // ... which check() makes sure of
+            } else if constexpr (SGL == 1) {      // single unit (the template's comment): one running sum, 8-byte entries
                 const double S1 = PRE ? __builtin_fma(ac[0], dt, base) : base;
                 const double m = __builtin_fmin(S1, 0.0);
                 const double f2 = __builtin_fma(m, dtinv, F0);                 // mrtm.py:60
@@ -875,6 +901,7 @@ __device__ __forceinline__ void wave_unit(WaveArgsK *ap, char *lds_generic, uint
     }
     if (alive) {
         if (SGL == 2) gsgl |= (xlane && fmin_seen < -SGL_XEPS) ? 4u : 0u;
+        if (LIN) gsgl |= (smin_seen < -SGL_EPS) ? 8u : 0u;
         if ((FOLD && __any(gfold != 0)) || (SGL != 0 && __any(gsgl != 0))) {
             __hip_atomic_store(A(fault), FAULT_GUARD, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             alive = false;
@@ -910,8 +937,14 @@ __device__ __forceinline__ void wave_unit(WaveArgsK *ap, char *lds_generic, uint
         const unsigned hw = __builtin_amdgcn_s_getreg((4) | (0 << 6) | (31 << 11));
         const unsigned xcc = __builtin_amdgcn_s_getreg((20) | (0 << 6) | (3 << 11));
         st[3] = (unsigned long long)((PRE + POST + (CHAIN ? 1 : 0) + 1) & 15) | (any_g ? 16u : 0u) | (any_x ? 32u : 0u) |
-                (V8 ? 64u : 0u) | (guard_set ? 128u : 0u) | ((unsigned long long)hw << 8) | ((unsigned long long)(xcc & 15u) << 40) |
+                (V8 ? 64u : 0u) | (guard_set ? 128u : 0u) | ((unsigned long long)(hw & 0xffffu) << 8) | ((unsigned long long)(xcc & 15u) << 40) |
                 (zone_groups << 44);
+#ifndef XH_WAVE_PROFILE
+        // the unit's form, where the upper half of HW_ID was (nobody read it): imports, outlets, linear, outlets known at compile
+        // time; bit 63 says that these fields are there (tools/rsum_probe.py)
+        st[3] |= ((unsigned long long)ng << 24) | ((unsigned long long)nx_out << 29) | (LIN ? 1ull << 34 : 0ull) |
+                 (NXR >= 0 ? 1ull << 35 : 0ull) | (1ull << 63);
+#endif
         st[4] = cyc_wait_data;
         st[5] = cyc_wait_ring;
 #ifdef XH_WAVE_PROFILE
