@@ -9,9 +9,14 @@
 //                          (forcing is loaded once per MB members).  Spin-up pass: per-wave sums/counts of the
 //                          three December soil-moisture / groundwater rows.  Simulation pass: per-wave monthly
 //                          sums of runoff (x area x 1e-6 for km3), nansum semantics.
+//   k_calib_march_m        the same march with lanes <-> members and CM cells per wave, for populations that fill waves of
+//                          64 members (below: "member-lane layout"); k_calib_split prepares its member-independent inputs
 //   k_calib_init           per member: basin mean of the Decembers (one basin id for all cells, :143) in fixed
-//                          chunk order
-//   k_calib_series / kge   per (member, month): sum the per-wave partials in fixed order; per member: KGE distance
+//                          chunk order (either layout: the strides of the December partials are arguments)
+//   k_calib_series         per (member, month): sum the per-wave partials in fixed order (either layout: the partials and the
+//                          series are ordered alike)
+//   k_calib_kge[_masked]   per member: the Kling-Gupta distance of xh_kge.h, one workgroup per series; k_calib_kge_m, for the
+//                          member-lane series, sums the months in order, one thread per member, and shares the finish
 //
 // All cross-lane / cross-wave sums run in a fixed order, so results are reproducible run to run.
 #include <cmath>
@@ -20,6 +25,7 @@
 
 #include "xh_abcd_dev.h"
 #include "xh_calib.h"
+#include "xh_kge.h"
 #include "xh_launch.h"
 
 namespace {
@@ -133,9 +139,12 @@ __global__ void __launch_bounds__(64) k_calib_march(const CalibBasin *__restrict
     }
 }
 
-// one thread per (basin, member): basin mean of the three Decembers over the basin's chunks, in chunk order
+// one thread per (basin, member): basin mean of the three Decembers over the basin's chunks, in chunk order.  Partial k of
+// member mem of chunk ch lies at ch * s_chunk + k * s_k + mem * s_mem: (6 nmembers, 1, 6) in the cell-lane layout,
+// (6 nmembers, nmembers, 1) in the member-lane layout.
 __global__ void __launch_bounds__(64) k_calib_init(const CalibBasin *__restrict__ basins,
                                                    const int *__restrict__ active, int nbasins, int nmembers,
+                                                   int64_t s_chunk, int64_t s_k, int64_t s_mem,
                                                    const double *__restrict__ dec_sum, const int *__restrict__ dec_cnt,
                                                    double *__restrict__ sm0, double *__restrict__ gw0) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -146,11 +155,11 @@ __global__ void __launch_bounds__(64) k_calib_init(const CalibBasin *__restrict_
     double sum[6] = {0, 0, 0, 0, 0, 0};
     long long cnt[6] = {0, 0, 0, 0, 0, 0};
     for (int ch = B.chunk0; ch < B.chunk0 + B.nchunks; ++ch) {
-        const int64_t o = ((int64_t)ch * nmembers + mem) * 6;
+        const int64_t o = ch * s_chunk + mem * s_mem;
 #pragma unroll
         for (int k = 0; k < 6; ++k) {
-            sum[k] += dec_sum[o + k];
-            cnt[k] += dec_cnt[o + k];
+            sum[k] += dec_sum[o + k * s_k];
+            cnt[k] += dec_cnt[o + k * s_k];
         }
     }
     double mean[6];
@@ -160,7 +169,8 @@ __global__ void __launch_bounds__(64) k_calib_init(const CalibBasin *__restrict_
     gw0[i] = ((mean[3] + mean[4]) + mean[5]) / 3.0;
 }
 
-// series[basin][member][month] = sum over the basin's chunks of part[chunk][member][month]
+// series[basin][r] = sum over the basin's chunks, in chunk order, of part[chunk][r], r over the basin's (member, month)
+// pairs in the layout's order: [member][month] in the cell-lane layout, [month][member] (d_series_m) in the member-lane one
 __global__ void __launch_bounds__(256) k_calib_series(const CalibBasin *__restrict__ basins,
                                                       const int *__restrict__ active, int nbasins, int nmembers,
                                                       int nmonths, const double *__restrict__ part,
@@ -170,23 +180,11 @@ __global__ void __launch_bounds__(256) k_calib_series(const CalibBasin *__restri
     if (i >= per_basin * nbasins) return;
     const int b = (int)(i / per_basin);
     if (active && !active[b]) return;
-    const int64_t r = i - (int64_t)b * per_basin;                // member * nmonths + month
+    const int64_t r = i - (int64_t)b * per_basin;
     const CalibBasin B = basins[b];
     double acc = 0.0;
     for (int ch = B.chunk0; ch < B.chunk0 + B.nchunks; ++ch) acc += part[(int64_t)ch * per_basin + r];
     series[i] = acc;
-}
-
-__device__ __forceinline__ double block_sum(double v, double *sh) {
-    sh[threadIdx.x] = v;
-    __syncthreads();
-    for (int stride = 128; stride > 0; stride >>= 1) {
-        if ((int)threadIdx.x < stride) sh[threadIdx.x] += sh[threadIdx.x + stride];
-        __syncthreads();
-    }
-    const double r = sh[0];
-    __syncthreads();
-    return r;
 }
 
 // one workgroup per member: ED = sqrt((r-1)^2 + (sd_m/sd_o - 1)^2 + (mean_m/mean_o - 1)^2) (:196-213)
@@ -196,37 +194,12 @@ __global__ void __launch_bounds__(256) k_calib_kge(const int *__restrict__ activ
     __shared__ double sh[256];
     const int mem = blockIdx.x;                          // basin * nmembers + member
     if (active && !active[mem / nmembers]) return;       // block-uniform
-    const double *x = series + (int64_t)mem * nmonths;
-    const double *obs = obs_all + (int64_t)(mem / nmembers) * nmonths;
-    double sx = 0.0, so = 0.0;
-    for (int m = threadIdx.x; m < nmonths; m += blockDim.x) {
-        sx += x[m];
-        so += obs[m];
-    }
-    const double n = (double)nmonths;
-    const double mx = block_sum(sx, sh) / n, mo = block_sum(so, sh) / n;
-    double vxx = 0.0, voo = 0.0, vxo = 0.0;
-    for (int m = threadIdx.x; m < nmonths; m += blockDim.x) {
-        const double dx = x[m] - mx, d_o = obs[m] - mo;
-        vxx += dx * dx;
-        voo += d_o * d_o;
-        vxo += dx * d_o;
-    }
-    vxx = block_sum(vxx, sh);
-    voo = block_sum(voo, sh);
-    vxo = block_sum(vxo, sh);
-    if (threadIdx.x == 0) {
-        const double relvar = sqrt(vxx / n) / sqrt(voo / n);     // np.std, population
-        const double bias = mx / mo;
-        const double c00 = voo / (n - 1.0), c11 = vxx / (n - 1.0), c01 = vxo / (n - 1.0);   // np.corrcoef via np.cov
-        double r = c01 / sqrt(c11) / sqrt(c00);
-        r = r > 1.0 ? 1.0 : (r < -1.0 ? -1.0 : r);               // corrcoef clips to [-1, 1]
-        ed[mem] = sqrt((r - 1.0) * (r - 1.0) + (relvar - 1.0) * (relvar - 1.0) + (bias - 1.0) * (bias - 1.0));
-    }
+    const XhKgeMoments M = xh_kge_moments<false>(nmonths, series + (int64_t)mem * nmonths,
+                                                 obs_all + (int64_t)(mem / nmembers) * nmonths, sh);
+    if (threadIdx.x == 0) ed[mem] = xh_kge_finish(M).ed;
 }
-// Gauge form of the streamflow objective: one workgroup per (gauge, member), ED over the months V whose observation is
-// finite, n = |V|.  The sums are those of k_calib_kge -- the same strided partial sums and the same tree -- and a skipped
-// month adds nothing, so a complete record gives k_calib_kge's bits.
+
+// Gauge form of the streamflow objective: one workgroup per (gauge, member), ED over the months whose observation is finite.
 __global__ void __launch_bounds__(256) k_calib_kge_masked(const int *__restrict__ active,
                                                           const int *__restrict__ gauge_basin, int nmonths, int nmembers,
                                                           const double *__restrict__ series,
@@ -235,40 +208,8 @@ __global__ void __launch_bounds__(256) k_calib_kge_masked(const int *__restrict_
     const int gm = blockIdx.x;                           // gauge * nmembers + member
     const int g = gm / nmembers;
     if (active && !active[gauge_basin[g]]) return;       // block-uniform
-    const double *x = series + (int64_t)gm * nmonths;
-    const double *obs = obs_all + (int64_t)g * nmonths;
-    double sx = 0.0, so = 0.0, cnt = 0.0;
-    for (int m = threadIdx.x; m < nmonths; m += blockDim.x) {
-        const double o = obs[m];
-        if (o - o == 0.0) {                              // finite
-            sx += x[m];
-            so += o;
-            cnt += 1.0;
-        }
-    }
-    const double n = block_sum(cnt, sh);                 // (whole numbers: exact)
-    const double mx = block_sum(sx, sh) / n, mo = block_sum(so, sh) / n;
-    double vxx = 0.0, voo = 0.0, vxo = 0.0;
-    for (int m = threadIdx.x; m < nmonths; m += blockDim.x) {
-        const double o = obs[m];
-        if (o - o == 0.0) {
-            const double dx = x[m] - mx, d_o = o - mo;
-            vxx += dx * dx;
-            voo += d_o * d_o;
-            vxo += dx * d_o;
-        }
-    }
-    vxx = block_sum(vxx, sh);
-    voo = block_sum(voo, sh);
-    vxo = block_sum(vxo, sh);
-    if (threadIdx.x == 0) {
-        const double relvar = sqrt(vxx / n) / sqrt(voo / n);     // np.std, population
-        const double bias = mx / mo;
-        const double c00 = voo / (n - 1.0), c11 = vxx / (n - 1.0), c01 = vxo / (n - 1.0);   // np.corrcoef via np.cov
-        double r = c01 / sqrt(c11) / sqrt(c00);
-        r = r > 1.0 ? 1.0 : (r < -1.0 ? -1.0 : r);               // corrcoef clips to [-1, 1]
-        ed[gm] = sqrt((r - 1.0) * (r - 1.0) + (relvar - 1.0) * (relvar - 1.0) + (bias - 1.0) * (bias - 1.0));
-    }
+    const XhKgeMoments M = xh_kge_moments<true>(nmonths, series + (int64_t)gm * nmonths, obs_all + (int64_t)g * nmonths, sh);
+    if (threadIdx.x == 0) ed[gm] = xh_kge_finish(M).ed;
 }
 
 // one thread per (basin, member): ED_B = (sum w_g ED_g) / (sum w_g) over the basin's gauges in their stored order
@@ -427,49 +368,6 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3)))
     }
 }
 
-__global__ void __launch_bounds__(64) k_calib_init_m(const xh_calib_basin *__restrict__ basins,
-                                                     const int *__restrict__ active, int nbasins, int nmembers,
-                                                     const double *__restrict__ dec_sum, const int *__restrict__ dec_cnt,
-                                                     double *__restrict__ sm0, double *__restrict__ gw0) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= nbasins * nmembers) return;
-    const int b = i / nmembers, mem = i - b * nmembers;
-    if (active && !active[b]) return;
-    const xh_calib_basin B = basins[b];
-    double sum[6] = {0, 0, 0, 0, 0, 0};
-    long long cnt[6] = {0, 0, 0, 0, 0, 0};
-    for (int ch = B.chunk0; ch < B.chunk0 + B.nchunks; ++ch) {
-        const int64_t o = (int64_t)ch * 6 * nmembers + mem;
-#pragma unroll
-        for (int k = 0; k < 6; ++k) {
-            sum[k] += dec_sum[o + (int64_t)k * nmembers];
-            cnt[k] += dec_cnt[o + (int64_t)k * nmembers];
-        }
-    }
-    double mean[6];
-#pragma unroll
-    for (int k = 0; k < 6; ++k) mean[k] = sum[k] / (double)cnt[k];
-    sm0[i] = ((mean[0] + mean[1]) + mean[2]) / 3.0;              // abcd.py:274-278
-    gw0[i] = ((mean[3] + mean[4]) + mean[5]) / 3.0;
-}
-
-// series_m[basin][month][member] = sum over the basin's chunks, in chunk order
-__global__ void __launch_bounds__(256) k_calib_series_m(const xh_calib_basin *__restrict__ basins,
-                                                        const int *__restrict__ active, int nbasins, int nmembers,
-                                                        int nmonths, const double *__restrict__ part,
-                                                        double *__restrict__ series_m) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t per_basin = (int64_t)nmembers * nmonths;
-    if (i >= per_basin * nbasins) return;
-    const int b = (int)(i / per_basin);
-    if (active && !active[b]) return;
-    const int64_t r = i - (int64_t)b * per_basin;                // month * nmembers + member
-    const xh_calib_basin B = basins[b];
-    double acc = 0.0;
-    for (int ch = B.chunk0; ch < B.chunk0 + B.nchunks; ++ch) acc += part[(int64_t)ch * per_basin + r];
-    series_m[i] = acc;
-}
-
 // one thread per (basin, member), lanes along the members: ED as in k_calib_kge, sums over the months in order
 __global__ void __launch_bounds__(64) k_calib_kge_m(const int *__restrict__ active, int nbasins, int nmonths, int nmembers,
                                                     const double *__restrict__ series_m,
@@ -493,12 +391,7 @@ __global__ void __launch_bounds__(64) k_calib_kge_m(const int *__restrict__ acti
         voo += d_o * d_o;
         vxo += dx * d_o;
     }
-    const double relvar = sqrt(vxx / n) / sqrt(voo / n);         // np.std, population
-    const double bias = mx / mo;
-    const double c00 = voo / (n - 1.0), c11 = vxx / (n - 1.0), c01 = vxo / (n - 1.0);   // np.corrcoef via np.cov
-    double r = c01 / sqrt(c11) / sqrt(c00);
-    r = r > 1.0 ? 1.0 : (r < -1.0 ? -1.0 : r);
-    ed[b * nmembers + mem] = sqrt((r - 1.0) * (r - 1.0) + (relvar - 1.0) * (relvar - 1.0) + (bias - 1.0) * (bias - 1.0));
+    ed[b * nmembers + mem] = xh_kge_finish(XhKgeMoments{n, mx, mo, vxx, voo, vxo}).ed;
 }
 
 // d_series [basin][member][month] from d_series_m [basin][month][member] (only when the caller asks for the series)
@@ -624,42 +517,33 @@ int xh_calib_problem_place(xh_ctx *ctx, xh_calib_problem &P, int32_t nmonths, in
     return XH_OK;
 }
 
-// spin-up march + basin mean of the Decembers -> P.d_sm0, P.d_gw0 (member-lane layout)
-static int spinup_m(xh_ctx *ctx, const xh_calib_problem &P, const double *d_pars, const int *d_active) {
+// Both marches take the same arguments; the layout picks the kernel and the members a workgroup covers.
+using MarchKernel = decltype(&k_calib_march<true>);
+
+static dim3 march_grid(const xh_calib_problem &P) {
+    const int per_block = P.member_lanes ? 64 : MB;
+    return dim3((unsigned)P.nchunks, (unsigned)((P.nmembers + per_block - 1) / per_block));
+}
+
+// spin-up march + basin mean of the Decembers -> P.d_sm0, P.d_gw0
+int xh_calib_spinup_enqueue(xh_ctx *ctx, const xh_calib_problem &P, const double *d_pars, const int *d_active) {
     const size_t nbm = (size_t)P.nbasins * P.nmembers;
-    const dim3 grid((unsigned)P.nchunks, (unsigned)((P.nmembers + 63) / 64)), block(64);
+    const int64_t nm = P.nmembers, s_k = P.member_lanes ? nm : 1, s_mem = P.member_lanes ? 1 : 6;
     hipStream_t st = ctx->stream;
-    if (!P.split_done) {
+    if (P.member_lanes && !P.split_done) {
         const int rc = xh_launch(ctx, nullptr, st, k_calib_split, dim3(256, (unsigned)P.nbasins), 256, 0, P.d_basins,
                                  P.nmonths);
         if (rc) return rc;
         P.split_done = true;
     }
-    int rc = xh_launch(ctx, nullptr, st, k_calib_march_m<true>, grid, block, 0, P.d_basins, P.d_chunk_basin, d_active,
-                       P.spinup, P.nmembers, P.npar, P.pstride, d_pars, (const double *)nullptr, (const double *)nullptr, P.d_dec,
-                       P.d_cnt, (double *)nullptr);
-    if (!rc)
-        rc = xh_launch(ctx, nullptr, st, k_calib_init_m, xh_grid(ctx, nbm, 64), 64, 0, P.d_basins, d_active, P.nbasins,
-                       P.nmembers, P.d_dec, P.d_cnt, P.d_sm0, P.d_gw0);
-    return rc;
-}
-
-// the same for the cell-lane layout
-static int spinup_c(xh_ctx *ctx, const xh_calib_problem &P, const double *d_pars, const int *d_active) {
-    const size_t nbm = (size_t)P.nbasins * P.nmembers;
-    const dim3 grid((unsigned)P.nchunks, (unsigned)((P.nmembers + MB - 1) / MB)), block(64);
-    hipStream_t st = ctx->stream;
-    int rc = xh_launch(ctx, nullptr, st, k_calib_march<true>, grid, block, 0, P.d_basins, P.d_chunk_basin, d_active,
+    const MarchKernel march = P.member_lanes ? k_calib_march_m<true> : k_calib_march<true>;
+    int rc = xh_launch(ctx, nullptr, st, march, march_grid(P), dim3(64), 0, P.d_basins, P.d_chunk_basin, d_active,
                        P.spinup, P.nmembers, P.npar, P.pstride, d_pars, (const double *)nullptr, (const double *)nullptr, P.d_dec,
                        P.d_cnt, (double *)nullptr);
     if (!rc)
         rc = xh_launch(ctx, nullptr, st, k_calib_init, xh_grid(ctx, nbm, 64), 64, 0, P.d_basins, d_active, P.nbasins,
-                       P.nmembers, P.d_dec, P.d_cnt, P.d_sm0, P.d_gw0);
+                       P.nmembers, 6 * nm, s_k, s_mem, P.d_dec, P.d_cnt, P.d_sm0, P.d_gw0);
     return rc;
-}
-
-int xh_calib_spinup_enqueue(xh_ctx *ctx, const xh_calib_problem &P, const double *d_pars, const int *d_active) {
-    return P.member_lanes ? spinup_m(ctx, P, d_pars, d_active) : spinup_c(ctx, P, d_pars, d_active);
 }
 
 int xh_calib_kge_enqueue(xh_ctx *ctx, const xh_calib_problem &P, const int *d_active, const double *d_series, double *d_ed) {
@@ -679,29 +563,6 @@ int xh_calib_gauge_score_enqueue(xh_ctx *ctx, const xh_calib_problem &P, const i
                      d_active, P.nbasins, P.nmembers, d_gauge_ptr, d_weight, P.d_ed_gauge, d_ed);
 }
 
-static int calib_enqueue_m(xh_ctx *ctx, const xh_calib_problem &P, const double *d_pars, const int *d_active,
-                           double *d_ed) {
-    const size_t nbm = (size_t)P.nbasins * P.nmembers;
-    const dim3 grid((unsigned)P.nchunks, (unsigned)((P.nmembers + 63) / 64)), block(64);
-    hipStream_t st = ctx->stream;
-    const int rc = xh_timed(ctx, "calib_abcd", st, [&] {
-        int rc = spinup_m(ctx, P, d_pars, d_active);
-        if (!rc)
-            rc = xh_launch(ctx, nullptr, st, k_calib_march_m<false>, grid, block, 0, P.d_basins, P.d_chunk_basin, d_active,
-                           P.nmonths, P.nmembers, P.npar, P.pstride, d_pars, P.d_sm0, P.d_gw0, (double *)nullptr, (int *)nullptr,
-                           P.d_part);
-        return rc;
-    });
-    if (rc) return rc;
-    return xh_timed(ctx, "calib_kge", st, [&] {
-        const int rc = xh_launch(ctx, nullptr, st, k_calib_series_m, xh_grid(ctx, (int64_t)nbm * P.nmonths, 256), 256, 0,
-                                 P.d_basins, d_active, P.nbasins, P.nmembers, P.nmonths, P.d_part, P.d_series_m);
-        if (rc) return rc;
-        return xh_launch(ctx, nullptr, st, k_calib_kge_m, dim3(xh_grid(ctx, P.nmembers, 64), (unsigned)P.nbasins), 64, 0,
-                         d_active, P.nbasins, P.nmonths, P.nmembers, P.d_series_m, P.d_obs, d_ed);
-    });
-}
-
 int xh_calib_series_out(xh_ctx *ctx, const xh_calib_problem &P) {
     if (!P.member_lanes || P.flow) return XH_OK;                 // (the streamflow march writes d_series itself)
     const int64_t n = (int64_t)P.nbasins * P.nmembers * P.nmonths;
@@ -711,26 +572,26 @@ int xh_calib_series_out(xh_ctx *ctx, const xh_calib_problem &P) {
 
 int xh_calib_enqueue(xh_ctx *ctx, const xh_calib_problem &P, const double *d_pars, const int *d_active, double *d_ed) {
     if (P.flow) return xh_calib_flow_enqueue(ctx, P, d_pars, d_active, d_ed);
-    if (P.member_lanes) return calib_enqueue_m(ctx, P, d_pars, d_active, d_ed);
-    const int nmblocks = (P.nmembers + MB - 1) / MB;
     const size_t nbm = (size_t)P.nbasins * P.nmembers;
-    const dim3 grid((unsigned)P.nchunks, (unsigned)nmblocks), block(64);
     hipStream_t st = ctx->stream;
+    const MarchKernel march = P.member_lanes ? k_calib_march_m<false> : k_calib_march<false>;
     const int rc = xh_timed(ctx, "calib_abcd", st, [&] {
-        int rc = spinup_c(ctx, P, d_pars, d_active);
+        int rc = xh_calib_spinup_enqueue(ctx, P, d_pars, d_active);
         if (!rc)
-            rc = xh_launch(ctx, nullptr, st, k_calib_march<false>, grid, block, 0, P.d_basins, P.d_chunk_basin, d_active,
-                           P.nmonths, P.nmembers, P.npar, P.pstride, d_pars, P.d_sm0, P.d_gw0, (double *)nullptr, (int *)nullptr,
-                           P.d_part);
+            rc = xh_launch(ctx, nullptr, st, march, march_grid(P), dim3(64), 0, P.d_basins, P.d_chunk_basin, d_active, P.nmonths, P.nmembers, P.npar,
+                           P.pstride, d_pars, P.d_sm0, P.d_gw0, (double *)nullptr, (int *)nullptr, P.d_part);
         return rc;
     });
     if (rc) return rc;
     return xh_timed(ctx, "calib_kge", st, [&] {
         const int rc = xh_launch(ctx, nullptr, st, k_calib_series, xh_grid(ctx, (int64_t)nbm * P.nmonths, 256), 256, 0,
-                                 P.d_basins, d_active, P.nbasins, P.nmembers, P.nmonths, P.d_part, P.d_series);
+                                 P.d_basins, d_active, P.nbasins, P.nmembers, P.nmonths, P.d_part,
+                                 P.member_lanes ? P.d_series_m : P.d_series);
         if (rc) return rc;
-        return xh_launch(ctx, nullptr, st, k_calib_kge, dim3((unsigned)nbm), 256, 0, d_active, P.nmonths, P.nmembers,
-                         P.d_series, P.d_obs, d_ed);
+        if (P.member_lanes)
+            return xh_launch(ctx, nullptr, st, k_calib_kge_m, dim3(xh_grid(ctx, P.nmembers, 64), (unsigned)P.nbasins), 64, 0,
+                             d_active, P.nbasins, P.nmonths, P.nmembers, P.d_series_m, P.d_obs, d_ed);
+        return xh_calib_kge_enqueue(ctx, P, d_active, P.d_series, d_ed);
     });
 }
 

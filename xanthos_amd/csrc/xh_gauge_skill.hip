@@ -8,34 +8,46 @@
 //                   every access to the row is coalesced) and of the gauge's record.  V = the months with a finite
 //                   observation.  First pass over V: the count, the sums of s and o, of (s - o) and of (s - o)^2 -- and the
 //                   row itself, all months, copied out bit for bit when the caller wants the series.  Second pass: the
-//                   centred second moments.  Every sum is 256 strided partial sums joined by one LDS tree: the sums of
-//                   k_calib_kge_masked (xh_calib.hip), restated here operation for operation, so ED has the bits of the
-//                   calibration's per-gauge ED on the same series and record (tests/test_gpu_gauge_skill.py holds it to that).
+//                   centred second moments.  Every sum is 256 strided partial sums joined by one LDS tree.  n, the means, the
+//                   moments and r, alpha, beta, ED are the masked Kling-Gupta distance of xh_kge.h, the one k_calib_kge_masked
+//                   (xh_calib.hip) calls, so ED has the bits of the calibration's per-gauge ED on the same series and record;
+//                   the kernel itself adds the copy, the two sums of differences and the eight-column row.
 //
 // A skipped month adds nothing; a NaN flow at a month of V reaches every sum it enters and makes columns 1..7 NaN; one outside
 // V is never added.  Fixed order, no atomics: two calls give the same bits.  IEEE arithmetic as written (no contraction).
 #include <cmath>
 
+#include "xh_kge.h"
 #include "xh_launch.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int GS_THREADS = 256;          // the strides and the tree of k_calib_kge_masked
+constexpr int GS_THREADS = 256;          // the strides and the tree of xh_kge.h
 constexpr int GS_COLS = 8;               // n, ED, r, alpha, beta, NSE, PBIAS, RMSE
 
-__device__ __forceinline__ double gs_block_sum(double v, double *sh) {
-    sh[threadIdx.x] = v;
-    __syncthreads();
-    for (int stride = 128; stride > 0; stride >>= 1) {
-        if ((int)threadIdx.x < stride) sh[threadIdx.x] += sh[threadIdx.x + stride];
-        __syncthreads();
+// the gauge cell's row of Avg_ChFlow; a cell outside the grid reads no flow and gives NaN
+struct GaugeRow {
+    const double *x;
+    bool in;                                                         // block-uniform
+    __device__ __forceinline__ double operator[](int m) const { return in ? x[m] : NAN; }
+};
+
+// what the kernel adds to the first pass of the distance: the copy-out and the sums the last three columns need
+struct GaugeSums {
+    double *out;                                                     // the gauge's row of the series output, or NULL
+    double so = 0.0, sd = 0.0, sdd = 0.0;
+    __device__ __forceinline__ void month(int m, double s) const {
+        if (out) out[m] = s;                                         // the row as it lies: a move, the same bits
     }
-    const double r = sh[0];
-    __syncthreads();
-    return r;
-}
+    __device__ __forceinline__ void used(double s, double o) {
+        const double d = s - o;
+        so += o;
+        sd += d;
+        sdd += d * d;
+    }
+};
 
 __global__ void __launch_bounds__(GS_THREADS) k_gauge_skill(int64_t ncell, int nmonths, const int32_t *__restrict__ gauge_cell,
                                                             const double *__restrict__ flow, const double *__restrict__ obs_all,
@@ -43,59 +55,24 @@ __global__ void __launch_bounds__(GS_THREADS) k_gauge_skill(int64_t ncell, int n
     __shared__ double sh[GS_THREADS];
     const int g = blockIdx.x;
     const int64_t cell = gauge_cell[g];
-    const bool in = cell >= 0 && cell < ncell;                       // block-uniform; a cell outside the grid reads no flow
-    const double *x = flow + (in ? cell : 0) * (int64_t)nmonths;
-    const double *obs = obs_all + (int64_t)g * nmonths;
-    double *out = series ? series + (int64_t)g * nmonths : nullptr;
-    double sx = 0.0, so = 0.0, cnt = 0.0, sd = 0.0, sdd = 0.0;
-    for (int m = threadIdx.x; m < nmonths; m += GS_THREADS) {
-        const double o = obs[m];
-        const double s = in ? x[m] : NAN;
-        if (out) out[m] = s;                                         // the row as it lies: a move, the same bits
-        if (o - o == 0.0) {                                          // finite
-            sx += s;
-            so += o;
-            cnt += 1.0;
-            const double d = s - o;
-            sd += d;
-            sdd += d * d;
-        }
-    }
-    const double n = gs_block_sum(cnt, sh);                          // (whole numbers: exact)
-    const double mx = gs_block_sum(sx, sh) / n, mo = gs_block_sum(so, sh) / n;
-    double vxx = 0.0, voo = 0.0, vxo = 0.0;
-    for (int m = threadIdx.x; m < nmonths; m += GS_THREADS) {
-        const double o = obs[m];
-        if (o - o == 0.0) {
-            const double dx = (in ? x[m] : NAN) - mx, d_o = o - mo;
-            vxx += dx * dx;
-            voo += d_o * d_o;
-            vxo += dx * d_o;
-        }
-    }
-    vxx = gs_block_sum(vxx, sh);
-    voo = gs_block_sum(voo, sh);
-    vxo = gs_block_sum(vxo, sh);
-    const double sum_o = gs_block_sum(so, sh);
-    sd = gs_block_sum(sd, sh);
-    sdd = gs_block_sum(sdd, sh);
+    const bool in = cell >= 0 && cell < ncell;                       // block-uniform
+    const GaugeRow x{flow + (in ? cell : 0) * (int64_t)nmonths, in};
+    GaugeSums sums{series ? series + (int64_t)g * nmonths : nullptr};
+    const XhKgeMoments M = xh_kge_moments<true>(nmonths, x, obs_all + (int64_t)g * nmonths, sh, sums);
+    const double sum_o = xh_block_sum256(sums.so, sh);
+    const double sd = xh_block_sum256(sums.sd, sh), sdd = xh_block_sum256(sums.sdd, sh);
     if (threadIdx.x == 0) {
-        const double relvar = sqrt(vxx / n) / sqrt(voo / n);         // np.std, population
-        const double bias = mx / mo;
-        const double c00 = voo / (n - 1.0), c11 = vxx / (n - 1.0), c01 = vxo / (n - 1.0);   // np.corrcoef via np.cov
-        double r = c01 / sqrt(c11) / sqrt(c00);
-        r = r > 1.0 ? 1.0 : (r < -1.0 ? -1.0 : r);                   // corrcoef clips to [-1, 1]; NaN stays NaN
-        const double ed = sqrt((r - 1.0) * (r - 1.0) + (relvar - 1.0) * (relvar - 1.0) + (bias - 1.0) * (bias - 1.0));
-        const bool ok = n >= 2.0;                                    // one month has a mean and a bias but no score
+        const XhKge k = xh_kge_finish(M);
+        const bool ok = M.n >= 2.0;                                  // one month has a mean and a bias but no score
         double *row = metrics + (int64_t)g * GS_COLS;
-        row[0] = n;
-        row[1] = ok ? ed : NAN;
-        row[2] = ok ? r : NAN;
-        row[3] = ok ? relvar : NAN;
-        row[4] = ok ? bias : NAN;
-        row[5] = ok ? 1.0 - sdd / voo : NAN;
+        row[0] = M.n;
+        row[1] = ok ? k.ed : NAN;
+        row[2] = ok ? k.r : NAN;
+        row[3] = ok ? k.relvar : NAN;
+        row[4] = ok ? k.bias : NAN;
+        row[5] = ok ? 1.0 - sdd / M.voo : NAN;
         row[6] = ok ? 100.0 * sd / sum_o : NAN;
-        row[7] = ok ? sqrt(sdd / n) : NAN;
+        row[7] = ok ? sqrt(sdd / M.n) : NAN;
     }
 }
 

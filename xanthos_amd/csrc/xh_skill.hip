@@ -9,16 +9,17 @@
 //                    the lanes of a wave run along 64 consecutive months and every access to a cell's row is one coalesced
 //                    512-byte run; the loop over the basin's cells is the sequential sum, eight rows in flight.  One one-wave
 //                    workgroup per (64 months, basin).  Each Q row of a listed cell is read exactly once.
-//   k_skill_kge      one workgroup per basin over its series and its observations: means, then the centred second
-//                    moments, each as 256 strided partial sums joined by one LDS tree (the sums of k_calib_kge, xh_calib.hip),
-//                    then ED = sqrt((r - 1)^2 + (sd_s / sd_o - 1)^2 + (mean_s / mean_o - 1)^2) as numpy forms it
-//                    (population standard deviations, np.corrcoef through np.cov and clipped to [-1, 1]).
+//   k_skill_kge      one workgroup per basin over its series and its observations: the Kling-Gupta distance of xh_kge.h
+//                    (means, then centred second moments, each as 256 strided partial sums joined by one LDS tree; then
+//                    ED = sqrt((r - 1)^2 + (sd_s / sd_o - 1)^2 + (mean_s / mean_o - 1)^2) as numpy forms it) -- the one
+//                    the calibration's objective calls (k_calib_kge, xh_calib.hip), so the bits are the same.
 //
 // The month split of the first kernel makes the second necessary: the order of the moments' sums must not depend on which
 // workgroup ends first.  Every sum has a fixed order and there is no atomic, so two calls give the same bits.  IEEE
 // arithmetic as written (no contraction): a constant series or a constant record gives NaN, as numpy does.
 #include <cmath>
 
+#include "xh_kge.h"
 #include "xh_launch.h"
 
 #pragma clang fp contract(off)
@@ -62,49 +63,12 @@ __global__ void __launch_bounds__(SKILL_LANES) k_skill_series(int64_t ncell, int
     series[(int64_t)b * nmonths + m] = acc;
 }
 
-__device__ __forceinline__ double skill_block_sum(double v, double *sh) {
-    sh[threadIdx.x] = v;
-    __syncthreads();
-    for (int stride = 128; stride > 0; stride >>= 1) {
-        if ((int)threadIdx.x < stride) sh[threadIdx.x] += sh[threadIdx.x + stride];
-        __syncthreads();
-    }
-    const double r = sh[0];
-    __syncthreads();
-    return r;
-}
-
 __global__ void __launch_bounds__(256) k_skill_kge(int nmonths, const double *__restrict__ series, const double *__restrict__ obs_all,
                                                    double *__restrict__ ed) {
     __shared__ double sh[256];
     const int b = blockIdx.x;
-    const double *x = series + (int64_t)b * nmonths;
-    const double *obs = obs_all + (int64_t)b * nmonths;
-    double sx = 0.0, so = 0.0;
-    for (int m = threadIdx.x; m < nmonths; m += 256) {
-        sx += x[m];
-        so += obs[m];
-    }
-    const double n = (double)nmonths;
-    const double mx = skill_block_sum(sx, sh) / n, mo = skill_block_sum(so, sh) / n;
-    double vxx = 0.0, voo = 0.0, vxo = 0.0;
-    for (int m = threadIdx.x; m < nmonths; m += 256) {
-        const double dx = x[m] - mx, d_o = obs[m] - mo;
-        vxx += dx * dx;
-        voo += d_o * d_o;
-        vxo += dx * d_o;
-    }
-    vxx = skill_block_sum(vxx, sh);
-    voo = skill_block_sum(voo, sh);
-    vxo = skill_block_sum(vxo, sh);
-    if (threadIdx.x == 0) {
-        const double relvar = sqrt(vxx / n) / sqrt(voo / n);     // np.std, population
-        const double bias = mx / mo;
-        const double c00 = voo / (n - 1.0), c11 = vxx / (n - 1.0), c01 = vxo / (n - 1.0);   // np.corrcoef via np.cov
-        double r = c01 / sqrt(c11) / sqrt(c00);
-        r = r > 1.0 ? 1.0 : (r < -1.0 ? -1.0 : r);               // corrcoef clips to [-1, 1]; NaN stays NaN
-        ed[b] = sqrt((r - 1.0) * (r - 1.0) + (relvar - 1.0) * (relvar - 1.0) + (bias - 1.0) * (bias - 1.0));
-    }
+    const XhKgeMoments M = xh_kge_moments<false>(nmonths, series + (int64_t)b * nmonths, obs_all + (int64_t)b * nmonths, sh);
+    if (threadIdx.x == 0) ed[b] = xh_kge_finish(M).ed;
 }
 
 }  // namespace
