@@ -613,6 +613,42 @@ int xh_std_index2(xh_ctx *ctx, int64_t ncell, int32_t nmonths, int32_t nscale, c
                   int32_t ref_nyear, int32_t dist, double max_shape, const double *d_x, const double *d_minus,
                   const double *const *h_d_par_in, double *const *h_d_par_out, double *const *h_d_index);
 
+/* ------------------------------------------------------------------ trend per row: Mann-Kendall and Theil-Sen
+ * xh_trend replaces NO function of the reference: xanthos has no trend statistic.  Per row r of d_x (nrows rows of row_stride
+ * doubles) it takes the window x[0 .. ncol) = d_x[r, col0 .. col0 + ncol) and writes d_out[r, 0 .. 10):
+ *   n, s, var_s, z, p, slope, intercept, slope_lo, slope_hi, npairs.
+ *   Column t belongs to season m = t mod nseason; its time is tau = (double)t / (double)nseason years from the window's start
+ *     (one correctly rounded division).  nseason = 1 is the plain Mann-Kendall test (Mann 1945, Kendall 1975) on an annual
+ *     series, nseason = 12 on a monthly one the seasonal Kendall test (Hirsch & Slack 1984).  A NaN element is left out of
+ *     everything; +-inf is treated as NaN.
+ *   A pair is (i, j), i < j, of the same season, both finite; npairs their number, n the number of finite elements.
+ *   s = sum over the pairs of (x_j > x_i) - (x_j < x_i), by comparisons.
+ *   V = sum_m n_m (n_m - 1)(2 n_m + 5) - sum over the finite elements of (e - 1)(2 e + 5), n_m the finite count of season m, e
+ *     the number of finite elements of the element's season equal to it (==, itself included): integers, exact; the second
+ *     sum is the tie correction sum over tie groups g (g - 1)(2 g + 5), without a sort.  var_s = (double)V / 18.0.
+ *   z = (s - 1) / sqrt(var_s) for s > 0, (s + 1) / sqrt(var_s) for s < 0, 0 for s = 0 or var_s = 0;
+ *     p = erfc(|z| 0.70710678118654752), two-sided.
+ *   The slope of a pair is (x_j - x_i) / (double)((j - i) / nseason): one rounded subtraction, one correctly rounded division
+ *     by a whole number of years, no contraction; -0.0 counts as +0.0.  With s_(0) <= ... <= s_(N-1) the sorted slopes, N =
+ *     npairs: slope = s_((N-1)/2) for odd N, (s_(N/2-1) + s_(N/2)) / 2.0 for even N (numpy's median; Sen 1968);  sigma =
+ *     sqrt(var_s);  Ru = min((int)rint((N - z_conf sigma) / 2.0), N - 1);  Rl = max((int)rint((N + z_conf sigma) / 2.0) - 1, 0),
+ *     rint to even;  slope_lo = s_(Rl), slope_hi = s_(Ru).  z_conf is the normal quantile of (1 - confidence) / 2, a negative
+ *     number.  For nseason = 1 without NaN these four are scipy.stats.theilslopes(x, arange(n), confidence), bit for bit.
+ *   intercept = median(finite x) - slope median(tau of the finite elements), medians by numpy's rule (theilslopes' default
+ *     method 'separate').
+ *   With n < 4 or npairs = 0 only n and npairs are filled; the other eight columns are NaN.  A constant row gives s = 0,
+ *     var_s = 0, z = 0, p = 1 and zero slopes.
+ * The order statistics are exact: the slopes (up to nseason C(ncol / nseason, 2) per row) are not stored but recomputed from
+ * the row in LDS by every pass of an MSB-first radix select on an order-preserving 64-bit key (csrc/xh_trend_dev.h, which
+ * a host build runs too).  One workgroup per row; integer LDS adds only, a fixed floating-point order: two calls give the
+ * same bits.  LDS: 8 B per column + 6.2 KB.
+ * XH_ERR_ARG: a NULL array, col0 < 0, col0 + ncol > row_stride, ncol not a positive multiple of nseason, z_conf not negative
+ * and finite.  XH_ERR_LIMIT: ncol > 4096, nseason outside 1..12.  Nothing is launched then.  Asynchronous on the context's
+ * stream, timer "trend"; nothing is uploaded.                                                                          */
+#define XH_TREND_NCOL 10
+int xh_trend(xh_ctx *ctx, int64_t nrows, int32_t row_stride, int32_t col0, int32_t ncol, int32_t nseason, double z_conf,
+             const double *d_x, double *d_out);
+
 /* The same objective for SEVERAL basins in one launch, each basin with its own population: one basin alone is only
  * months x ~1.7 us of dependent chain, far too little to fill the chip.  h_ncell [nbasins]; h_pars [nbasins, nmembers,
  * npar]; h_pet_t / h_precip_t / h_tmin_t / h_area: host arrays of nbasins DEVICE pointers ([nmonths, ncell_b] each;

@@ -212,6 +212,7 @@ SIGNATURES = {
                             POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p)]),
     'xh_std_index2': (c_int, [_P, c_int64, c_int32, c_int32, POINTER(c_int32), c_int32, c_int32, c_int32, c_double, _P, _P,
                              POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p)]),
+    'xh_trend': (c_int, [_P, c_int64, c_int32, c_int32, c_int32, c_int32, c_double, _P, _P]),
     'xh_synth_forcing': (c_int, [_P, c_uint64, c_double, c_int64, c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
 }
 
@@ -898,6 +899,15 @@ class Context:
         self._check(lib().xh_std_index2(self.handle, int(ncell), int(nmonths), int(k.size), k.ctypes.data_as(POINTER(c_int32)),
                                         int(ref_month0), int(ref_nyear), STD_INDEX_DIST2[dist], float(max_shape), _dptr(x),
                                         _dptr(minus), table(par_in), table(par_out), table(index)))
+
+    # ---- trend per row (csrc/xh_trend.hip)
+    def trend(self, nrows, row_stride, col0, ncol, nseason, z_conf, x, out):
+        """Mann-Kendall test and Theil-Sen slope of the window ``x[r, col0 : col0 + ncol]`` of every row of ``x`` [nrows,
+        row_stride] into ``out`` [nrows, 10] = n, s, var_s, z, p, slope, intercept, slope_lo, slope_hi, npairs (xh_trend,
+        which states the definition): column t is season ``t mod nseason`` at ``t / nseason`` years; ``z_conf`` is the
+        normal quantile of (1 - confidence) / 2.  DeviceArrays or raw device addresses.  Asynchronous."""
+        self._check(lib().xh_trend(self.handle, int(nrows), int(row_stride), int(col0), int(ncol), int(nseason), float(z_conf),
+                                   _dptr(x), _dptr(out)))
 
     # ---- bench support
     def synth_forcing(self, seed, ncell, nmonths, lat, out, nan_frac=0.001, cell_ids=None):

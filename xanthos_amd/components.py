@@ -329,6 +329,7 @@ class Components:
         c._writer = c._q = c._ac = None
         c.gauge_skill = c.gauge_flow = None
         c.__dict__.pop('drought_index', None)          # (the result of drought_index() stands in the method's place)
+        c.__dict__.pop('trend', None)                  # (... and that of trend())
         return c
 
     def _pipeline_args(self, runoff, um, cells=None):
@@ -430,7 +431,29 @@ class Components:
             self.drought_index, self.drought_index_parameters = res.index, res.parameters
             logging.info('---Drought Index has finished successfully: %s seconds ------' % (time.time() - t0))
 
-    def _precipitation(self, var):
+    def trend(self):
+        """Trend tables of [Trend] (not in the reference): the Mann-Kendall test and the Theil-Sen slope per cell of the
+        run's runoff, PET, AET, soil moisture, routed flow or precipitation, from the arrays in HBM.  Leaves the result as
+        the ATTRIBUTE ``trend`` of this object, {(var, series): ndarray [ncell, 10]}, in place of this method."""
+        if getattr(self.s, 'CalculateTrend', 0) and self.is_root:
+            from .trend import Trend
+            logging.info('---Start Trend:')
+            t0 = time.time()
+
+            def result(attr):
+                if self.pipe is not None and attr not in self._host:
+                    return self.pipe.out[_RESULTS[attr]]
+                return getattr(self, attr)
+            rows_of = {'q': self._runoff, 'avgchflow': self._routed_flow, 'precip': lambda: self._precipitation('precip', 'Trend'),
+                       'pet': lambda: result('PET'), 'aet': lambda: result('AET'), 'soilmoisture': lambda: result('Sav')}
+            tables = {}
+            for var in self.s.trend['vars']:
+                for series, table in Trend(self.s, var, rows_of[var]()).tables.items():
+                    tables[(var, series)] = table
+            self.trend = tables
+            logging.info('---Trend has finished successfully: %s seconds ------' % (time.time() - t0))
+
+    def _precipitation(self, var, section='DroughtIndex'):
         """The run's precipitation [ncell, nmonths] for SPI / SPEI: the forcing array in HBM after a device-resident
         simulation, the loader's host array after a run that went stage by stage.  On a sharded run every rank's pipeline
         holds its own rows of the forcing only, and nothing gathers them: refused rather than indexed in part."""
@@ -439,8 +462,9 @@ class Components:
         forcing = getattr(self.pipe, 'forcing', None)
         rows = forcing.get('precip') if forcing is not None else None
         if rows is None or tuple(rows.shape) != (self.s.ncell, self.s.nmonths):
-            raise ValidationException("[DroughtIndex] index_var = {} needs the run's whole precipitation array on one GPU: in a run "
-                                      "sharded over several GPUs every rank holds its own cells' rows only.".format(var))
+            raise ValidationException("[{}] {} = {} needs the run's whole precipitation array on one GPU: in a run "
+                                      "sharded over several GPUs every rank holds its own cells' rows only.".format(
+                                          section, 'index_var' if section == 'DroughtIndex' else 'trend_vars', var))
         return rows
 
     def accessible_water(self):

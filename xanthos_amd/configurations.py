@@ -32,6 +32,7 @@ class ConfigRunner:
         c.accessible_water()          # post-processors, the outputs, the plots: the reference's order (configurations.py:117-139)
         c.drought()
         c.drought_index()             # ([DroughtIndex], not in the reference: standardized drought indices)
+        c.trend()                     # ([Trend], not in the reference: Mann-Kendall test and Theil-Sen slope per cell)
         c.hydropower_potential()
         c.hydropower_actual()
         c.evaluate()                  # ([Evaluate], not in the reference: the routed flow scored at stream gauges)

@@ -226,6 +226,16 @@ class ConfigReader:
             if not isinstance(c.get('DroughtIndex'), dict):
                 raise ValidationException('CalculateDroughtIndex = 1 but the config file has no [DroughtIndex] section.')
             self.configure_drought_index(c['DroughtIndex'])
+        # [Trend] (not in the reference): Mann-Kendall test and Theil-Sen slope per cell of the run's results
+        raw_tr = str(p.get('CalculateTrend', 0)).strip()
+        if raw_tr not in ('0', '1'):
+            raise ValidationException("CalculateTrend must be 0 or 1, not '{}'".format(raw_tr))
+        self.CalculateTrend = int(raw_tr)
+        self.trend = None
+        if self.CalculateTrend:
+            if not isinstance(c.get('Trend'), dict):
+                raise ValidationException('CalculateTrend = 1 but the config file has no [Trend] section.')
+            self.configure_trend(c['Trend'])
 
     # ------------------------------------------------------------------ modules
     def configure_pet(self, cfg):
@@ -744,6 +754,71 @@ class ConfigReader:
         self.drought_index = {'var': var, 'scales': scales, 'distribution': dist,
                               'reference_start_year': years['reference_start_year'],
                               'reference_end_year': years['reference_end_year'], 'max_shape': max_shape, 'parameters': files}
+
+    def configure_trend(self, cfg):
+        """[Trend] (not a section of the reference; trend/trend.py): trend_vars = a list from q | pet | aet | soilmoisture |
+        avgchflow | precip; series = a list from annual (the yearly series, plain Mann-Kendall test) | seasonal (the monthly
+        series, seasonal Kendall test over the 12 calendar months); annual = sum | mean (how a year is formed; default: sum
+        for q, pet, aet and precip -- a NaN month makes the year NaN --, mean for soilmoisture and avgchflow);
+        start_year / end_year (default: the run's years; whole years inside the run, at least 4); confidence (default 0.95)
+        of the slope's interval.  Kept as ``self.trend``; 'annual' there is {var: 'sum' | 'mean'}."""
+        from .trend.trend import ANNUAL_DEFAULT, MAX_COLS, MIN_YEARS, SERIES, VARS
+
+        def refuse(key, why):
+            raise ValidationException('[Trend] {} {}'.format(key, why))
+
+        def words(key):
+            raw = cfg.get(key)
+            raw = [] if raw in (None, '') else (raw if isinstance(raw, list) else [raw])
+            return [str(w).strip().lower() for w in raw]
+        if self.calibrate:
+            refuse('and Calibrate = 1', 'exclude each other: a calibration writes no outputs to test for a trend.')
+        if getattr(self, 'ensemble', None) is not None:
+            refuse('and an [Ensemble] section', 'exclude each other: per-member trends are not implemented.')
+        tvars = words('trend_vars')
+        if not tvars or len(set(tvars)) != len(tvars) or any(v not in VARS for v in tvars):
+            refuse('trend_vars', '= {!r} must be different names from {}.'.format(cfg.get('trend_vars'), ', '.join(VARS)))
+        if 'avgchflow' in tvars and self.routing_module != 'mrtm':
+            refuse('trend_vars', "= avgchflow is the routed channel flow: the run needs routing_module = mrtm, not '{}'.".format(
+                self.routing_module))
+        for v in tvars:
+            if v in ('q', 'aet', 'soilmoisture', 'precip') and self.runoff_module == 'none':
+                refuse('trend_vars', "= {} comes from (precip: is loaded by) the runoff module: the run needs a runoff_module, not "
+                       "'none'.".format(v))
+            if v == 'pet' and self.pet_module == 'none':
+                refuse('trend_vars', "= pet is the PET module's result: the run needs a pet_module, not 'none'.")
+        series = words('series')
+        if not series or len(set(series)) != len(series) or any(w not in SERIES for w in series):
+            refuse('series', '= {!r} must be different names from {}.'.format(cfg.get('series'), ', '.join(SERIES)))
+        annual = dict(ANNUAL_DEFAULT)
+        if cfg.get('annual') is not None:
+            how = str(cfg.get('annual')).strip().lower()
+            if how not in ('sum', 'mean'):
+                refuse('annual', "= '{}' must be sum or mean.".format(cfg.get('annual')))
+            annual = {v: how for v in VARS}
+        years = {}
+        for key, default in (('start_year', self.StartYear), ('end_year', self.EndYear)):
+            try:
+                years[key] = int(cfg.get(key, default))
+            except (TypeError, ValueError):
+                refuse(key, '= {!r} is not a year.'.format(cfg.get(key)))
+            if not self.StartYear <= years[key] <= self.EndYear:
+                refuse(key, '= {} lies outside the years of the run, {} - {}.'.format(years[key], self.StartYear, self.EndYear))
+        nyears = years['end_year'] - years['start_year'] + 1
+        if nyears < MIN_YEARS:
+            refuse('end_year', '= {}: the window {} - {} is shorter than the {} years a trend needs.'.format(
+                years['end_year'], years['start_year'], years['end_year'], MIN_YEARS))
+        if 'seasonal' in series and 12 * nyears > MAX_COLS:
+            refuse('series', '= seasonal: the window {} - {} has {} months, more than the {} one row may take.'.format(
+                years['start_year'], years['end_year'], 12 * nyears, MAX_COLS))
+        try:
+            confidence = float(cfg.get('confidence', 0.95))
+        except (TypeError, ValueError):
+            confidence = float('nan')
+        if not 0.5 < confidence < 1.0:
+            refuse('confidence', '= {!r} must lie between 0.5 and 1.'.format(cfg.get('confidence')))
+        self.trend = {'vars': tvars, 'series': series, 'annual': annual, 'start_year': years['start_year'],
+                      'end_year': years['end_year'], 'confidence': confidence}
 
     @staticmethod
     def ck_obs_unit(set_calib, unit):

@@ -711,6 +711,18 @@ def enable_drought_index(ini, index_var='q', scales=(1, 3, 12), **keys):
     return ini
 
 
+def enable_trend(ini, trend_vars=('q',), series=('annual', 'seasonal'), **keys):
+    """Switch the trend tables on in an .ini written by one of the example writers: ``CalculateTrend = 1`` in [Project] and a
+    [Trend] section with ``trend_vars``, ``series`` and whatever else is given (``annual``, ``start_year``, ``end_year``,
+    ``confidence``) as written."""
+    text = open(ini).read()
+    text = text.replace('\n[PET]', '\nCalculateTrend = 1\n\n[PET]', 1)
+    text += '\n[Trend]\ntrend_vars = {}\nseries = {}\n'.format(', '.join(trend_vars), ', '.join(series))
+    text += ''.join('{} = {}\n'.format(k, v) for k, v in keys.items())
+    open(ini, 'w').write(text)
+    return ini
+
+
 def write_diag_inputs(root, world, seed=17, nvic=30, dir_name='diagnostics'):
     """Write the four comparison tables of the diagnostics (the reference's DiagDir, ini_reader.py:439-445) matched to
     ``world`` under ``root``/input/``dir_name`` and return its path.
