@@ -649,6 +649,45 @@ int xh_std_index2(xh_ctx *ctx, int64_t ncell, int32_t nmonths, int32_t nscale, c
 int xh_trend(xh_ctx *ctx, int64_t nrows, int32_t row_stride, int32_t col0, int32_t ncol, int32_t nseason, double z_conf,
              const double *d_x, double *d_out);
 
+/* ------------------------------------------------------------------ annual extremes: GEV by L-moments
+ * xh_extremes replaces NO function of the reference: xanthos has no extreme-value statistics.  Per row r of d_x (nrows rows of
+ * row_stride doubles) it takes the window x[0 .. 12 nyear) = d_x[r, col0 .. col0 + 12 nyear) of a monthly series, year y being
+ * columns 12 y .. 12 y + 11, and writes d_table[r, 0 .. 8 + nT) = n, l1, l2, t3, t4, k, alpha, xi, x_T..., d_annual[r, 0 .. nyear)
+ * and d_T_year[r, 0 .. nyear) (either may be NULL).  No operation is contracted.
+ *   1 a_y = the largest (kind = XH_EXTREMES_MAX) or smallest (XH_EXTREMES_MIN) of the year's 12 months, by comparisons from the
+ *     first month on (of equal months the first stays); a NaN or +-inf month makes the year missing (a_y = NaN).  n = the years
+ *     not missing.  z_y = a_y for max, -a_y for min: the low-flow fit is the GEV of the negated minima, the three-parameter
+ *     Weibull distribution.
+ *   2 Sample L-moments (Hosking 1990) of the n values z, sorted ascending by counting (ties by position, as the log-logistic
+ *     fit ranks): b_r = (sum_i w_r(i) z_(i)) / (double)n, r = 0 .. 3, from 0.0 over ascending rank i, w_0 = 1, w_r(i) =
+ *     (w_{r-1}(i) (double)(i - r + 1)) / (double)(n - r);  l1 = b0;  l2 = 2 b1 - b0;  l3 = (6 b2 - 6 b1) + b0;  l4 = ((20 b3 -
+ *     30 b2) + 12 b1) - b0;  t3 = l3 / l2;  t4 = l4 / l2.
+ *   3 GEV by L-moments (Hosking & Wallis 1997), Hosking's sign of the shape (scipy.stats.genextreme's c): k solves
+ *     expm1(-k ln 3) / expm1(-k ln 2) = (3 + t3) / 2 by 10 Newton steps, always all of them, from k0 = 7.8590 c + (2.9554 c) c,
+ *     c = 2 / (3 + t3) - ln 2 / ln 3;  G = tgamma(1 + k);  alpha = (l2 d) / G with d = k / -expm1(-k ln 2) (1 / ln 2 at k = 0);
+ *     xi = l1 - alpha g with g = (1 - G) / k for |k| >= 0.25 and the Taylor series of Gamma(1 + k) (30 terms) below, which at
+ *     k = 0 is the Gumbel limit alpha = l2 / ln 2, xi = l1 - 0.5772... alpha.  No fit when n < min_years, when the series is
+ *     constant (z_(0) = z_(n-1)), when l2 is not > 0, or when k <= -1, decided as t3 > 1 - 2^-20 on the shared bits of t3
+ *     (or a k that is not > -1 or not finite): the row then holds n, l1 and l2 as far as defined, the rest NaN.
+ *   4 x_T, T > 1:  y = -log1p(-1 / T);  q = xi - alpha (expm1(k log y) / k), xi - alpha log y at k = 0;  x_T = q for max (exceeded
+ *     once in T years on average), -q for min (undershot once in T years).  l1 and xi are reported negated back for min;
+ *     l2, t3, t4, k, alpha are those of z.
+ *   5 T_y:  s = (z_y - xi) / alpha;  u = -log F = exp(log1p(-k s) / k), exp(-s) at k = 0, outside the support (-k s <= -1) 0 for
+ *     k > 0 and +inf for k < 0;  T_y = -1 / expm1(-u): 1 at F = 0, +inf at F = 1; NaN for a missing year or a row without a fit.
+ *   d_par_in (NULL: none) [nrows, 8] = n .. xi as reported by another call (a historic run): steps 2 and 3 are skipped, the 8
+ *     columns are copied bit for bit, and steps 4 and 5 use them on this call's annual series.
+ * csrc/xh_extremes_dev.h holds this definition for device and host.  One wavefront per row, four to a workgroup, no workgroup
+ * barrier; no atomics, a fixed order: two calls give the same bits.  LDS per workgroup: 4 (776 + 2 nyear) doubles.
+ * XH_ERR_ARG: a NULL d_x or d_table (or h_T with nT > 0), col0 < 0, col0 + 12 nyear > row_stride, nyear < 1, 12 nyear > 4096,
+ * nT outside 0..8, a T not > 1, kind neither 0 nor 1, min_years < 5.  Nothing is launched then.  Asynchronous on the context's
+ * stream, timer "extremes"; h_T is read before the call returns; nothing is uploaded.                                   */
+#define XH_EXTREMES_NPAR 8
+#define XH_EXTREMES_MAX 0
+#define XH_EXTREMES_MIN 1
+int xh_extremes(xh_ctx *ctx, int64_t nrows, int32_t row_stride, int32_t col0, int32_t nyear, int32_t kind, int32_t min_years,
+                int32_t nT, const double *h_T, const double *d_x, const double *d_par_in, double *d_table, double *d_annual,
+                double *d_T_year);
+
 /* The same objective for SEVERAL basins in one launch, each basin with its own population: one basin alone is only
  * months x ~1.7 us of dependent chain, far too little to fill the chip.  h_ncell [nbasins]; h_pars [nbasins, nmembers,
  * npar]; h_pet_t / h_precip_t / h_tmin_t / h_area: host arrays of nbasins DEVICE pointers ([nmonths, ncell_b] each;

@@ -28,6 +28,7 @@ NARROW_KINDS = {np.dtype('<f4'): (XH_SRC_F32_LE, 'f32'), np.dtype('>f4'): (XH_SR
                 np.dtype('>f8'): (XH_SRC_F64_BE, 'f64be')}
 STD_INDEX_DIST = {'gamma': 0, 'empirical': 1}                        # XH_STD_INDEX_* of xh_std_index
 STD_INDEX_DIST2 = dict(STD_INDEX_DIST, loglogistic=2)                # ... and of xh_std_index2
+EXTREMES_KIND = {'max': 0, 'min': 1}                                 # xh_extremes' kind
 ENS_STAT_BITS = {'mean': 1, 'std': 2, 'min': 4, 'max': 8}       # XH_ENS_* of xh_ens_stats, in its output order
 
 
@@ -213,6 +214,7 @@ SIGNATURES = {
     'xh_std_index2': (c_int, [_P, c_int64, c_int32, c_int32, POINTER(c_int32), c_int32, c_int32, c_int32, c_double, _P, _P,
                              POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p)]),
     'xh_trend': (c_int, [_P, c_int64, c_int32, c_int32, c_int32, c_int32, c_double, _P, _P]),
+    'xh_extremes': (c_int, [_P, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P, _P, _P, _P, _P]),
     'xh_synth_forcing': (c_int, [_P, c_uint64, c_double, c_int64, c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
 }
 
@@ -908,6 +910,20 @@ class Context:
         normal quantile of (1 - confidence) / 2.  DeviceArrays or raw device addresses.  Asynchronous."""
         self._check(lib().xh_trend(self.handle, int(nrows), int(row_stride), int(col0), int(ncol), int(nseason), float(z_conf),
                                    _dptr(x), _dptr(out)))
+
+    # ---- annual extremes per row (csrc/xh_extremes.hip)
+    def extremes(self, nrows, row_stride, col0, nyear, kind, min_years, return_periods, x, table, annual=None, T_year=None,
+                 par_in=None):
+        """Annual maxima (``kind`` 'max' or 0) or minima ('min' or 1) of the monthly window ``x[r, col0 : col0 + 12 nyear]`` of
+        every row of ``x`` [nrows, row_stride], the GEV fitted to them by L-moments, the return levels of ``return_periods``
+        (at most 8, each > 1) and every year's return period (xh_extremes, which states the definition): ``table`` [nrows,
+        8 + nT] = n, l1, l2, t3, t4, k, alpha, xi, x_T...; ``annual`` and ``T_year`` [nrows, nyear] or None; ``par_in`` [nrows,
+        8]: the parameters of another call instead of a fit.  DeviceArrays or raw device addresses.  Asynchronous."""
+        T = np.ascontiguousarray(return_periods, dtype=np.float64).ravel()
+        kind = EXTREMES_KIND.get(kind, kind) if isinstance(kind, str) else kind
+        self._check(lib().xh_extremes(self.handle, int(nrows), int(row_stride), int(col0), int(nyear), int(kind), int(min_years),
+                                      int(T.size), T.ctypes.data_as(c_void_p) if T.size else None, _dptr(x), _dptr(par_in),
+                                      _dptr(table), _dptr(annual), _dptr(T_year)))
 
     # ---- bench support
     def synth_forcing(self, seed, ncell, nmonths, lat, out, nan_frac=0.001, cell_ids=None):

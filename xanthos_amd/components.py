@@ -330,6 +330,7 @@ class Components:
         c.gauge_skill = c.gauge_flow = None
         c.__dict__.pop('drought_index', None)          # (the result of drought_index() stands in the method's place)
         c.__dict__.pop('trend', None)                  # (... and that of trend())
+        c.__dict__.pop('extremes', None)               # (... and that of extremes())
         return c
 
     def _pipeline_args(self, runoff, um, cells=None):
@@ -453,6 +454,29 @@ class Components:
             self.trend = tables
             logging.info('---Trend has finished successfully: %s seconds ------' % (time.time() - t0))
 
+    def extremes(self):
+        """Extremes of [Extremes] (not in the reference): annual maxima or minima per cell of the run's runoff, PET, AET, soil
+        moisture, routed flow or precipitation, the GEV fitted to them by L-moments, return levels and every year's return
+        period, from the arrays in HBM.  Leaves the result as the ATTRIBUTE ``extremes`` of this object, {(var, kind):
+        {'table': [ncell, 8 + nT], 'annual': [ncell, nyear], 'return_period': [ncell, nyear]}}, in place of this method."""
+        if getattr(self.s, 'CalculateExtremes', 0) and self.is_root:
+            from .extremes import Extremes
+            logging.info('---Start Extremes:')
+            t0 = time.time()
+
+            def result(attr):
+                if self.pipe is not None and attr not in self._host:
+                    return self.pipe.out[_RESULTS[attr]]
+                return getattr(self, attr)
+            rows_of = {'q': self._runoff, 'avgchflow': self._routed_flow, 'precip': lambda: self._precipitation('precip', 'Extremes'),
+                       'pet': lambda: result('PET'), 'aet': lambda: result('AET'), 'soilmoisture': lambda: result('Sav')}
+            results = {}
+            for var in self.s.extremes['vars']:
+                for kind, res in Extremes(self.s, var, rows_of[var]()).results.items():
+                    results[(var, kind)] = res
+            self.extremes = results
+            logging.info('---Extremes has finished successfully: %s seconds ------' % (time.time() - t0))
+
     def _precipitation(self, var, section='DroughtIndex'):
         """The run's precipitation [ncell, nmonths] for SPI / SPEI: the forcing array in HBM after a device-resident
         simulation, the loader's host array after a run that went stage by stage.  On a sharded run every rank's pipeline
@@ -464,7 +488,7 @@ class Components:
         if rows is None or tuple(rows.shape) != (self.s.ncell, self.s.nmonths):
             raise ValidationException("[{}] {} = {} needs the run's whole precipitation array on one GPU: in a run "
                                       "sharded over several GPUs every rank holds its own cells' rows only.".format(
-                                          section, 'index_var' if section == 'DroughtIndex' else 'trend_vars', var))
+                                          section, {'DroughtIndex': 'index_var', 'Extremes': 'extreme_vars'}.get(section, 'trend_vars'), var))
         return rows
 
     def accessible_water(self):

@@ -236,6 +236,16 @@ class ConfigReader:
             if not isinstance(c.get('Trend'), dict):
                 raise ValidationException('CalculateTrend = 1 but the config file has no [Trend] section.')
             self.configure_trend(c['Trend'])
+        # [Extremes] (not in the reference): annual maxima / minima per cell, the GEV by L-moments, return levels and periods
+        raw_ex = str(p.get('CalculateExtremes', 0)).strip()
+        if raw_ex not in ('0', '1'):
+            raise ValidationException("CalculateExtremes must be 0 or 1, not '{}'".format(raw_ex))
+        self.CalculateExtremes = int(raw_ex)
+        self.extremes = None
+        if self.CalculateExtremes:
+            if not isinstance(c.get('Extremes'), dict):
+                raise ValidationException('CalculateExtremes = 1 but the config file has no [Extremes] section.')
+            self.configure_extremes(c['Extremes'])
 
     # ------------------------------------------------------------------ modules
     def configure_pet(self, cfg):
@@ -819,6 +829,104 @@ class ConfigReader:
             refuse('confidence', '= {!r} must lie between 0.5 and 1.'.format(cfg.get('confidence')))
         self.trend = {'vars': tvars, 'series': series, 'annual': annual, 'start_year': years['start_year'],
                       'end_year': years['end_year'], 'confidence': confidence}
+
+    def configure_extremes(self, cfg):
+        """[Extremes] (not a section of the reference; extremes/extremes.py): extreme_vars = a list from q | pet | aet |
+        soilmoisture | avgchflow | precip; kinds = a list from max | min; return_periods (default 2, 5, 10, 20, 50, 100; at
+        most 8, different, each > 1); start_year / end_year (default: the run's; the years in which the first and the last
+        year of the window start); year_start_month (1 - 12, default 1: a hydrological year runs from that month to the month
+        before it a year later, and the last one must end inside the run); min_years (default 10, at least 5): the years a
+        fit needs; parameters (optional) = <OutputFolder>/<OutputNameStr> of a historic run, whose tables stand in for the
+        fit.  Kept as ``self.extremes``; 'parameters' there is {(var, kind): file} or None."""
+        import numpy as np
+        from .extremes.extremes import KINDS, MAX_COLS, MAX_PERIODS, MIN_YEARS, MIN_YEARS_DEFAULT, RETURN_PERIODS, VARS, parameter_file
+
+        def refuse(key, why):
+            raise ValidationException('[Extremes] {} {}'.format(key, why))
+
+        def words(key):
+            raw = cfg.get(key)
+            raw = [] if raw in (None, '') else (raw if isinstance(raw, list) else [raw])
+            return [str(w).strip().lower() for w in raw]
+        if self.calibrate:
+            refuse('and Calibrate = 1', 'exclude each other: a calibration writes no outputs to take extremes of.')
+        if getattr(self, 'ensemble', None) is not None:
+            refuse('and an [Ensemble] section', 'exclude each other: per-member extremes are not implemented.')
+        if getattr(self, 'OutputInYear', 0) == 1:
+            refuse('and OutputInYear = 1', 'exclude each other: the extremes are those of the monthly series.')
+        evars = words('extreme_vars')
+        if not evars or len(set(evars)) != len(evars) or any(v not in VARS for v in evars):
+            refuse('extreme_vars', '= {!r} must be different names from {}.'.format(cfg.get('extreme_vars'), ', '.join(VARS)))
+        if 'avgchflow' in evars and self.routing_module != 'mrtm':
+            refuse('extreme_vars', "= avgchflow is the routed channel flow: the run needs routing_module = mrtm, not '{}'.".format(
+                self.routing_module))
+        for v in evars:
+            if v in ('q', 'aet', 'soilmoisture', 'precip') and self.runoff_module == 'none':
+                refuse('extreme_vars', "= {} comes from (precip: is loaded by) the runoff module: the run needs a runoff_module, "
+                       "not 'none'.".format(v))
+            if v == 'pet' and self.pet_module == 'none':
+                refuse('extreme_vars', "= pet is the PET module's result: the run needs a pet_module, not 'none'.")
+        kinds = words('kinds')
+        if not kinds or len(set(kinds)) != len(kinds) or any(w not in KINDS for w in kinds):
+            refuse('kinds', '= {!r} must be different names from {}.'.format(cfg.get('kinds'), ', '.join(KINDS)))
+        periods = list(RETURN_PERIODS)
+        if cfg.get('return_periods') not in (None, ''):
+            raw = cfg.get('return_periods')
+            try:
+                periods = [float(w) for w in (raw if isinstance(raw, list) else [raw])]
+            except (TypeError, ValueError):
+                periods = []
+            if not periods or len(periods) > MAX_PERIODS or len(set(periods)) != len(periods) or not all(
+                    T > 1.0 and T < float('inf') for T in periods):
+                refuse('return_periods', '= {!r} must be at most {} different numbers, each > 1.'.format(raw, MAX_PERIODS))
+        try:
+            month = int(cfg.get('year_start_month', 1))
+        except (TypeError, ValueError):
+            month = 0
+        if not 1 <= month <= 12:
+            refuse('year_start_month', '= {!r} must be a month, 1 - 12.'.format(cfg.get('year_start_month')))
+        try:
+            min_years = int(cfg.get('min_years', MIN_YEARS_DEFAULT))
+        except (TypeError, ValueError):
+            min_years = 0
+        if min_years < MIN_YEARS:
+            refuse('min_years', '= {!r} must be a whole number, at least {}.'.format(cfg.get('min_years'), MIN_YEARS))
+        # the last year that starts in month `month` and ends inside the run
+        last_start = self.EndYear if month == 1 else self.EndYear - 1
+        years = {}
+        for key, default in (('start_year', self.StartYear), ('end_year', last_start)):
+            try:
+                years[key] = int(cfg.get(key, default))
+            except (TypeError, ValueError):
+                refuse(key, '= {!r} is not a year.'.format(cfg.get(key)))
+            if not self.StartYear <= years[key] <= self.EndYear:
+                refuse(key, '= {} lies outside the years of the run, {} - {}.'.format(years[key], self.StartYear, self.EndYear))
+        if years['end_year'] > last_start:
+            refuse('end_year', '= {}: the year that starts in month {} of {} ends after the run ({}); the last complete one '
+                   'starts in {}.'.format(years['end_year'], month, years['end_year'], self.EndYear, last_start))
+        nyears = years['end_year'] - years['start_year'] + 1
+        if nyears < min_years:
+            refuse('end_year', '= {}: the window {} - {} has {} years, fewer than min_years = {}.'.format(
+                years['end_year'], years['start_year'], years['end_year'], max(nyears, 0), min_years))
+        if 12 * nyears > MAX_COLS:
+            refuse('end_year', '= {}: the window {} - {} has {} months, more than the {} one row may take.'.format(
+                years['end_year'], years['start_year'], years['end_year'], 12 * nyears, MAX_COLS))
+        files = None
+        if cfg.get('parameters') not in (None, ''):
+            stem = str(cfg.get('parameters')).strip()
+            files = {}
+            for v in evars:
+                for kind in kinds:
+                    path = parameter_file(stem, v, kind)
+                    if not os.path.isfile(path):
+                        refuse('parameters', "= {}: the table of {} ({}), '{}', does not exist.".format(stem, v, kind, path))
+                    shape = np.load(path, mmap_mode='r').shape
+                    if len(shape) != 2 or shape[0] != self.ncell or shape[1] < 8:
+                        refuse('parameters', '= {}: {} has shape {}, the run needs [{}, 8 or more] (cells; n, l1, l2, t3, t4, k, '
+                               'alpha, xi).'.format(stem, path, tuple(shape), self.ncell))
+                    files[(v, kind)] = path
+        self.extremes = {'vars': evars, 'kinds': kinds, 'return_periods': periods, 'start_year': years['start_year'],
+                         'end_year': years['end_year'], 'year_start_month': month, 'min_years': min_years, 'parameters': files}
 
     @staticmethod
     def ck_obs_unit(set_calib, unit):

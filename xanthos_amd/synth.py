@@ -723,6 +723,19 @@ def enable_trend(ini, trend_vars=('q',), series=('annual', 'seasonal'), **keys):
     return ini
 
 
+def enable_extremes(ini, extreme_vars=('q',), kinds=('max', 'min'), **keys):
+    """Switch the extremes on in an .ini written by one of the example writers: ``CalculateExtremes = 1`` in [Project] and an
+    [Extremes] section with ``extreme_vars``, ``kinds`` and whatever else is given (``return_periods`` -- a sequence is joined
+    by commas --, ``start_year``, ``end_year``, ``year_start_month``, ``min_years``, ``parameters``) as written."""
+    text = open(ini).read()
+    text = text.replace('\n[PET]', '\nCalculateExtremes = 1\n\n[PET]', 1)
+    text += '\n[Extremes]\nextreme_vars = {}\nkinds = {}\n'.format(', '.join(extreme_vars), ', '.join(kinds))
+    for k, v in keys.items():
+        text += '{} = {}\n'.format(k, ', '.join(str(w) for w in v) if isinstance(v, (list, tuple)) else v)
+    open(ini, 'w').write(text)
+    return ini
+
+
 def write_diag_inputs(root, world, seed=17, nvic=30, dir_name='diagnostics'):
     """Write the four comparison tables of the diagnostics (the reference's DiagDir, ini_reader.py:439-445) matched to
     ``world`` under ``root``/input/``dir_name`` and return its path.
