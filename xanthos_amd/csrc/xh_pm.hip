@@ -14,7 +14,10 @@
 // table and 1/fwet shared by the classes, and the three quotients that make up a class's ET (:306-327) are put over one
 // common denominator (one reciprocal per class instead of three).  Differences from numpy therefore come from the
 // exp/log/sqrt implementations, from fdiv() (xh_math.h: up to 19 ulp per quotient) and from those regroupings -- 5e-13 in
-// PET overall.
+// PET overall on cells that mix eight ordinary classes, against numpy.  That figure does not hold for a class alone: with
+// one class per cell, edge tables and forcing on every step of the model (tests/test_gpu_pm.py) the worst relative error
+// against a long-double evaluation is 5.8e-11 (at PET >= 1e-3 mm; 5.7e-11 at >= 1 mm), 3.0e-2 of the 1e-9 |x| + 1e-9 mm bar;
+// the double reference itself is 1.3e-2 of that bar away from the same truth, where esx - vap cancels near saturation.
 #include <algorithm>
 
 #include "xh_launch.h"
@@ -182,8 +185,11 @@ __device__ __forceinline__ double pm_class(const PmLds &L, const PmTablesDev *__
     const double dz = M.dz;
     const int moy = M.moy;
     double et;
-    const double oma = (l == water_idx) ? L.one_m_alpha[0][moy]
-                                        : ((l == snow_idx) ? L.one_m_alpha[6][moy] : L.one_m_alpha[l][moy]);
+    // The snow test comes first, here and below: the reference assigns water, then snow (run_pmpet :460-464), so a class that
+    // both indices name ends up as snow, and et_snow reads albedo row 6 (:377).  For any other pair of indices the order of
+    // the two tests selects the same row.
+    const double oma = (l == snow_idx) ? L.one_m_alpha[6][moy]
+                                       : ((l == water_idx) ? L.one_m_alpha[0][moy] : L.one_m_alpha[l][moy]);
         if (l == snow_idx) {
             // et_snow (:364-377): emissivity 0.85, albedo of land class 6
             const double rnl = sig_t4_dz * 0.85 - rl_term;
