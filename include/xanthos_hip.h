@@ -279,7 +279,9 @@ int xh_route_plan_info(const xh_route_plan *plan, int64_t info[16]);
 int xh_route_plan_prepare(xh_ctx *ctx, xh_route_plan *plan, const double *h_flow_dist, const double *h_velocity, double dt);
 
 /* Diagnostics: with XH_FLOW_STATS=1 in the environment the dataflow kernel records, per unit, {shader cycles inside the
- * sub-step loops, shader cycles total, 100 MHz ticks total, shape bits + placement, cycles waiting for data, cycles waiting for ring space}; this call waits for the
+ * sub-step loops, shader cycles total, 100 MHz ticks total, shape bits + placement, cycles waiting for data, cycles waiting for ring space}
+ * -- the last two in bits 0-35 of their words, above them the flow-control checks that looked at the stream counter (36-49) and
+ * those at which the value already known covered the need (50-63); this call waits for the
  * stream and copies up to max_words 64-bit words (6 per unit) of the last xh_route_series launch. */
 int xh_route_plan_stats(xh_route_plan *plan, int64_t max_words, uint64_t *h_words, int64_t *n_words);
 

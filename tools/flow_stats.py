@@ -37,7 +37,10 @@ if os.environ.get('XH_STATS_LOOP'):
     ctx.sync()
     ms, n = ctx.timing('mrtm_route')
     print('back-to-back steps: mrtm_route avg ms', ms / n)
-st = pipe.plan.stats().astype(np.float64)
+st = pipe.plan.stats()
+# st[4] / st[5]: the waits' cycles are bits 0-35 (above them: counts of looks at the stream counters, tools/rsum_probe.py)
+st[:, 4:6] &= np.uint64((1 << 36) - 1)
+st = st.astype(np.float64)
 nsub = sum(int(d) * 8 for d in pipe.ndays)
 print('plan', pipe.plan.info(), 'reassociated', pipe.plan.rsum_info())
 print('route ms', ms / n, 'substeps', nsub, 'us/substep', ms / n * 1e3 / nsub)

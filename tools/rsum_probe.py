@@ -72,8 +72,15 @@ for name in t:
 
 # per-unit accounting of the last reassociated launch
 route(_hip.XH_ROUTE_REASSOC)
-st = pipe.plan.stats().astype(np.float64)
-raw3 = pipe.plan.stats()[:, 3]
+raw = pipe.plan.stats()
+st = raw.astype(np.float64)
+raw3 = raw[:, 3]
+# st[4] / st[5]: cycles of the checks in bits 0-35; above them (libraries since profiles/check_path) the checks that looked at the
+# counter (36-49) and those at which the known value covered the need (50-63): data = `ready` of the imports, ring = `done`
+for k in (4, 5):
+    st[:, k] = (raw[:, k] & np.uint64((1 << 36) - 1)).astype(np.float64)
+looks = {k: ((raw[:, k] >> np.uint64(36)) & np.uint64(0x3fff)).astype(int) for k in (4, 5)}
+covered = {k: ((raw[:, k] >> np.uint64(50)) & np.uint64(0x3fff)).astype(int) for k in (4, 5)}
 nsub = (sum(int(d) for d in pipe.ndays) + sum(int(d) for d in pipe.ndays[:spin])) * 8
 loop, total, ticks = st[:, 0], st[:, 1], st[:, 2]
 shape = (raw3 & np.uint64(255)).astype(int)
@@ -88,6 +95,14 @@ for flag, name in ((0, 'no streams'), (16, 'imports'), (32, 'exports'), (48, 'bo
         print('  %-10s n=%4d cycles/sub-step median %.0f max %.0f; wait data %.1f%% ring %.1f%%' % (
             name, sel.sum(), np.median(loop[sel] / nsub), (loop[sel] / nsub).max(), 100 * np.median(st[sel, 4] / total[sel]),
             100 * np.median(st[sel, 5] / total[sel])))
+if any(looks[k].any() or covered[k].any() for k in (4, 5)):
+    for k, name in ((4, 'ready (imports)'), (5, 'done (outlets)')):
+        sel = (looks[k] + covered[k]) > 0
+        print('  checks that looked at %-15s: units %4d, median %d of %d checks, max %d; all units together %d of %d' % (
+            name, sel.sum(), np.median(looks[k][sel]), np.median((looks[k] + covered[k])[sel]), looks[k][sel].max(),
+            looks[k].sum(), (looks[k] + covered[k]).sum()))
+else:
+    print('  looks at the stream counters: not recorded by this library (both counters at every check)')
 single_plan = pipe.plan.rsum_info()['pair_cells'] >= 0      # bit 64: 8-byte entries = a single unit; the others are its pair units
 pairu = ((shape & 64) == 0) if single_plan else np.zeros(len(shape), dtype=bool)
 if pairu.any():

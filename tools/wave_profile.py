@@ -33,7 +33,14 @@ raw = st
 waits, total_c = (raw[:, 1] >> np.uint64(32)).astype(np.float64), (raw[:, 1] & lo32).astype(np.float64)
 p_check, p_hk = (raw[:, 2] >> np.uint64(32)).astype(np.float64), (raw[:, 2] & lo32).astype(np.float64)
 p_fin, p_zx = (raw[:, 5] >> np.uint64(32)).astype(np.float64), (raw[:, 5] & lo32).astype(np.float64)
+# the split of check() (libraries since profiles/check_path; zeros from an older one): st[0] / st[4] carry, above their 32-bit
+# cycle counts, the statement that drains the wave's memory operations with the counter loads it asked for, and the waits for a
+# counter that did have to poll; st[3] bits 24-39 the checks that asked for a counter
+p_drain, p_poll = (raw[:, 0] >> np.uint64(32)).astype(np.float64), (raw[:, 4] >> np.uint64(32)).astype(np.float64)
+n_looks = ((raw3 >> np.uint64(24)) & np.uint64(0xffff)).astype(np.float64)
 st = st.astype(np.float64)
+st[:, 0] = (raw[:, 0] & lo32).astype(np.float64)
+st[:, 4] = (raw[:, 4] & lo32).astype(np.float64)
 st[:, 1] = total_c
 st[:, 5] = p_check + p_hk + p_fin + p_zx      # "checks + months", as before the split
 nsub = sum(int(d) * 8 for d in pipe.ndays)
@@ -75,6 +82,22 @@ if pipe.plan.info()['last_tree_kernel'] == 4:      # k_mrtm_rsum: by streams and
         print('%-11s %-6s n=%4d | %5.1f | %5.1f | %5.1f (%4.0f) | %5.1f (%4.0f) | %5.1f (%4.0f) | outside waits %.0f' % (
             name, 'single' if pl else 'pair', sel.sum(), med((p_check - waits) / nsub), med(waits / nsub), med(p_fin / nsub), med(p_fin / nmon),
             med(p_zx / nsub), med(p_zx / nmon), med(p_hk / nsub), med(p_hk / nmon), med((total - waits) / nsub)))
+    # check() in three parts, cycles per sub-step of the run: (a + b) the drain up to vmcnt(0) with the counter loads the build /
+    # the switch XH_FLOW_LOOK_ALWAYS asked for -- run both ways, the difference is what the loads add; (c) polls that had to poll;
+    # the rest of check() (publication, guards, the timers of this build); and how many of the checks asked for a counter
+    n_checks = float((nsub + 255) // 256)
+    top = np.zeros(len(shape), dtype=bool)
+    top[np.argsort(-(total - waits))[:10]] = True
+    pairx = ((shape & 64) == 0) & ((shape & 32) != 0) if pipe.plan.rsum_info()['pair_cells'] >= 0 else np.zeros(len(shape), dtype=bool)
+    print('split of check() (median per class), XH_FLOW_LOOK_ALWAYS=%s: drain + counter loads | polls that polled | rest of check() | '
+          'cycles per check in the drain | checks that asked for a counter, of %d' % (os.environ.get('XH_FLOW_LOOK_ALWAYS', '0'), n_checks))
+    for name, pl, sel in classes + [('top 10', 64, top), ('pair+outlet', 0, pairx)]:
+        if not sel.any():
+            continue
+        med = lambda x: np.median(x[sel])
+        print('%-11s %-6s n=%4d | %5.2f | %5.2f | %5.2f | %6.0f | %4.0f' % (
+            name, 'single' if pl else 'pair', sel.sum(), med(p_drain / nsub), med(p_poll / nsub), med((p_check - p_drain - p_poll) / nsub),
+            med(p_drain / n_checks), med(n_looks)))
     pu = np.nonzero((shape & 64) == 0)[0] if pipe.plan.rsum_info()['pair_cells'] >= 0 else []
     for u in pu:
         og = groups - zg[u]

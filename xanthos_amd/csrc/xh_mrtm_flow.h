@@ -99,5 +99,7 @@ int wave_launch(xh_ctx *ctx, FlowPlan *fp, const FlowSched &s, const FlowIO &io,
 const void *wave_rsum_kernel();      // k_mrtm_rsum (xh_mrtm_rsum.hip): the kernel wave_launch starts for a reassociated plan
 const void *wave_exact_kernel();     // k_mrtm_wave (xh_mrtm_wave.hip)
 // Per-unit cycle accounting of the last launch (only when XH_FLOW_STATS=1): 6 words per unit
-// {shader cycles in sub-step loops, shader cycles total, 100 MHz ticks total, shape bits, data-wait, ring-wait cycles}.
+// {shader cycles in sub-step loops, shader cycles total, 100 MHz ticks total, shape bits, data-wait, ring-wait cycles}; the
+// time-skewed kernels keep the cycles in bits 0-35 of the last two and count above them the checks that looked at the stream
+// counter (36-49) and those the known value covered (50-63): check() of xh_mrtm_wave_unit.h.
 int flow_stats_fetch(xh_ctx *ctx, FlowPlan *fp, std::vector<unsigned long long> &out);

@@ -209,6 +209,7 @@ int wave_launch(xh_ctx *ctx, FlowPlan *fp, const FlowSched &s, const FlowIO &io,
     }
     a.fold_cell = static_cast<const int *>(fp->d_fold_cell.p);
     a.linear = xh_env_on("XH_RSUM_LINEAR", true) ? 1 : 0;      // A/B switch: 0 makes the linear units run the clamping step
+    a.look_always = xh_env_on("XH_FLOW_LOOK_ALWAYS", false) ? 1 : 0;      // A/B switch: 1 makes every check() load both stream counters
     if (!fp->d_skew_args) XH_HIP(ctx, hipMalloc(&fp->d_skew_args, sizeof(WaveArgs) + 256));
     // stream-ordered: the previous launch has finished reading the block before this one rewrites it
     hipLaunchKernelGGL(k_mrtm_wave_args, dim3(1), dim3(256), 0, st, a, static_cast<WaveArgs *>(fp->d_skew_args),

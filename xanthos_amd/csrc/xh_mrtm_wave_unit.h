@@ -12,6 +12,7 @@
 #include <type_traits>
 
 #include "xh_mrtm_flow.h"
+#include "xh_mrtm_flowctl.h"
 #include "xh_mrtm_rec.h"
 
 namespace {
@@ -78,6 +79,7 @@ struct WaveArgs {
     unsigned long long *stats;
     const int *fold_cell;             // (at the end: k_mrtm_rsum only) [units*64] the leaf cell a lane carries besides its own, or -1; NULL: none
     int linear;                       // k_mrtm_rsum: 1 = units marked linear (unit_p bit 5) run the clamp-free step; 0 (XH_RSUM_LINEAR=0): they clamp
+    int look_always;                  // XH_FLOW_LOOK_ALWAYS=1: check() asks for both stream counters every time, needed or not (A/B: see check())
 };
 
 __device__ __forceinline__ unsigned ld_relaxed(const unsigned *p) {
@@ -444,7 +446,23 @@ __device__ __forceinline__ void wave_unit(WaveArgsK *ap, char *lds_generic, uint
             __builtin_amdgcn_s_sleep(16);
         }
     };
-    unsigned long long cyc_wait_data = 0, cyc_wait_ring = 0, zone_groups = 0;
+    unsigned long long zone_groups = 0;
+    // check()'s accounting (XH_FLOW_STATS=1 only: `stats` is set).  The cycles of a check and whether it looked at a counter are
+    // ADDED to the unit's words st[4] / st[5] in memory at the end of that check, by an atomic that returns nothing: an ordinary
+    // run holds neither the timer reads nor an accumulator in registers through the sub-step loops.  A word is
+    // {cycles: bits 0-35, checks that looked at the counter: 36-49, checks at which the known value covered the need: 50-63}.
+    constexpr unsigned long long ST_CYC_MASK = (1ull << 36) - 1ull;
+    constexpr int ST_LOOK_SHIFT = 36, ST_COVER_SHIFT = 50;
+    if (A(stats) && lane == 0) {
+        unsigned long long *st = A(stats) + (int64_t)unit * 6;
+        st[4] = 0;
+        st[5] = 0;
+    }
+#ifdef XH_WAVE_PROFILE      // the diagnostic build keeps its accumulators in registers; st[4] / st[5] mean something else there
+    // prof_drain: check()'s statement that waits for the wave's memory operations, with the counter loads it asks for;
+    // prof_poll: the waits for a counter that did have to poll; prof_looks: checks that asked for at least one counter
+    unsigned long long cyc_wait_data = 0, cyc_wait_ring = 0, prof_drain = 0, prof_poll = 0, prof_looks = 0;
+#endif
     const unsigned long long cyc_begin = __builtin_amdgcn_s_memtime();
     const unsigned long long rt_begin = __builtin_amdgcn_s_memrealtime();
 
@@ -462,34 +480,66 @@ __device__ __forceinline__ void wave_unit(WaveArgsK *ap, char *lds_generic, uint
     //      XCD's L2.  No release / acquire fences.  Evidence: every full-size launch of the test suite bit-identical to
     //      the oracle, XH_ROUTE_VALIDATE (the same call routed by the barrier-only kernel and compared on the device),
     //      two contexts routing concurrently, the fuzzers; a violation would show as a wrong bit, a lost wake-up as a
-    //      bounded-wait fault.  Each check asks for both counters FIRST, in front of the wait for the wave's memory operations
-    //      that it begins with anyway, and first looks at those values; only if they do not cover its needs does it poll.
-    //      The two loads and the wait are ONE asm statement: its outputs are defined when it ends, so no register of a load
+    //      bounded-wait fault.  Each check asks for the counters it has to LOOK at (below) FIRST, in front of the wait for the
+    //      wave's memory operations that it begins with anyway, and first looks at those values; only if they do not cover its
+    //      needs does it poll.
+    //      The loads and the wait are ONE asm statement: its outputs are defined when it ends, so no register of a load
     //      in flight exists outside it and nothing the register allocator does around a loop header can read one early.
     //      (Until the linear units: the counters were asked for at the END of a check for the next one, CH sub-steps ahead,
     //      in registers that stayed in flight across the unrolled loops -- 31 sites in the ISA where such a register was
     //      copied at a loop header with no wait between the load and the copy: profiles/pace/ab.txt, profiles/linear_units.)
     //      Counters only grow, so a value read before the wait is merely conservative.
+    //      WHEN A UNIT LOOKS (xh_mrtm_flowctl.h).  `seen_ready` / `seen_done` keep the last value each lane read: a lower bound
+    //      of the counter for ever after.  A check asks for a counter only if some lane has the stream kind and what it last
+    //      saw does not cover what the next CH iterations need (need > seen) -- a unit behind faster producers, or ahead of
+    //      consumers that keep up, runs thousands of sub-steps (the rings hold 4,096 - 8,192) on one look.  The statement
+    //      that begins a check therefore has four forms, chosen by two uniform conditions: both loads + the wait, either
+    //      load + the wait, the bare wait.  What a unit PUBLISHES is unchanged -- the wait, then its `ready` store and its
+    //      `done` store, at every check -- so its partners see it exactly as fresh as before; only its own looks are rarer.
+    //      XH_FLOW_LOOK_ALWAYS=1 (A/B, diagnosis): both counters at every check, as until profiles/check_path.
     unsigned seen_ready = 0, seen_done = 0;
     auto check = [&](int n) {
-        const unsigned long long w0 = __builtin_amdgcn_s_memtime();
+#ifdef XH_WAVE_PROFILE
+        constexpr bool timed = true;
+#else
+        const bool timed = A(stats) != nullptr;      // uniform; an ordinary run reads no timer here
+#endif
+        unsigned long long w0 = 0, w1 = 0;
+        if (timed) w0 = __builtin_amdgcn_s_memtime();
         unsigned now_ready = 0, now_done = 0;
+        const unsigned need_done = fc_need_done(n, CH, lmax, A(rs), total);
+        const unsigned need_ready = fc_need_ready(n, CH, GROUP, lag_g, total);
+        const bool look_always = A(look_always) != 0;
+        const bool look_done = any_x && (look_always || __any(fc_look(has_x, need_done, seen_done)));
+        const bool look_ready = any_g && (look_always || __any(fc_look(has_g, need_ready, seen_ready)));
         // Round 5, the default since: EVERY memory operation of the wave has been acknowledged before the counter
         // store -- `s_waitcnt vmcnt(0)` in front of the flag, the guide's measured `sc1` hand-off form, without the L2 write-back
         // of a release fence; the import loads two blocks ahead are simply waited for.  Priced on both kernels, same box,
         // alternating (profiles/round5/fence_mid_ab.txt): 15.08 - 15.38 against 15.16 - 15.36 ms (reassociated), 22.0 - 22.9
         // against 22.3 - 23.0 (bit-exact) -- nothing; the full release / acquire pair costs +76 % / +40 % (XH_ROUTE_FENCED=1).
         // (Until round 4: all but the 8 youngest operations + a publication lag of 64 sub-steps.)
-        // The counters ride under that wait (a unit without streams asks for none).  Both loads, whichever the unit needs:
-        // done_p / ready_p of a unit without outlets / imports point at word 0 of their arrays, which lie in one block with
-        // the placement words behind them (wave_launch), so the address is always inside it.
-        if (any_x || any_g)
+        // The counters the unit has to look at ride under that wait (a unit without streams asks for none, and neither does
+        // one whose known values cover its needs).  Every lane loads: done_p / ready_p of a lane without an outlet / import
+        // point at word 0 of their arrays, which lie in one block with the placement words behind them (wave_launch), so the
+        // address is always inside it.
+#ifdef XH_WAVE_PROFILE
+        const unsigned long long d0 = __builtin_amdgcn_s_memtime();
+#endif
+        if (look_done && look_ready)
             asm volatile("global_load_dword %0, %2, off sc1\n\tglobal_load_dword %1, %3, off sc1\n\ts_waitcnt vmcnt(0)"
                          : "=&v"(now_done), "=&v"(now_ready)
                          : "v"(done_p), "v"(ready_p)
                          : "memory");
+        else if (look_done)
+            asm volatile("global_load_dword %0, %1, off sc1\n\ts_waitcnt vmcnt(0)" : "=&v"(now_done) : "v"(done_p) : "memory");
+        else if (look_ready)
+            asm volatile("global_load_dword %0, %1, off sc1\n\ts_waitcnt vmcnt(0)" : "=&v"(now_ready) : "v"(ready_p) : "memory");
         else
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#ifdef XH_WAVE_PROFILE
+        prof_drain += __builtin_amdgcn_s_memtime() - d0;
+        prof_looks += (look_done || look_ready) ? 1u : 0u;
+#endif
         if (SGL == 2) gsgl |= (xlane && fmin_seen < -SGL_XEPS) ? 4u : 0u;
         if (LIN) gsgl |= (smin_seen < -SGL_EPS) ? 8u : 0u;
         if ((FOLD && __any(gfold != 0)) || (SGL != 0 && __any(gsgl != 0))) {      // a folded leaf that can fire after all, a single-sum plan made for other data: the host routes again on the plan of pairs
@@ -507,24 +557,52 @@ __device__ __forceinline__ void wave_unit(WaveArgsK *ap, char *lds_generic, uint
             // new box / build is cross-checked against the barrier-only kernel instead (xh_mrtm.hip, first_check_*).
             if (fenced) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
             if (has_x) __hip_atomic_store(A(ready) + xedge, (unsigned)pub, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const int need = n + CH - lmax - A(rs);
-            seen_done = max(seen_done, now_done);
-            if (need > 0 && alive)
-                alive = wave_wait_ge(has_x, done_p, (unsigned)min(need, total), seen_done, A(fault), FAULT_RING_WAIT);
+            seen_done = max(seen_done, now_done);      // (no look: now_done is 0)
+            if (need_done > 0 && alive) {
+#ifdef XH_WAVE_PROFILE
+                const bool polls = __any(fc_look(has_x, need_done, seen_done));
+                const unsigned long long p0 = __builtin_amdgcn_s_memtime();
+#endif
+                alive = wave_wait_ge(has_x, done_p, need_done, seen_done, A(fault), FAULT_RING_WAIT);
+#ifdef XH_WAVE_PROFILE
+                if (polls) prof_poll += __builtin_amdgcn_s_memtime() - p0;
+#endif
+            }
         }
-        const unsigned long long w1 = __builtin_amdgcn_s_memtime();
+        if (timed) w1 = __builtin_amdgcn_s_memtime();
         if (any_g && alive) {   // the next CH iterations load up to sub-step n + CH + GROUP - 1 - lag_g
             if (lane == 0)    // every import has been consumed up to n - glmax
                 __hip_atomic_store(A(done) + unit, (unsigned)min(max(n - glmax, 0), total), __ATOMIC_RELAXED,
                                    __HIP_MEMORY_SCOPE_AGENT);
-            const int need = min(total, n + CH + GROUP - lag_g);
-            seen_ready = max(seen_ready, now_ready);
-            alive = wave_wait_ge(has_g && need > 0, ready_p, (unsigned)max(need, 0), seen_ready, A(fault), FAULT_DATA_WAIT);
+            seen_ready = max(seen_ready, now_ready);   // (no look: now_ready is 0)
+#ifdef XH_WAVE_PROFILE
+            const bool polls = __any(fc_look(has_g, need_ready, seen_ready));
+            const unsigned long long p0 = __builtin_amdgcn_s_memtime();
+#endif
+            alive = wave_wait_ge(has_g && need_ready > 0, ready_p, need_ready, seen_ready, A(fault), FAULT_DATA_WAIT);
+#ifdef XH_WAVE_PROFILE
+            if (polls) prof_poll += __builtin_amdgcn_s_memtime() - p0;
+#endif
             if (fenced) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
             asm volatile("" ::: "memory");      // the stream loads stay behind the poll
         }
+#ifdef XH_WAVE_PROFILE
         cyc_wait_ring += w1 - w0;
         cyc_wait_data += __builtin_amdgcn_s_memtime() - w1;
+#else
+        if (timed) {      // (the brackets charge the whole body of a check, whether or not anything was waited for)
+            const unsigned long long w2 = __builtin_amdgcn_s_memtime();
+            if (lane == 0) {
+                unsigned long long *st = A(stats) + (int64_t)unit * 6;
+                const unsigned long long ring = ((w1 - w0) & ST_CYC_MASK) |
+                                                (any_x ? 1ull << (look_done ? ST_LOOK_SHIFT : ST_COVER_SHIFT) : 0ull);
+                const unsigned long long data = ((w2 - w1) & ST_CYC_MASK) |
+                                                (any_g ? 1ull << (look_ready ? ST_LOOK_SHIFT : ST_COVER_SHIFT) : 0ull);
+                __hip_atomic_fetch_add(st + 5, ring, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_fetch_add(st + 4, data, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        }
+#endif
     };
 
     // ---- month bookkeeping for all lanes at once: outputs of iteration it - 1, lateral inflow of iteration it + 1.
@@ -931,6 +1009,12 @@ __device__ __forceinline__ void wave_unit(WaveArgsK *ap, char *lds_generic, uint
     if (A(stats) && lane == 0) {
         unsigned long long *st = A(stats) + (int64_t)unit * 6;
         const unsigned long long cyc = __builtin_amdgcn_s_memtime() - cyc_begin;
+#ifndef XH_WAVE_PROFILE
+        // what the checks added to st[4] / st[5] (check()); the words stay as they are: cycles and the two counts of looks
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        const unsigned long long cyc_wait_data = __hip_atomic_load(st + 4, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & ST_CYC_MASK;
+        const unsigned long long cyc_wait_ring = __hip_atomic_load(st + 5, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & ST_CYC_MASK;
+#endif
         st[0] = cyc - cyc_wait_data - cyc_wait_ring;
         st[1] = cyc;
         st[2] = __builtin_amdgcn_s_memrealtime() - rt_begin;
@@ -945,11 +1029,13 @@ __device__ __forceinline__ void wave_unit(WaveArgsK *ap, char *lds_generic, uint
         st[3] |= ((unsigned long long)ng << 24) | ((unsigned long long)nx_out << 29) | (LIN ? 1ull << 34 : 0ull) |
                  (NXR >= 0 ? 1ull << 35 : 0ull) | (1ull << 63);
 #endif
-        st[4] = cyc_wait_data;
-        st[5] = cyc_wait_ring;
 #ifdef XH_WAVE_PROFILE
-        st[0] = prof_plain;      // cycles in groups without a month boundary
-        st[4] = prof_zone;       // cycles in boundary groups (their number: st[3] >> 44)
+        // low halves: cycles in groups without a month boundary; in boundary groups (their number: st[3] >> 44).  High halves:
+        // the split of check() -- the statement that drains the wave's memory operations, with the counter loads it asked
+        // for; the waits for a counter that had to poll.  st[3] bits 24-39: checks that asked for a counter.
+        st[0] = (prof_plain & 0xffffffffull) | (prof_drain << 32);
+        st[4] = (prof_zone & 0xffffffffull) | (prof_poll << 32);
+        st[3] |= (prof_looks < 0xffffull ? prof_looks : 0xffffull) << 24;
         // 32 bits each (a launch is some 3e7 cycles): the whole run and the waits inside the checks; the checks with their waits
         // and the housekeeping; finalize() and the zone exits
         st[1] = (cyc & 0xffffffffull) | ((cyc_wait_data + cyc_wait_ring) << 32);
