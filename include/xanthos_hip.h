@@ -690,6 +690,38 @@ int xh_extremes(xh_ctx *ctx, int64_t nrows, int32_t row_stride, int32_t col0, in
                 int32_t nT, const double *h_T, const double *d_x, const double *d_par_in, double *d_table, double *d_annual,
                 double *d_T_year);
 
+/* ------------------------------------------------------------------ bootstrap intervals of the return levels
+ * xh_extremes_boot replaces NO function of the reference.  Per row r of d_x (the window as in xh_extremes) it writes
+ * d_ci[r, 0 .. 3 + 2 nT) = nb, k_lo, k_hi, x_T1_lo, x_T1_hi, ... and, when d_rep is not NULL, d_rep[r, b, 0 .. 5 + nT) = l1*, l2*,
+ * t3*, t4*, k*, q*_T... of replicate b = 0 .. B - 1 in z's sign (a test and diagnosis output).  No operation is contracted.
+ *   1 The row: the annual series, the counted sort zs[0 .. n), the L-moments and the fit of xh_extremes, steps 1 - 3.  A row
+ *     without a fit gets nb = 0 and NaN everywhere else, and no replicate is drawn for it.
+ *   2 Draws, mod 2^64, splitmix64(x): z = x + 0x9E3779B97F4A7C15; z = (z ^ z >> 30) 0xBF58476D1CE4E5B9; z = (z ^ z >> 27)
+ *     0x94D049BB133111EB; z ^ z >> 31.  h_row = splitmix64(seed ^ ((uint64)(row0 + r) * 0xD1342543DE82EF95));  h_rep =
+ *     splitmix64(h_row ^ (uint64)(b + 1));  word(m) = splitmix64(h_rep ^ (uint64)(m + 1));  draw i of replicate b takes u32 = the
+ *     low 32 bits of word(i >> 1) for even i, the high 32 bits for odd i;  j_i = (u32 * (uint64)n) >> 32, i = 0 .. n - 1, an
+ *     index into zs (its bias: a cell's probability is off by at most n / 2^32 of itself).  The draws depend on (seed,
+ *     row0 + r, b, i) alone: rows [a, b) of a call equal the call on that slice with row0 = a, and the replicates b < B1 of a
+ *     call with B2 > B1 are those of the call with B1.
+ *   3 A replicate's sample is the multiset {zs[j_i]} sorted ascending; its b_0 .. b_3, l1 .. l4, t3, t4 are step 2 of xh_extremes
+ *     on it (formed by walking the counts c_j = #{i : j_i = j} over ascending j: equal values are interchangeable, the bits
+ *     are a sort's), its fit follows the same rules (not constant, l2 > 0, t3 <= 1 - 2^-20, k > -1 and finite) through the
+ *     same functions.  nb = the replicates with a fit.
+ *   4 p_lo = (1 - confidence) / 2, p_hi = 1 - p_lo.  For k and each return level, the nb values sorted ascending, numpy's
+ *     `linear` quantile: h = (nb - 1) p, lo = floor(h), hi = min(lo + 1, nb - 1), g = h - lo, d = a[hi] - a[lo], g < 0.5 ?
+ *     a[lo] + d g : a[hi] - d (1 - g).  Reported in the variable's own sign with lo <= hi: for min the level bounds are
+ *     -Q(p_hi) and -Q(p_lo); k's interval is that of z's k.  nb < ceil(B / 2): every bound NaN, nb still reported.
+ * csrc/xh_exboot_dev.h holds this definition for device and host.  One one-wavefront workgroup per row at a time, lane <->
+ * replicate; no atomics, nothing crosses a workgroup, every trip count known at launch, a fixed order: two calls give the
+ * same bytes whatever the grid.  Scratch slot 2 holds (1 + nT) B doubles per workgroup.
+ * XH_ERR_ARG: what xh_extremes refuses, B outside 2..2048, confidence not strictly between 0 and 1, row0 < 0; each message
+ * names its value.  Nothing is launched then.  Asynchronous on the context's stream, timer "extremes_boot"; h_T is read
+ * before the call returns; nothing is uploaded.                                                                        */
+#define XH_EXB_MAX_B 2048
+int xh_extremes_boot(xh_ctx *ctx, int64_t nrows, int32_t row_stride, int32_t col0, int32_t nyear, int32_t kind, int32_t min_years,
+                     int32_t nT, const double *h_T, int32_t B, double confidence, uint64_t seed, int64_t row0, const double *d_x,
+                     double *d_ci, double *d_rep);
+
 /* The same objective for SEVERAL basins in one launch, each basin with its own population: one basin alone is only
  * months x ~1.7 us of dependent chain, far too little to fill the chip.  h_ncell [nbasins]; h_pars [nbasins, nmembers,
  * npar]; h_pet_t / h_precip_t / h_tmin_t / h_area: host arrays of nbasins DEVICE pointers ([nmonths, ncell_b] each;

@@ -215,6 +215,8 @@ SIGNATURES = {
                              POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p)]),
     'xh_trend': (c_int, [_P, c_int64, c_int32, c_int32, c_int32, c_int32, c_double, _P, _P]),
     'xh_extremes': (c_int, [_P, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P, _P, _P, _P, _P]),
+    'xh_extremes_boot': (c_int, [_P, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _P, c_int32, c_double, c_uint64,
+                                 c_int64, _P, _P, _P]),
     'xh_synth_forcing': (c_int, [_P, c_uint64, c_double, c_int64, c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
 }
 
@@ -924,6 +926,19 @@ class Context:
         self._check(lib().xh_extremes(self.handle, int(nrows), int(row_stride), int(col0), int(nyear), int(kind), int(min_years),
                                       int(T.size), T.ctypes.data_as(c_void_p) if T.size else None, _dptr(x), _dptr(par_in),
                                       _dptr(table), _dptr(annual), _dptr(T_year)))
+
+    def extremes_boot(self, nrows, row_stride, col0, nyear, kind, min_years, return_periods, B, confidence, seed, x, ci, rep=None,
+                      row0=0):
+        """Bootstrap intervals of the GEV shape and the return levels of the window of ``extremes`` (xh_extremes_boot, which
+        states the definition): ``B`` replicates (2 .. 2048) of every row's annual series, drawn from ``seed`` and the row's
+        number ``row0 + r``, refitted, and the percentiles (1 -+ ``confidence``) / 2 of the refitted values: ``ci`` [nrows,
+        3 + 2 nT] = nb, k_lo, k_hi, x_T_lo, x_T_hi, ...; ``rep`` [nrows, B, 5 + nT] or None: every replicate's l1, l2, t3, t4, k and
+        levels.  DeviceArrays or raw device addresses.  Asynchronous."""
+        T = np.ascontiguousarray(return_periods, dtype=np.float64).ravel()
+        kind = EXTREMES_KIND.get(kind, kind) if isinstance(kind, str) else kind
+        self._check(lib().xh_extremes_boot(self.handle, int(nrows), int(row_stride), int(col0), int(nyear), int(kind), int(min_years),
+                                           int(T.size), T.ctypes.data_as(c_void_p) if T.size else None, int(B), float(confidence),
+                                           int(seed), int(row0), _dptr(x), _dptr(ci), _dptr(rep)))
 
     # ---- bench support
     def synth_forcing(self, seed, ncell, nmonths, lat, out, nan_frac=0.001, cell_ids=None):

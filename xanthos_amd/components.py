@@ -458,7 +458,9 @@ class Components:
         """Extremes of [Extremes] (not in the reference): annual maxima or minima per cell of the run's runoff, PET, AET, soil
         moisture, routed flow or precipitation, the GEV fitted to them by L-moments, return levels and every year's return
         period, from the arrays in HBM.  Leaves the result as the ATTRIBUTE ``extremes`` of this object, {(var, kind):
-        {'table': [ncell, 8 + nT], 'annual': [ncell, nyear], 'return_period': [ncell, nyear]}}, in place of this method."""
+        {'table': [ncell, 8 + nT], 'annual': [ncell, nyear], 'return_period': [ncell, nyear]}}, in place of this method; with
+        ``bootstrap`` in the section (the settings' ``extremes_bootstrap``, which Extremes reads) every entry also holds 'ci':
+        [ncell, 3 + 2 nT], the bootstrap intervals of the shape and the return levels."""
         if getattr(self.s, 'CalculateExtremes', 0) and self.is_root:
             from .extremes import Extremes
             logging.info('---Start Extremes:')

@@ -1,1 +1,1 @@
-from .extremes import COLUMNS, KINDS, RETURN_PERIODS, VARS, Extremes, extremes_rows, output_stem  # noqa: F401
+from .extremes import CI_COLUMNS, COLUMNS, KINDS, RETURN_PERIODS, VARS, Extremes, bootstrap_rows, extremes_rows, output_stem  # noqa: F401

@@ -242,6 +242,7 @@ class ConfigReader:
             raise ValidationException("CalculateExtremes must be 0 or 1, not '{}'".format(raw_ex))
         self.CalculateExtremes = int(raw_ex)
         self.extremes = None
+        self.extremes_bootstrap = None
         if self.CalculateExtremes:
             if not isinstance(c.get('Extremes'), dict):
                 raise ValidationException('CalculateExtremes = 1 but the config file has no [Extremes] section.')
@@ -837,9 +838,13 @@ class ConfigReader:
         year of the window start); year_start_month (1 - 12, default 1: a hydrological year runs from that month to the month
         before it a year later, and the last one must end inside the run); min_years (default 10, at least 5): the years a
         fit needs; parameters (optional) = <OutputFolder>/<OutputNameStr> of a historic run, whose tables stand in for the
-        fit.  Kept as ``self.extremes``; 'parameters' there is {(var, kind): file} or None."""
+        fit.  Kept as ``self.extremes``; 'parameters' there is {(var, kind): file} or None.
+        bootstrap (100 - 2048; absent or 0: off) = the replicates of the percentile-bootstrap confidence intervals of the shape
+        and the return levels, confidence (default 0.90, strictly between 0 and 1) their level, bootstrap_seed
+        (default 1, a whole number >= 0) what the draws start from.  Kept apart as ``self.extremes_bootstrap``: None or {'B',
+        'confidence', 'seed'}.  Not together with parameters: a handed-in fit has no sample of this run to resample."""
         import numpy as np
-        from .extremes.extremes import KINDS, MAX_COLS, MAX_PERIODS, MIN_YEARS, MIN_YEARS_DEFAULT, RETURN_PERIODS, VARS, parameter_file
+        from .extremes.extremes import BOOTSTRAP_MAX, BOOTSTRAP_MIN, CONFIDENCE_DEFAULT, KINDS, MAX_COLS, MAX_PERIODS, MIN_YEARS, MIN_YEARS_DEFAULT, RETURN_PERIODS, VARS, parameter_file
 
         def refuse(key, why):
             raise ValidationException('[Extremes] {} {}'.format(key, why))
@@ -925,6 +930,37 @@ class ConfigReader:
                         refuse('parameters', '= {}: {} has shape {}, the run needs [{}, 8 or more] (cells; n, l1, l2, t3, t4, k, '
                                'alpha, xi).'.format(stem, path, tuple(shape), self.ncell))
                     files[(v, kind)] = path
+        boot = None
+        raw_b = cfg.get('bootstrap')
+        try:
+            nboot = 0 if raw_b in (None, '') else int(str(raw_b).strip())
+        except (TypeError, ValueError):
+            nboot = -1
+        if nboot != 0 and not BOOTSTRAP_MIN <= nboot <= BOOTSTRAP_MAX:
+            refuse('bootstrap', '= {!r} must be a whole number of replicates, {} - {} (0 or absent: no intervals).'.format(
+                raw_b, BOOTSTRAP_MIN, BOOTSTRAP_MAX))
+        if nboot == 0:
+            for key in ('confidence', 'bootstrap_seed'):
+                if cfg.get(key) not in (None, ''):
+                    refuse(key, '= {!r} belongs to the bootstrap intervals, and the section asks for none (bootstrap).'.format(cfg.get(key)))
+        else:
+            if files is not None:
+                refuse('bootstrap', '= {} and parameters exclude each other: a handed-in fit has no sample of this run to '
+                       'resample.'.format(nboot))
+            try:
+                confidence = float(cfg.get('confidence', CONFIDENCE_DEFAULT))
+            except (TypeError, ValueError):
+                confidence = 0.0
+            if not 0.0 < confidence < 1.0:
+                refuse('confidence', '= {!r} must be a number strictly between 0 and 1.'.format(cfg.get('confidence')))
+            try:
+                bseed = int(str(cfg.get('bootstrap_seed', 1)).strip())
+            except (TypeError, ValueError):
+                bseed = -1
+            if not 0 <= bseed < 2 ** 64:
+                refuse('bootstrap_seed', '= {!r} must be a whole number, 0 or more (below 2^64).'.format(cfg.get('bootstrap_seed')))
+            boot = {'B': nboot, 'confidence': confidence, 'seed': bseed}
+        self.extremes_bootstrap = boot
         self.extremes = {'vars': evars, 'kinds': kinds, 'return_periods': periods, 'start_year': years['start_year'],
                          'end_year': years['end_year'], 'year_start_month': month, 'min_years': min_years, 'parameters': files}
 
