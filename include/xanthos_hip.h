@@ -722,6 +722,46 @@ int xh_extremes_boot(xh_ctx *ctx, int64_t nrows, int32_t row_stride, int32_t col
                      int32_t nT, const double *h_T, int32_t B, double confidence, uint64_t seed, int64_t row0, const double *d_x,
                      double *d_ci, double *d_rep);
 
+/* ------------------------------------------------------------------ flow duration curve and regime signatures
+ * xh_signatures replaces NO function of the reference: xanthos has no flow signatures.  Per row r of d_x (nrows rows of
+ * row_stride doubles) the window is x[0 .. 12 nyear) = d_x[r, col0 ..); column t has calendar month (cal0 + t) mod 12, 0 =
+ * January; year y is columns 12 y .. 12 y + 11.  Every element enters as x + 0.0 (-0.0 counts as +0.0); a NaN or +-inf element is
+ * left out of everything.  No operation is contracted.
+ *   S256(f): lane l of 256 adds f(t) from 0.0 over the included t = l, l + 256, ... in ascending order; the 256 partial sums are
+ *     joined by the tree of xh_block_sum256 (csrc/xh_kge.h).  A "pair" is (t, t + 1) with both elements included.  "Sequential":
+ *     from 0.0 in ascending index order.
+ *   Q(p): the n included values sorted ascending a[0 .. n), numpy's `linear` quantile: h = (n - 1) p, lo = floor(h), hi =
+ *     min(lo + 1, n - 1), g = h - lo, d = a[hi] - a[lo], g < 0.5 ? a[lo] + d g : a[hi] - d (1 - g).
+ *   xbar_m = (the sequential sum over ascending t of the included elements of calendar month m) / c_m, c_m their count;
+ *     R = the sequential sum over m = 0 .. 11 of xbar_m;  C, S = the sequential sums over m of xbar_m COS[m], xbar_m SIN[m], COS
+ *     and SIN the correctly rounded doubles of cos and sin of pi (2 m + 1) / 12.  A_y = the sequential sum of the 12 months of
+ *     year y, for the years whose 12 months are all included.
+ *   d_table[r, 0 .. 18):
+ *      0 n   1 n_zero = #{x == 0}   2 mean = S256(x) / n   3 std = sqrt(S256((x - mean)^2) / (n - 1)), NaN for n < 2
+ *      4 cv = std / mean   5 median = Q(0.5)
+ *      6 lag1 = S256 over pairs((x_t - mean)(x_{t+1} - mean)) / S256((x - mean)^2), NaN for n < 2
+ *      7 flashiness = S256 over pairs(|x_{t+1} - x_t|) / S256(x)   (Richards-Baker)
+ *      8 fdc_slope = (log Q(0.67) - log Q(0.34)) / 0.33, NaN when Q(0.34) is not > 0
+ *      9 regime_total = R   10 peak_month, 11 low_month = 1 + the first m of the largest, the smallest xbar_m
+ *     12 seasonality = (sequential sum over m of |xbar_m - R / 12.0|) / R   (Walsh & Lawler 1981)
+ *     13 centroid = atan2(S, C) (6 / pi), plus 12.0 if negative: months from 1 January, 0.5 = mid-January
+ *     14 concentration = sqrt(C C + S S) / R   (Markham 1970)
+ *     15 n_years = the complete years   16 annual_mean = (sequential sum of A_y) / n_years
+ *     17 annual_cv = sqrt((sequential sum of (A_y - annual_mean)^2) / (n_years - 1)) / annual_mean, NaN for n_years < 2
+ *     Columns 9 - 14 are NaN when any c_m = 0.  With n = 0 only n, n_zero and n_years are numbers, the rest is NaN.
+ *   d_fdc (NULL: none) [nrows, nP]: Q(h_prob[j]), NaN for n = 0.   d_regime (NULL: none) [nrows, 12]: xbar_m, NaN where c_m = 0.
+ * csrc/xh_signatures_dev.h holds this definition for device and host.  One 256-lane workgroup per row at a time, the row in
+ * LDS padded to a power of two P, a bitonic sort in place; no atomics, nothing crosses a workgroup, every trip count known at
+ * launch, a fixed order: two calls give the same bytes whatever the grid.  LDS per workgroup: (P + 800 + nyear) doubles.
+ * XH_ERR_ARG: a NULL d_x or d_table (or h_prob with nP > 0), col0 < 0, col0 + 12 nyear > row_stride, nyear < 1, 12 nyear > 4096,
+ * cal0 outside 0..11, nP outside 0..16, a probability not strictly between 0 and 1; each message names its value.  Nothing is
+ * launched then.  Asynchronous on the context's stream, timer "signatures"; h_prob is read before the call returns; nothing is
+ * uploaded.                                                                                                             */
+#define XH_SIG_NCOL 18
+#define XH_SIG_MAX_P 16
+int xh_signatures(xh_ctx *ctx, int64_t nrows, int32_t row_stride, int32_t col0, int32_t nyear, int32_t cal0, int32_t nP,
+                  const double *h_prob, const double *d_x, double *d_table, double *d_fdc, double *d_regime);
+
 /* The same objective for SEVERAL basins in one launch, each basin with its own population: one basin alone is only
  * months x ~1.7 us of dependent chain, far too little to fill the chip.  h_ncell [nbasins]; h_pars [nbasins, nmembers,
  * npar]; h_pet_t / h_precip_t / h_tmin_t / h_area: host arrays of nbasins DEVICE pointers ([nmonths, ncell_b] each;

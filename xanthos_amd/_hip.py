@@ -217,6 +217,7 @@ SIGNATURES = {
     'xh_extremes': (c_int, [_P, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P, _P, _P, _P, _P]),
     'xh_extremes_boot': (c_int, [_P, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _P, c_int32, c_double, c_uint64,
                                  c_int64, _P, _P, _P]),
+    'xh_signatures': (c_int, [_P, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P, _P, _P, _P]),
     'xh_synth_forcing': (c_int, [_P, c_uint64, c_double, c_int64, c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
 }
 
@@ -939,6 +940,19 @@ class Context:
         self._check(lib().xh_extremes_boot(self.handle, int(nrows), int(row_stride), int(col0), int(nyear), int(kind), int(min_years),
                                            int(T.size), T.ctypes.data_as(c_void_p) if T.size else None, int(B), float(confidence),
                                            int(seed), int(row0), _dptr(x), _dptr(ci), _dptr(rep)))
+
+    # ---- flow duration curve and regime signatures per row (csrc/xh_signatures.hip)
+    def signatures(self, nrows, row_stride, col0, nyear, cal0, probabilities, x, table, fdc=None, regime=None):
+        """Flow duration curve and regime signatures of the monthly window ``x[r, col0 : col0 + 12 nyear]`` of every row of ``x``
+        [nrows, row_stride], whose first column is calendar month ``cal0`` (0 = January) (xh_signatures, which states the
+        definition): ``table`` [nrows, 18] = n, n_zero, mean, std, cv, median, lag1, flashiness, fdc_slope, regime_total,
+        peak_month, low_month, seasonality, centroid, concentration, n_years, annual_mean, annual_cv; ``fdc`` [nrows, nP] or
+        None: the linear quantiles of ``probabilities`` (at most 16, each strictly between 0 and 1); ``regime`` [nrows, 12]
+        or None: the calendar months' means.  DeviceArrays or raw device addresses.  Asynchronous."""
+        p = np.ascontiguousarray(probabilities, dtype=np.float64).ravel()
+        self._check(lib().xh_signatures(self.handle, int(nrows), int(row_stride), int(col0), int(nyear), int(cal0), int(p.size),
+                                        p.ctypes.data_as(c_void_p) if p.size else None, _dptr(x), _dptr(table), _dptr(fdc),
+                                        _dptr(regime)))
 
     # ---- bench support
     def synth_forcing(self, seed, ncell, nmonths, lat, out, nan_frac=0.001, cell_ids=None):

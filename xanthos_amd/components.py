@@ -331,6 +331,7 @@ class Components:
         c.__dict__.pop('drought_index', None)          # (the result of drought_index() stands in the method's place)
         c.__dict__.pop('trend', None)                  # (... and that of trend())
         c.__dict__.pop('extremes', None)               # (... and that of extremes())
+        c.__dict__.pop('signatures', None)             # (... and that of signatures())
         return c
 
     def _pipeline_args(self, runoff, um, cells=None):
@@ -479,6 +480,28 @@ class Components:
             self.extremes = results
             logging.info('---Extremes has finished successfully: %s seconds ------' % (time.time() - t0))
 
+    def signatures(self):
+        """Signatures of [Signatures] (not in the reference): the flow duration curve, the variability, persistence and
+        seasonality signatures and the annual totals' variation per cell of the run's runoff, PET, AET, soil moisture, routed
+        flow or precipitation, from the arrays in HBM.  Leaves the result as the ATTRIBUTE ``signatures`` of this object,
+        {var: {'table': [ncell, 18], 'fdc': [ncell, nP], 'regime': [ncell, 12]}}, in place of this method."""
+        if getattr(self.s, 'CalculateSignatures', 0) and self.is_root:
+            from .signatures import Signatures
+            logging.info('---Start Signatures:')
+            t0 = time.time()
+
+            def result(attr):
+                if self.pipe is not None and attr not in self._host:
+                    return self.pipe.out[_RESULTS[attr]]
+                return getattr(self, attr)
+            rows_of = {'q': self._runoff, 'avgchflow': self._routed_flow, 'precip': lambda: self._precipitation('precip', 'Signatures'),
+                       'pet': lambda: result('PET'), 'aet': lambda: result('AET'), 'soilmoisture': lambda: result('Sav')}
+            results = {}
+            for var in self.s.signatures['vars']:
+                results[var] = Signatures(self.s, var, rows_of[var]()).results
+            self.signatures = results
+            logging.info('---Signatures has finished successfully: %s seconds ------' % (time.time() - t0))
+
     def _precipitation(self, var, section='DroughtIndex'):
         """The run's precipitation [ncell, nmonths] for SPI / SPEI: the forcing array in HBM after a device-resident
         simulation, the loader's host array after a run that went stage by stage.  On a sharded run every rank's pipeline
@@ -490,7 +513,7 @@ class Components:
         if rows is None or tuple(rows.shape) != (self.s.ncell, self.s.nmonths):
             raise ValidationException("[{}] {} = {} needs the run's whole precipitation array on one GPU: in a run "
                                       "sharded over several GPUs every rank holds its own cells' rows only.".format(
-                                          section, {'DroughtIndex': 'index_var', 'Extremes': 'extreme_vars'}.get(section, 'trend_vars'), var))
+                                          section, {'DroughtIndex': 'index_var', 'Extremes': 'extreme_vars', 'Signatures': 'signature_vars'}.get(section, 'trend_vars'), var))
         return rows
 
     def accessible_water(self):

@@ -247,6 +247,16 @@ class ConfigReader:
             if not isinstance(c.get('Extremes'), dict):
                 raise ValidationException('CalculateExtremes = 1 but the config file has no [Extremes] section.')
             self.configure_extremes(c['Extremes'])
+        # [Signatures] (not in the reference): the flow duration curve and the flow-regime signatures per cell
+        raw_sg = str(p.get('CalculateSignatures', 0)).strip()
+        if raw_sg not in ('0', '1'):
+            raise ValidationException("CalculateSignatures must be 0 or 1, not '{}'".format(raw_sg))
+        self.CalculateSignatures = int(raw_sg)
+        self.signatures = None
+        if self.CalculateSignatures:
+            if not isinstance(c.get('Signatures'), dict):
+                raise ValidationException('CalculateSignatures = 1 but the config file has no [Signatures] section.')
+            self.configure_signatures(c['Signatures'])
 
     # ------------------------------------------------------------------ modules
     def configure_pet(self, cfg):
@@ -963,6 +973,81 @@ class ConfigReader:
         self.extremes_bootstrap = boot
         self.extremes = {'vars': evars, 'kinds': kinds, 'return_periods': periods, 'start_year': years['start_year'],
                          'end_year': years['end_year'], 'year_start_month': month, 'min_years': min_years, 'parameters': files}
+
+    def configure_signatures(self, cfg):
+        """[Signatures] (not a section of the reference; signatures/signatures.py): signature_vars = a list from q | pet | aet |
+        soilmoisture | avgchflow | precip; exceedance (default 1, 5, 10, 20, 50, 80, 90, 95, 99; at most 16, different, each
+        strictly between 0 and 100) = the percents of the time whose exceeded values make the duration curve; start_year /
+        end_year (default: the run's; the years in which the first and the last year of the window start); year_start_month
+        (1 - 12, default 1: the window starts in that month, and its last year must end inside the run).  Kept as
+        ``self.signatures``."""
+        from .signatures.signatures import EXCEEDANCE, MAX_COLS, MAX_EXCEEDANCE, VARS
+
+        def refuse(key, why):
+            raise ValidationException('[Signatures] {} {}'.format(key, why))
+
+        known = ('signature_vars', 'exceedance', 'start_year', 'end_year', 'year_start_month')
+        for key in cfg:
+            if key not in known:
+                refuse(key, 'is not a key of the section; it knows {}.'.format(', '.join(known)))
+        if self.calibrate:
+            refuse('and Calibrate = 1', 'exclude each other: a calibration writes no outputs to take signatures of.')
+        if getattr(self, 'ensemble', None) is not None:
+            refuse('and an [Ensemble] section', 'exclude each other: per-member signatures are not implemented.')
+        if getattr(self, 'OutputInYear', 0) == 1:
+            refuse('and OutputInYear = 1', 'exclude each other: the signatures are those of the monthly series.')
+        raw = cfg.get('signature_vars')
+        raw = [] if raw in (None, '') else (raw if isinstance(raw, list) else [raw])
+        svars = [str(w).strip().lower() for w in raw]
+        if not svars or len(set(svars)) != len(svars) or any(v not in VARS for v in svars):
+            refuse('signature_vars', '= {!r} must be different names from {}.'.format(cfg.get('signature_vars'), ', '.join(VARS)))
+        if 'avgchflow' in svars and self.routing_module != 'mrtm':
+            refuse('signature_vars', "= avgchflow is the routed channel flow: the run needs routing_module = mrtm, not '{}'.".format(
+                self.routing_module))
+        for v in svars:
+            if v in ('q', 'aet', 'soilmoisture', 'precip') and self.runoff_module == 'none':
+                refuse('signature_vars', "= {} comes from (precip: is loaded by) the runoff module: the run needs a runoff_module, "
+                       "not 'none'.".format(v))
+            if v == 'pet' and self.pet_module == 'none':
+                refuse('signature_vars', "= pet is the PET module's result: the run needs a pet_module, not 'none'.")
+        percents = [float(p) for p in EXCEEDANCE]
+        if cfg.get('exceedance') not in (None, ''):
+            raw = cfg.get('exceedance')
+            try:
+                percents = [float(w) for w in (raw if isinstance(raw, list) else [raw])]
+            except (TypeError, ValueError):
+                percents = []
+            if not percents or len(percents) > MAX_EXCEEDANCE or len(set(percents)) != len(percents) or not all(
+                    0.0 < p < 100.0 and 0.0 < (100.0 - p) / 100.0 < 1.0 for p in percents):
+                refuse('exceedance', '= {!r} must be at most {} different percents, each strictly between 0 and 100.'.format(
+                    raw, MAX_EXCEEDANCE))
+        try:
+            month = int(cfg.get('year_start_month', 1))
+        except (TypeError, ValueError):
+            month = 0
+        if not 1 <= month <= 12:
+            refuse('year_start_month', '= {!r} must be a month, 1 - 12.'.format(cfg.get('year_start_month')))
+        # the last year that starts in month `month` and ends inside the run
+        last_start = self.EndYear if month == 1 else self.EndYear - 1
+        years = {}
+        for key, default in (('start_year', self.StartYear), ('end_year', last_start)):
+            try:
+                years[key] = int(cfg.get(key, default))
+            except (TypeError, ValueError):
+                refuse(key, '= {!r} is not a year.'.format(cfg.get(key)))
+            if not self.StartYear <= years[key] <= self.EndYear:
+                refuse(key, '= {} lies outside the years of the run, {} - {}.'.format(years[key], self.StartYear, self.EndYear))
+        if years['end_year'] > last_start:
+            refuse('end_year', '= {}: the year that starts in month {} of {} ends after the run ({}); the last complete one '
+                   'starts in {}.'.format(years['end_year'], month, years['end_year'], self.EndYear, last_start))
+        nyears = years['end_year'] - years['start_year'] + 1
+        if nyears < 1:
+            refuse('end_year', '= {} lies before start_year = {}.'.format(years['end_year'], years['start_year']))
+        if 12 * nyears > MAX_COLS:
+            refuse('end_year', '= {}: the window {} - {} has {} months, more than the {} one row may take.'.format(
+                years['end_year'], years['start_year'], years['end_year'], 12 * nyears, MAX_COLS))
+        self.signatures = {'vars': svars, 'exceedance': percents, 'start_year': years['start_year'],
+                           'end_year': years['end_year'], 'year_start_month': month}
 
     @staticmethod
     def ck_obs_unit(set_calib, unit):

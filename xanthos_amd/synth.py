@@ -736,6 +736,19 @@ def enable_extremes(ini, extreme_vars=('q',), kinds=('max', 'min'), **keys):
     return ini
 
 
+def with_signatures(ini, signature_vars=('q',), **keys):
+    """Switch the flow signatures on in an .ini written by one of the example writers: ``CalculateSignatures = 1`` in [Project]
+    and a [Signatures] section with ``signature_vars`` and whatever else is given (``exceedance`` -- a sequence is joined by
+    commas --, ``start_year``, ``end_year``, ``year_start_month``) as written."""
+    text = open(ini).read()
+    text = text.replace('\n[PET]', '\nCalculateSignatures = 1\n\n[PET]', 1)
+    text += '\n[Signatures]\nsignature_vars = {}\n'.format(', '.join(signature_vars))
+    for k, v in keys.items():
+        text += '{} = {}\n'.format(k, ', '.join(str(w) for w in v) if isinstance(v, (list, tuple)) else v)
+    open(ini, 'w').write(text)
+    return ini
+
+
 def write_diag_inputs(root, world, seed=17, nvic=30, dir_name='diagnostics'):
     """Write the four comparison tables of the diagnostics (the reference's DiagDir, ini_reader.py:439-445) matched to
     ``world`` under ``root``/input/``dir_name`` and return its path.
