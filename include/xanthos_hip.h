@@ -762,6 +762,53 @@ int xh_extremes_boot(xh_ctx *ctx, int64_t nrows, int32_t row_stride, int32_t col
 int xh_signatures(xh_ctx *ctx, int64_t nrows, int32_t row_stride, int32_t col0, int32_t nyear, int32_t cal0, int32_t nP,
                   const double *h_prob, const double *d_x, double *d_table, double *d_fdc, double *d_regime);
 
+/* ------------------------------------------------------------------ water balance and Budyko signatures
+ * xh_water_balance replaces NO function of the reference: xanthos has no signatures of two variables.  Per row r of d_p, d_pet,
+ * d_q and d_aet (NULL: none; nrows rows of row_stride doubles each) the window is columns col0 .. col0 + 12 nyear; year y is
+ * columns 12 y .. 12 y + 11 of it.  Every element enters as x + 0.0.  Month t is INCLUDED when every array given is finite at t;
+ * a year is COMPLETE when its 12 months are included.  No operation is contracted.
+ *   A^v_y, v in {P, PET, AET, Q}: the sequential sum (from 0.0, ascending) of the 12 months of a complete year.
+ *   Y256(f): lane l of 256 adds f(y) from 0.0 over the complete years y = l, l + 256, ... in ascending order; the 256 partial
+ *     sums are joined by the tree of xh_block_sum256 (csrc/xh_kge.h).  S256(f): the same over the included months.
+ *   n_years = the complete years; vbar = Y256(A^v) / n_years; dv_y = A^v_y - vbar.
+ *   d_table[r, 0 .. 21):
+ *      0 n_years   1 n_months = the included months   2 p_mean = pbar   3 pet_mean = petbar   4 aet_mean = aetbar (NaN without
+ *      d_aet)   5 q_mean = qbar   6 runoff_ratio = qbar / pbar   7 aridity = phi = petbar / pbar   8 evaporative = aetbar / pbar
+ *      9 residual = (pbar - aetbar) - qbar, the implied storage change per year   10 closure = residual / pbar
+ *     11 omega = Fu's parameter: the omega > 1 with fu(phi, omega) = eps, eps = (pbar - qbar) / pbar
+ *     12 budyko_dev = eps - fu(phi, omega0)
+ *     13 elast_p = the median (the values sorted ascending, numpy's `linear` rule at 0.5 as xh_signatures writes it) of
+ *        e_y = (dQ_y / dP_y) (pbar / qbar) over the complete years with dP_y != 0; 14 elast_pet the same with dPET_y and petbar;
+ *        NaN when qbar is not > 0 or no year qualifies      (Sankarasubramanian et al. 2001)
+ *     15 elast_p_ls = b1, 16 elast_pet_ls = b2: with x1 = dP_y / pbar, x2 = dPET_y / petbar, z = dQ_y / qbar and the Y256 sums
+ *        s11 = x1 x1, s12 = x1 x2, s22 = x2 x2, s1z = x1 z, s2z = x2 z: det = s11 s22 - s12 s12,
+ *        b1 = (s1z s22 - s2z s12) / det, b2 = (s2z s11 - s1z s12) / det; NaN unless n_years >= 3 and det > 0
+ *     17 r_pq = Y256(dP dQ) / sqrt(Y256(dP dP) Y256(dQ dQ)), NaN unless the product is > 0
+ *     18 dry_fraction = #{included t: P_t < PET_t} / n_months
+ *     19 lag_peak = the first k in 0 .. max_lag with the largest c_k, 20 r_peak = that c_k; NaN when no c_k is a number, with
+ *        mP = S256(P) / n_months, mQ = S256(Q) / n_months and c_k = S256 over the t with t and t + k both included
+ *        ((P_t - mP) (Q_{t+k} - mQ)) / sqrt(S256((P - mP)^2) S256((Q - mQ)^2))
+ *   d_xcorr (NULL: none) [nrows, max_lag + 1]: c_k.   d_annual (NULL: none) [nrows, 4, nyear]: A^v_y, NaN for a year that is not
+ *   complete, the AET plane NaN without d_aet.
+ *   Fu's curve in a form that neither overflows nor cancels: lo = min(1, phi), m = max(1, phi), r = lo / m,
+ *     g(omega) = log1p(exp(omega log r)) / omega, fu(phi, omega) = lo - m expm1(g(omega)); NaN when phi is NaN.  omega solves
+ *     m expm1(g(omega)) = lo - eps by exactly 60 bisection steps on s = log(omega - 1) over [log 2^-20, log 2^7], always all of
+ *     them, and is 1 + exp(the last interval's midpoint); NaN unless 0 < eps < lo and the target lies strictly between the
+ *     function's values at the two ends.
+ *   With n_years = 0 only columns 0, 1, 18, 19 and 20 may be numbers.  A ratio whose denominator is 0 follows IEEE.  Every column
+ *   but omega and budyko_dev is comparisons, + - x / and sqrt in this order: the same bits from the host and the device build.
+ * csrc/xh_wbalance_dev.h holds this definition for device and host.  One 256-lane workgroup per row at a time, P and Q in LDS;
+ * no atomics, nothing crosses a workgroup, every trip count known at launch, a fixed order: two calls give the same bytes
+ * whatever the grid.  LDS per workgroup: (28 nyear + 2 P2 + 1808) doubles, P2 the power of two >= nyear.
+ * XH_ERR_ARG: a NULL d_p, d_pet, d_q or d_table, col0 < 0, col0 + 12 nyear > row_stride, nyear < 1, 12 nyear > 4096, max_lag
+ * outside 0..12, omega0 not finite or not > 1; each message names its value.  Nothing is launched then.  Asynchronous on the
+ * context's stream, timer "water_balance"; nothing is uploaded.                                                         */
+#define XH_WB_NCOL 21
+#define XH_WB_MAX_LAG 12
+int xh_water_balance(xh_ctx *ctx, int64_t nrows, int32_t row_stride, int32_t col0, int32_t nyear, int32_t max_lag, double omega0,
+                     const double *d_p, const double *d_pet, const double *d_q, const double *d_aet, double *d_table,
+                     double *d_annual, double *d_xcorr);
+
 /* The same objective for SEVERAL basins in one launch, each basin with its own population: one basin alone is only
  * months x ~1.7 us of dependent chain, far too little to fill the chip.  h_ncell [nbasins]; h_pars [nbasins, nmembers,
  * npar]; h_pet_t / h_precip_t / h_tmin_t / h_area: host arrays of nbasins DEVICE pointers ([nmonths, ncell_b] each;

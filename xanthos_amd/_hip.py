@@ -218,6 +218,7 @@ SIGNATURES = {
     'xh_extremes_boot': (c_int, [_P, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _P, c_int32, c_double, c_uint64,
                                  c_int64, _P, _P, _P]),
     'xh_signatures': (c_int, [_P, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P, _P, _P, _P]),
+    'xh_water_balance': (c_int, [_P, c_int64, c_int32, c_int32, c_int32, c_int32, c_double, _P, _P, _P, _P, _P, _P, _P]),
     'xh_synth_forcing': (c_int, [_P, c_uint64, c_double, c_int64, c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
 }
 
@@ -953,6 +954,18 @@ class Context:
         self._check(lib().xh_signatures(self.handle, int(nrows), int(row_stride), int(col0), int(nyear), int(cal0), int(p.size),
                                         p.ctypes.data_as(c_void_p) if p.size else None, _dptr(x), _dptr(table), _dptr(fdc),
                                         _dptr(regime)))
+
+    # ---- water balance and Budyko signatures per row (csrc/xh_wbalance.hip)
+    def water_balance(self, nrows, row_stride, col0, nyear, max_lag, omega0, precip, pet, q, aet, table, annual=None, xcorr=None):
+        """Water balance and Budyko signatures of the monthly window ``[r, col0 : col0 + 12 nyear]`` of every row of ``precip``,
+        ``pet``, ``q`` and ``aet`` (or None) [nrows, row_stride] (xh_water_balance, which states the definition): ``table``
+        [nrows, 21] = n_years, n_months, p_mean, pet_mean, aet_mean, q_mean, runoff_ratio, aridity, evaporative, residual,
+        closure, omega, budyko_dev, elast_p, elast_pet, elast_p_ls, elast_pet_ls, r_pq, dry_fraction, lag_peak, r_peak;
+        ``annual`` [nrows, 4, nyear] or None: the annual totals of P, PET, AET and Q; ``xcorr`` [nrows, max_lag + 1] or None:
+        the correlation of P with Q ``k`` months later.  DeviceArrays or raw device addresses.  Asynchronous."""
+        self._check(lib().xh_water_balance(self.handle, int(nrows), int(row_stride), int(col0), int(nyear), int(max_lag),
+                                           float(omega0), _dptr(precip), _dptr(pet), _dptr(q), _dptr(aet), _dptr(table),
+                                           _dptr(annual), _dptr(xcorr)))
 
     # ---- bench support
     def synth_forcing(self, seed, ncell, nmonths, lat, out, nan_frac=0.001, cell_ids=None):

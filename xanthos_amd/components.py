@@ -332,6 +332,7 @@ class Components:
         c.__dict__.pop('trend', None)                  # (... and that of trend())
         c.__dict__.pop('extremes', None)               # (... and that of extremes())
         c.__dict__.pop('signatures', None)             # (... and that of signatures())
+        c.__dict__.pop('water_balance', None)          # (... and that of water_balance())
         return c
 
     def _pipeline_args(self, runoff, um, cells=None):
@@ -502,6 +503,30 @@ class Components:
             self.signatures = results
             logging.info('---Signatures has finished successfully: %s seconds ------' % (time.time() - t0))
 
+    def water_balance(self):
+        """Water balance of [WaterBalance] (not in the reference): the runoff ratio, the aridity and evaporative index, the
+        closure of the balance, Fu's parameter and the departure from a Budyko curve, the elasticities of runoff to
+        precipitation and to PET and the lag of runoff behind precipitation, per cell and per basin, from the run's
+        precipitation, PET, AET and runoff in HBM.  Leaves the result as the ATTRIBUTE ``water_balance`` of this object,
+        {level: {'table': [n, 21], 'annual': [n, 4, nyear], 'xcorr': [n, max_lag + 1]}}, in place of this method."""
+        if getattr(self.s, 'CalculateWaterBalance', 0) and self.is_root:
+            from .waterbalance import WaterBalance
+            logging.info('---Start Water Balance:')
+            t0 = time.time()
+
+            def result(attr):
+                if self.pipe is not None and attr not in self._host:
+                    return self.pipe.out[_RESULTS[attr]]
+                return getattr(self, attr)
+            precip = self._precipitation('precip', 'WaterBalance')
+            aet = result('AET') if self.s.runoff_module in ('abcd', 'gwam') else None     # (handed in when the run makes it)
+            results = {}
+            for level in self.s.water_balance['levels']:
+                results[level] = WaterBalance(self.s, level, precip, result('PET'), self._runoff(), aet, area=self.data.area,
+                                              basin_ids=self.data.basin_ids).results
+            self.water_balance = results
+            logging.info('---Water Balance has finished successfully: %s seconds ------' % (time.time() - t0))
+
     def _precipitation(self, var, section='DroughtIndex'):
         """The run's precipitation [ncell, nmonths] for SPI / SPEI: the forcing array in HBM after a device-resident
         simulation, the loader's host array after a run that went stage by stage.  On a sharded run every rank's pipeline
@@ -513,7 +538,7 @@ class Components:
         if rows is None or tuple(rows.shape) != (self.s.ncell, self.s.nmonths):
             raise ValidationException("[{}] {} = {} needs the run's whole precipitation array on one GPU: in a run "
                                       "sharded over several GPUs every rank holds its own cells' rows only.".format(
-                                          section, {'DroughtIndex': 'index_var', 'Extremes': 'extreme_vars', 'Signatures': 'signature_vars'}.get(section, 'trend_vars'), var))
+                                          section, {'DroughtIndex': 'index_var', 'Extremes': 'extreme_vars', 'Signatures': 'signature_vars', 'WaterBalance': 'levels'}.get(section, 'trend_vars'), var))
         return rows
 
     def accessible_water(self):

@@ -35,6 +35,7 @@ class ConfigRunner:
         c.trend()                     # ([Trend], not in the reference: Mann-Kendall test and Theil-Sen slope per cell)
         c.extremes()                  # ([Extremes], not in the reference: GEV by L-moments, return levels and periods per cell)
         c.signatures()                # ([Signatures], not in the reference: flow duration curve and regime signatures per cell)
+        c.water_balance()             # ([WaterBalance], not in the reference: water balance and Budyko signatures per cell and basin)
         c.hydropower_potential()
         c.hydropower_actual()
         c.evaluate()                  # ([Evaluate], not in the reference: the routed flow scored at stream gauges)

@@ -217,6 +217,9 @@ def validate(config, members, statistics=(), statistics_vars=None, member_output
     if getattr(s, 'CalculateSignatures', 0):
         raise refuse(None, 'CalculateSignatures', 'the signatures of [Signatures] belong to one run; per-member signatures are '
                      'not implemented: run the ensemble with CalculateSignatures = 0')
+    if getattr(s, 'CalculateWaterBalance', 0):
+        raise refuse(None, 'CalculateWaterBalance', 'the water balance of [WaterBalance] belongs to one run; per-member water '
+                     'balances are not implemented: run the ensemble with CalculateWaterBalance = 0')
     env_gpus = int(os.environ.get('XH_GPUS') or 1)
     if (gpus and int(gpus) > 1) or env_gpus > 1 or launch.env_world()[2] > 1:
         raise refuse(None, 'gpus', 'members dealt over several GPUs are not implemented; run the ensemble on one GPU')

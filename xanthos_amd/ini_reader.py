@@ -257,6 +257,16 @@ class ConfigReader:
             if not isinstance(c.get('Signatures'), dict):
                 raise ValidationException('CalculateSignatures = 1 but the config file has no [Signatures] section.')
             self.configure_signatures(c['Signatures'])
+        # [WaterBalance] (not in the reference): water balance and Budyko signatures per cell and per basin
+        raw_wb = str(p.get('CalculateWaterBalance', 0)).strip()
+        if raw_wb not in ('0', '1'):
+            raise ValidationException("CalculateWaterBalance must be 0 or 1, not '{}'".format(raw_wb))
+        self.CalculateWaterBalance = int(raw_wb)
+        self.water_balance = None
+        if self.CalculateWaterBalance:
+            if not isinstance(c.get('WaterBalance'), dict):
+                raise ValidationException('CalculateWaterBalance = 1 but the config file has no [WaterBalance] section.')
+            self.configure_water_balance(c['WaterBalance'])
 
     # ------------------------------------------------------------------ modules
     def configure_pet(self, cfg):
@@ -1048,6 +1058,82 @@ class ConfigReader:
                 years['end_year'], years['start_year'], years['end_year'], 12 * nyears, MAX_COLS))
         self.signatures = {'vars': svars, 'exceedance': percents, 'start_year': years['start_year'],
                            'end_year': years['end_year'], 'year_start_month': month}
+
+    def configure_water_balance(self, cfg):
+        """[WaterBalance] (not a section of the reference; waterbalance/waterbalance.py): levels = a list from cell | basin
+        (default cell); start_year / end_year (default: the run's; the years in which the first and the last year of the window
+        start); year_start_month (1 - 12, default 1: the window starts in that month, and its last year must end inside the
+        run); max_lag (0 - 12, default 6: the largest lag of runoff behind precipitation, in months); omega0 (> 1, default 2.6:
+        Fu's parameter of the curve budyko_dev is measured from); annual = 1 | 0 (default 0: also write the annual totals).
+        Kept as ``self.water_balance``."""
+        from .waterbalance.waterbalance import LEVELS, MAX_COLS, MAX_LAG, OMEGA0
+
+        def refuse(key, why):
+            raise ValidationException('[WaterBalance] {} {}'.format(key, why))
+
+        known = ('levels', 'start_year', 'end_year', 'year_start_month', 'max_lag', 'omega0', 'annual')
+        for key in cfg:
+            if key not in known:
+                refuse(key, 'is not a key of the section; it knows {}.'.format(', '.join(known)))
+        if self.calibrate:
+            refuse('and Calibrate = 1', 'exclude each other: a calibration writes no outputs to take a water balance of.')
+        if getattr(self, 'ensemble', None) is not None:
+            refuse('and an [Ensemble] section', 'exclude each other: per-member water balances are not implemented.')
+        if getattr(self, 'OutputInYear', 0) == 1:
+            refuse('and OutputInYear = 1', 'exclude each other: the water balance is that of the monthly series.')
+        if self.runoff_module == 'none':
+            refuse('and runoff_module = none', 'exclude each other: the run needs a runoff_module, which makes the runoff and loads '
+                   'the precipitation.')
+        if self.pet_module == 'none':
+            refuse('and pet_module = none', "exclude each other: the run needs a pet_module, which makes the PET.")
+        raw = cfg.get('levels', 'cell')
+        raw = [] if raw in (None, '') else (raw if isinstance(raw, list) else [raw])
+        levels = [str(w).strip().lower() for w in raw]
+        if not levels or len(set(levels)) != len(levels) or any(v not in LEVELS for v in levels):
+            refuse('levels', '= {!r} must be different names from {}.'.format(cfg.get('levels'), ', '.join(LEVELS)))
+        try:
+            month = int(cfg.get('year_start_month', 1))
+        except (TypeError, ValueError):
+            month = 0
+        if not 1 <= month <= 12:
+            refuse('year_start_month', '= {!r} must be a month, 1 - 12.'.format(cfg.get('year_start_month')))
+        # the last year that starts in month `month` and ends inside the run
+        last_start = self.EndYear if month == 1 else self.EndYear - 1
+        years = {}
+        for key, default in (('start_year', self.StartYear), ('end_year', last_start)):
+            try:
+                years[key] = int(cfg.get(key, default))
+            except (TypeError, ValueError):
+                refuse(key, '= {!r} is not a year.'.format(cfg.get(key)))
+            if not self.StartYear <= years[key] <= self.EndYear:
+                refuse(key, '= {} lies outside the years of the run, {} - {}.'.format(years[key], self.StartYear, self.EndYear))
+        if years['end_year'] > last_start:
+            refuse('end_year', '= {}: the year that starts in month {} of {} ends after the run ({}); the last complete one '
+                   'starts in {}.'.format(years['end_year'], month, years['end_year'], self.EndYear, last_start))
+        nyears = years['end_year'] - years['start_year'] + 1
+        if nyears < 2:
+            refuse('end_year', '= {} with start_year = {}: the window has {} years, and the water balance needs at least 2.'.format(
+                years['end_year'], years['start_year'], nyears))
+        if 12 * nyears > MAX_COLS:
+            refuse('end_year', '= {}: the window {} - {} has {} months, more than the {} one row may take.'.format(
+                years['end_year'], years['start_year'], years['end_year'], 12 * nyears, MAX_COLS))
+        try:
+            max_lag = int(cfg.get('max_lag', 6))
+        except (TypeError, ValueError):
+            max_lag = -1
+        if not 0 <= max_lag <= MAX_LAG:
+            refuse('max_lag', '= {!r} must be a whole number of months, 0 - {}.'.format(cfg.get('max_lag'), MAX_LAG))
+        try:
+            omega0 = float(cfg.get('omega0', OMEGA0))
+        except (TypeError, ValueError):
+            omega0 = float('nan')
+        if not (omega0 > 1.0 and omega0 != float('inf')):
+            refuse('omega0', "= {!r} must be a finite number > 1 (Fu's parameter).".format(cfg.get('omega0')))
+        raw_annual = str(cfg.get('annual', 0)).strip()
+        if raw_annual not in ('0', '1'):
+            refuse('annual', "= {!r} must be 0 or 1.".format(cfg.get('annual')))
+        self.water_balance = {'levels': levels, 'start_year': years['start_year'], 'end_year': years['end_year'],
+                              'year_start_month': month, 'max_lag': max_lag, 'omega0': omega0, 'annual': int(raw_annual)}
 
     @staticmethod
     def ck_obs_unit(set_calib, unit):

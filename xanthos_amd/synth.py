@@ -749,6 +749,19 @@ def with_signatures(ini, signature_vars=('q',), **keys):
     return ini
 
 
+def with_water_balance(ini, levels=('cell',), **keys):
+    """Switch the water balance on in an .ini written by one of the example writers: ``CalculateWaterBalance = 1`` in [Project]
+    and a [WaterBalance] section with ``levels`` and whatever else is given (``start_year``, ``end_year``, ``year_start_month``,
+    ``max_lag``, ``omega0``, ``annual``) as written."""
+    text = open(ini).read()
+    text = text.replace('\n[PET]', '\nCalculateWaterBalance = 1\n\n[PET]', 1)
+    text += '\n[WaterBalance]\nlevels = {}\n'.format(', '.join(levels))
+    for k, v in keys.items():
+        text += '{} = {}\n'.format(k, ', '.join(str(w) for w in v) if isinstance(v, (list, tuple)) else v)
+    open(ini, 'w').write(text)
+    return ini
+
+
 def write_diag_inputs(root, world, seed=17, nvic=30, dir_name='diagnostics'):
     """Write the four comparison tables of the diagnostics (the reference's DiagDir, ini_reader.py:439-445) matched to
     ``world`` under ``root``/input/``dir_name`` and return its path.
